@@ -9,8 +9,8 @@
              The network is the reference's `Network` record -- an op and its parameters, no
              activation tags -- driven through gradTOp; the launches it collapses into are found
              by the library in the class-method stream (csrc/lazy.cpp).  --steps K steps are
-             timed in each of 5 back-to-back regions (barrier + synchronize on both sides of
-             each, max over ranks); value comes from the MEDIAN region, all five are listed.
+             timed in one region (barrier + synchronize on both sides, max over ranks); with
+             --full in each of 5 back-to-back regions, value from the MEDIAN one, all listed.
              On N GPUs every rank steps its own 1024-row shard of a 1024*N global batch
              (config 4) with one RCCL all-reduce of the flat weight gradients per step, so
              the job completes N shard-steps per synchronised iteration ("weak" scaling).
@@ -21,9 +21,16 @@
   cpu_baseline  the oracle's plain-C restatement of the reference's per-sample HMat path
              (single thread) on a bounded sample of the same workload.
 
+A plain run measures `value` and nothing else.  roofline, extra, cpu_baseline, the steady-state
+and device-time figures and, for N>1, the N = 1 rate and the config-4 parity check run only with
+--full.
+
 Inputs are synthetic (seed 0x7e500001) and resident in HBM before the timed region.
-Usage: python bench.py [--gpus N --steps K --warmup W]; for N>1 launch through
-`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`.
+--dump-outputs DIR writes the parameters the last timed step produced (what Trainer.step hands
+its caller) as DIR/<name>.npy, float32: identical arguments give identical inputs, so two builds
+can be compared output for output.
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]; for N>1
+launch through `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`.
 """
 import argparse
 import ctypes as C
@@ -665,10 +672,17 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=1024, help="rows per GPU (BASELINE config 3)")
-    ap.add_argument("--no-aux", action="store_true", help="skip gmul / map / cpu_baseline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline: the gmul / map / fp64 / online legs, cpu_baseline, "
+                         "steady_state, the device time of the step, five timed regions, and for N>1 the N = 1 rate and "
+                         "the config-4 parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the parameters after the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip gmul / map / cpu_baseline legs")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--regions", type=int, default=5, help="timed regions of --steps steps each (value = median)")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of --steps steps each (value = median); default 1, 5 with --full")
     ap.add_argument("--collective", choices=["auto", "torch", "direct", "p2p"], default="auto",
                     help="all-reduce transport.  auto (default): both C-ABI transports are set up, probed and timed, the "
                          "one that measured faster here (slowest rank's latency) carries the step.  "
@@ -686,6 +700,8 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) and all-reduce even at world size 1 (self-test)")
     args = ap.parse_args()
+    nregions = max(1, args.regions if args.regions is not None else (5 if args.full else 1))
+    aux = args.full and not args.no_aux
 
     # stdout carries ONE JSON line.  gloo and RCCL print banners on the C-level stdout (RCCL's arrive when its
     # buffers flush at exit), so file descriptor 1 is pointed at stderr for the whole run and the line is written
@@ -753,7 +769,7 @@ def main():
         # (DataParallel.capture), so the trainer issues directly; at N = 1 the trainer replays its own capture
         whole_step_capture = dist is not None and world > 1 and args.collective != "torch" and not args.no_graph
         n1 = None
-        if dist is not None and world > 1:
+        if dist is not None and world > 1 and args.full:
             # this rank's N = 1 rate, measured in this run (same protocol: regions of --steps steps, median), on a net of its
             # own: what `weak_scaling_efficiency` in the JSON line is relative to
             net1 = tops.genNet([(T.put(w), T.put(b)) for w, b in ws], "actMapLogistic", "actSoftmax")
@@ -761,7 +777,7 @@ def main():
             for _ in range(max(args.warmup, 5)):
                 tr1.step()
             r1 = []
-            for _ in range(max(1, args.regions)):
+            for _ in range(nregions):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(args.steps):
@@ -797,21 +813,24 @@ def main():
             if step_captured and not flag.item():
                 dp.release()
             step_captured = bool(flag.item())
-        for _ in range(args.warmup):
+        launches = None
+        for i in range(args.warmup):
+            if i == args.warmup - 1:
+                l0 = T.stats()["launches"]
             dp.step()
-        l0 = T.stats()["launches"]
-        dp.step()
-        launches = T.stats()["launches"] - l0   # kernels per step (the collective, if any, not counted)
+        if args.warmup:
+            launches = T.stats()["launches"] - l0   # kernels per step (the collective, if any, not counted)
         # Each region: barrier + synchronize, EXACTLY --steps steps, synchronize + barrier; max over ranks.
-        # A region of 20 steps is ~0.6 ms: one region swings by 10 % from run to run, the median of five does not.
+        # A region of 20 steps is ~0.6 ms: one region swings by 10 % from run to run, the median of five (--full) does not.
         # Round 5: nothing but the steps sits between the two synchronisations.  The two device-timer events bench.py used
         # to record INSIDE the region (for step.device_ms_per_step) cost 24 us per region -- 1.2 us a step at 20 steps
         # (tools/region_probe.py: 536 vs 513 us for 20 steps) -- and torch.cuda.synchronize(), a device-wide wait, another
         # ~40 us when it is the call that has to notice the stream going idle; the library's own stream wait (to_sync) goes
         # first, so the device-wide one that brackets the region finds the device idle.  The device time of a region is
-        # measured on an untimed twin region right after each timed one.
+        # measured on an untimed twin region right after each timed one (--full).
         regions, dev_regions = [], []
-        for _ in range(max(1, args.regions)):
+        outputs = None
+        for k in range(nregions):
             if dist is not None:
                 dist.barrier()
             torch.cuda.synchronize()
@@ -823,10 +842,13 @@ def main():
             if dist is not None:
                 dist.barrier()
             el = time.perf_counter() - t0
-            T.timer_start()                      # (the untimed twin: device time of --steps steps, HIP events on the launch stream)
-            for _ in range(args.steps):
-                dp.step()
-            dev_regions.append(T.timer_stop())
+            if args.dump_outputs and rank == 0 and k == nregions - 1:
+                outputs = [p.numpy() for p in tr.net.params]   # before any untimed step moves them on
+            if args.full:
+                T.timer_start()                  # (the untimed twin: device time of --steps steps, HIP events on the launch stream)
+                for _ in range(args.steps):
+                    dp.step()
+                dev_regions.append(T.timer_stop())
             if dist is not None:
                 tmax = torch.tensor([el], dtype=torch.float64,
                                     device="cpu" if dist.get_backend() == "gloo" else "cuda")
@@ -836,7 +858,7 @@ def main():
         # the same step in regions long enough for the fixed cost of a region's two ends to vanish (200 steps): a separately
         # named figure, never `value` -- `value` is what the driver's protocol (--steps K, regions of exactly K steps) gives
         steady = None
-        if world == 1 and not args.no_aux:
+        if world == 1 and aux:
             rs = []
             for _ in range(3):
                 torch.cuda.synchronize()
@@ -883,7 +905,7 @@ def main():
                              "not compute a training step's arithmetic on meaningful numbers")
         order = sorted(range(len(regions)), key=lambda k: regions[k])
         mid = order[len(order) // 2]
-        elapsed, dev_ms = regions[mid], dev_regions[mid]
+        elapsed, dev_ms = regions[mid], (dev_regions[mid] if dev_regions else None)
 
         # N > 1: the first line a multi-GPU box produces is also the first config-4 parity evidence.
         # After the timed regions the replicated parameters are reset to the initial ones, THREE data-parallel steps run
@@ -891,7 +913,7 @@ def main():
         # parameters with a single-GPU replay of the same three steps on the full batch (world x rows) at 1e-5 --
         # the check of tests/test_gpu_multi.py:72-80; replicas must be bit-identical.
         c4 = None
-        if dist is not None and world > 1:
+        if dist is not None and world > 1 and args.full:
             def flat_of(params):
                 out, off = np.zeros(nflat, dtype=np.float32), 0
                 for p in params:
@@ -985,14 +1007,15 @@ def main():
                          else "separate launch after the all-reduce",
                          "graph_replay": not args.no_graph, "library_fusion": tr.fused,
                          "rate": rate, "params_finite_after_timed_region": params_finite,
-                         "device_ms_per_step": round(dev_ms / args.steps, 5),
                          "algorithmic_flops": STEP_FLOPS * args.batch // 1024,
-                         "tflops": round(STEP_FLOPS * args.batch / 1024 / (dev_ms / args.steps) / 1e9, 3),
-                         "frac_mfma": round(STEP_FLOPS * args.batch / 1024 / (dev_ms / args.steps) / 1e9
-                                            / PEAK_MFMA_F32_TF, 4),
                          "note": "latency-bound: ~5 MB working set, 0.84 GFLOP = 5.3 us at MFMA peak"},
             }
-            if world == 1 and not args.no_aux:
+            if dev_ms is not None:
+                result["step"].update({
+                    "device_ms_per_step": round(dev_ms / args.steps, 5),
+                    "tflops": round(STEP_FLOPS * args.batch / 1024 / (dev_ms / args.steps) / 1e9, 3),
+                    "frac_mfma": round(STEP_FLOPS * args.batch / 1024 / (dev_ms / args.steps) / 1e9 / PEAK_MFMA_F32_TF, 4)})
+            if world == 1 and aux:
                 result.update(aux_benchmarks(T))
                 result["cpu_baseline"] = cpu_baseline(ws, X, Y, args.cpu_seconds)
                 cb = result["cpu_baseline"]
@@ -1007,6 +1030,9 @@ def main():
                     same["f32"] = {"gpu_steps_per_s": result["value"], "cpu_steps_per_s": cb["f32_build"]["value"],
                                    "ratio": round(result["value"] / max(cb["f32_build"]["value"], 1e-12), 1)}
                 result["gpu_over_cpu_same_precision"] = same
+            elif world == 1 and dist is None:   # a plain one-GPU line: the headline only
+                result["cpu_baseline"] = None
+                result["roofline"] = None
             else:
                 result["cpu_baseline"] = None
                 result["roofline"] = exchange_roofline(world, nflat * 4, args.collective, collective_us)
@@ -1021,6 +1047,10 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+    if outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for (layer, kind), a in zip([(1, "weights"), (1, "bias"), (2, "weights"), (2, "bias")], outputs):
+            np.save(os.path.join(args.dump_outputs, "layer%d_%s.npy" % (layer, kind)), a.astype(np.float32))
     if result is not None:
         os.write(real_stdout, (json.dumps(result) + "\n").encode())
 

@@ -107,7 +107,7 @@ def test_bench_line_from_two_ranks_sharing_the_gpu(repo_root):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(repo_root, "bench.py"),
-                        "--gpus", "2", "--same-gpu", "--steps", "5", "--warmup", "2", "--regions", "3"],
+                        "--gpus", "2", "--same-gpu", "--full", "--steps", "5", "--warmup", "2", "--regions", "3"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=repo_root)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -496,12 +496,11 @@ def test_calls_from_many_threads_are_serialised_correctly(T, O):
     assert T.stats()["live_handles"] == before
 
 
-def test_c_abi_collective_world_of_one(T):
-    """to_comm_* (the exchange step of SURVEY.md 8(e) on the C ABI): unique id -> communicator -> in-place
-    all-reduce(sum) on the library stream.  A world of one rank is what a 1-GPU box can exercise: the sum is
-    the identity, for both element types, and the error paths are loud."""
+def _collective_world_of_one():
+    """the body of test_c_abi_collective_world_of_one, run in an interpreter of its own"""
     from tensor_ops_amd import capi
     from tensor_ops_amd.hipt import HipT
+    T = HipT(0)
     L = capi.lib()
     w = C.c_int(-1)
     capi.check(L.to_comm_world(C.byref(w)))
@@ -525,6 +524,21 @@ def test_c_abi_collective_world_of_one(T):
     capi.check(L.to_comm_shutdown())
     capi.check(L.to_comm_world(C.byref(w)))
     assert w.value == 0
+
+
+def test_c_abi_collective_world_of_one(repo_root):
+    """to_comm_* (the exchange step of SURVEY.md 8(e) on the C ABI): unique id -> communicator -> in-place
+    all-reduce(sum) on the library stream.  A world of one rank is what a 1-GPU box can exercise: the sum is
+    the identity, for both element types, and the error paths are loud.
+    The body runs in a fresh interpreter: the HIP runtime and the RCCL the library binds to are whichever copies the
+    process loaded first, and an earlier test of the suite that imports torch brings torch's own."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = "import sys; sys.path[:0] = [%r, %r]; import test_gpu_tensor_class as t; t._collective_world_of_one()" % (repo_root, here)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=repo_root)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
 
 
 def test_argMin(T, O):

@@ -22,8 +22,8 @@ pmc() {  # name, counters, command...
   timeout 600 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d /tmp/rp_$name -o $name -- "$@" > $OUT/${name}.log 2>&1
   find /tmp/rp_$name -name "*counter_collection.csv" -exec cp {} $OUT/${TAG}_${name}_counter_collection.csv \;
 }
-python $REPO/bench.py --steps 500 --warmup 50 > $OUT/${TAG}_bench_unprofiled.json 2> $OUT/bench_unprofiled.err
-stats bench python $REPO/bench.py --steps 500 --warmup 50
+python $REPO/bench.py --full --steps 500 --warmup 50 > $OUT/${TAG}_bench_unprofiled.json 2> $OUT/bench_unprofiled.err
+stats bench python $REPO/bench.py --full --steps 500 --warmup 50
 grep '^{' $OUT/bench.log > $OUT/${TAG}_bench_under_rocprof.json
 WARM=30 stats gemm4096 python $REPO/tools/gemm_bench.py 4096 4096 4096 50
 WARM=50 stats gemm1024 python $REPO/tools/gemm_bench.py 1024 1024 1024 300   # the wave-split kernel (gemm_kwave.hip)

@@ -359,6 +359,24 @@ to_status to_graph_online_sgd(to_graph g, to_tensor x_buf, to_tensor y_buf, to_t
 /* how often to_graph_online_sgd recognised a captured step and ran the persistent kernel, and over how many samples */
 to_status to_online_sgd_stats(int64_t* runs, int64_t* samples);
 
+/* `runNetwork` (FeedForward.hs:123-129, 216-235) of the same stacks over the hidden batch of x -- a_l = act_l (W_l a_{l-1}
+ * + b_l), hidden_act TO_ACT_LOGISTIC, out_act TO_ACT_SOFTMAX or TO_ACT_LOGISTIC -- with the validation folds of
+ * app/MNIST.hs:366-389 in the same call.  fp32 or fp64, any batch (an unbatched x is one row), any layer widths: never
+ * TO_ERR_UNSUPPORTED for a valid stack.  What it writes, each optional, at least one asked for (else TO_ERR_ARG):
+ *   out_or_null        caller-allocated [B; n_L] of x's dtype (contiguous): the network's output rows;
+ *   classes_or_null    host int64[B]: `TT.argMax` of every row of out as stored -- bit for bit what to_arg_max returns for
+ *                      it, ties (earliest index) and NaN included;
+ *   confusion_or_null  host int64[n_L * n_L], [predicted * n_L + actual], actual = argMax of the target row of
+ *                      y_or_null ([B; n_L], x's dtype; required for it, TO_ERR_ARG otherwise): `confusion`'s map, its
+ *                      trace `validate`'s count of correct rows.
+ * Parameters, x and y are only read; pending operands are produced first.  The last layer and everything after it is ONE
+ * launch for n_L <= 32 at any fan-in (csrc/infer_head.hip: the activations stream from HBM once, W_L in LDS); wider heads
+ * are the last GEMM plus one row launch.  A row's values do not depend on the batch or the row's place in it.  Refused
+ * during graph capture (TO_ERR_STATE); blocks when it returns host data; keeps no handle. */
+to_status to_fflayer_stack_infer(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                 to_tensor x, to_tensor y_or_null, to_tensor out_or_null,
+                                 int64_t* classes_or_null, int64_t* confusion_or_null);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 /* Average duration (ms) of kernels enqueued between the two calls, measured with
  * HIP events on the library's stream. */

@@ -2215,6 +2215,32 @@ static bool fused_gemm(int dtype, const void* A, int64_t a_sm, int64_t a_sk, con
   return false;
 }
 
+// The checks the ffLayer stack entry points share.  Hidden layers: logistic only.
+static void stack_hidden_act_check(int hidden_act) {
+  TO_CHECK(hidden_act == TO_ACT_LOGISTIC, TO_ERR_UNSUPPORTED, "fused path: hidden activation must be logistic");
+}
+
+// Every layer's W [n_l, n_{l-1}] and b [n_l]: unbatched, contiguous, of the data's dtype, chained from `fan_in`; gradient
+// destinations (gw / gb null: none) of the parameters' shapes.  Returns n_L.
+static int64_t stack_params_check(int n_layers, const to_tensor* w, const to_tensor* b, const to_tensor* gw,
+                                  const to_tensor* gb, int dt, int64_t fan_in) {
+  for (int l = 0; l < n_layers; ++l) {
+    NONNULL(w[l]); NONNULL(b[l]);
+    if (gw) { NONNULL(gw[l]); NONNULL(gb[l]); }
+    TO_CHECK(w[l]->dtype == dt && b[l]->dtype == dt && (!gw || (gw[l]->dtype == dt && gb[l]->dtype == dt)), TO_ERR_ARG,
+             gw ? "parameters, gradients and data must share one dtype" : "parameters and data must share one dtype");
+    TO_CHECK(w[l]->rank == 2 && w[l]->batch == 0 && w[l]->dims[1] == fan_in && w[l]->contiguous(),
+             TO_ERR_SHAPE, "layer " + std::to_string(l) + ": W has shape " + shape_str(w[l]));
+    TO_CHECK(b[l]->rank == 1 && b[l]->batch == 0 && b[l]->dims[0] == w[l]->dims[0] && b[l]->contiguous(),
+             TO_ERR_SHAPE, "layer " + std::to_string(l) + ": b has shape " + shape_str(b[l]));
+    if (gw)
+      TO_CHECK(same_shape(gw[l], w[l]) && gw[l]->contiguous() && same_shape(gb[l], b[l]) && gb[l]->contiguous(),
+               TO_ERR_SHAPE, "gradient destinations must match the parameters");
+    fan_in = w[l]->dims[0];
+  }
+  return fan_in;
+}
+
 // sgd: gw/gb are the parameters themselves and the weight-gradient launches apply
 // P <- P - rate * gradient in their epilogue (alpha = -rate, beta = 1, Cin = C = W; the bias through the
 // accumulating row sum): the step loses its separate update launch.
@@ -2234,7 +2260,7 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
     before_write(gb[l]);
     if (sgd) { w[l]->id = fresh_id(); b[l]->id = fresh_id(); }
   }
-  TO_CHECK(hidden_act == TO_ACT_LOGISTIC, TO_ERR_UNSUPPORTED, "fused path: hidden activation must be logistic");
+  stack_hidden_act_check(hidden_act);
   const bool sm_ce = out_act == TO_ACT_SOFTMAX && loss == TO_LOSS_CROSS_ENTROPY;
   const bool lg_se = out_act == TO_ACT_LOGISTIC && loss == TO_LOSS_SQUARED_ERROR;
   TO_CHECK(sm_ce || lg_se, TO_ERR_UNSUPPORTED,
@@ -2245,19 +2271,7 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
   const int dt = x->dtype;
   TO_CHECK(y->dtype == dt, TO_ERR_ARG, "x and y have different dtypes");
   const int64_t B = x->batch;
-  int64_t fan_in = x->dims[0];
-  for (int l = 0; l < n_layers; ++l) {
-    NONNULL(w[l]); NONNULL(b[l]); NONNULL(gw[l]); NONNULL(gb[l]);
-    TO_CHECK(w[l]->dtype == dt && b[l]->dtype == dt && gw[l]->dtype == dt && gb[l]->dtype == dt, TO_ERR_ARG,
-             "parameters, gradients and data must share one dtype");
-    TO_CHECK(w[l]->rank == 2 && w[l]->batch == 0 && w[l]->dims[1] == fan_in && w[l]->contiguous(),
-             TO_ERR_SHAPE, "layer " + std::to_string(l) + ": W has shape " + shape_str(w[l]));
-    TO_CHECK(b[l]->rank == 1 && b[l]->batch == 0 && b[l]->dims[0] == w[l]->dims[0] && b[l]->contiguous(),
-             TO_ERR_SHAPE, "layer " + std::to_string(l) + ": b has shape " + shape_str(b[l]));
-    TO_CHECK(same_shape(gw[l], w[l]) && gw[l]->contiguous() && same_shape(gb[l], b[l]) && gb[l]->contiguous(),
-             TO_ERR_SHAPE, "gradient destinations must match the parameters");
-    fan_in = w[l]->dims[0];
-  }
+  const int64_t fan_in = stack_params_check(n_layers, w, b, gw, gb, dt, x->dims[0]);
   TO_CHECK(y->dims[0] == fan_in, TO_ERR_SHAPE, "y does not match the output layer");
   if (losses) TO_CHECK(losses->rank == 0 && losses->batch == B && losses->contiguous(), TO_ERR_SHAPE,
                        "losses must be a batched scalar");
@@ -2474,6 +2488,126 @@ to_status to_fflayer_stack_online_sgd(int n_layers, const to_tensor* w, const to
                                       double rate) {
   API_BEGIN
   online_sgd_impl(n_layers, w, b, hidden_act, out_act, loss, X, Y, n_idx, idx_or_null, rate);
+  API_END
+}
+
+// `runNetwork` (FeedForward.hs:123-129) of an ffLayer stack over a batch and the folds of `validate` / `confusion`
+// (app/MNIST.hs:366-389).  Hidden layers: one GEMM each, bias + logistic in its epilogue where the kernel carries one,
+// else a plain GEMM and one elementwise launch.  The head (infer_head.hip): n_L <= 32 the last layer's contraction and
+// everything after it in one launch; wider, the last GEMM into scratch (or `out` itself) and one row launch.
+static void fflayer_stack_infer_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                     to_tensor x, to_tensor y, to_tensor out, int64_t* classes, int64_t* confusion) {
+  require_init();
+  no_capture("to_fflayer_stack_infer");
+  NONNULL(w); NONNULL(b); NONNULL(x);
+  TO_CHECK(n_layers >= 1, TO_ERR_ARG, "need at least one layer");
+  TO_CHECK(out || classes || confusion, TO_ERR_ARG, "infer: no output asked for (out, classes or confusion)");
+  TO_CHECK(!confusion || y, TO_ERR_ARG, "infer: the confusion matrix needs the targets y");
+  stack_hidden_act_check(hidden_act);
+  TO_CHECK(out_act == TO_ACT_SOFTMAX || out_act == TO_ACT_LOGISTIC, TO_ERR_UNSUPPORTED,
+           "infer: the output activation must be softmax or logistic");
+  TO_CHECK(x->rank == 1 && x->dims[0] >= 1, TO_ERR_SHAPE, "infer: x must be a (batched) vector, got " + shape_str(x));
+  const int dt = x->dtype;
+  const int64_t nL = stack_params_check(n_layers, w, b, nullptr, nullptr, dt, x->dims[0]);
+  const int64_t B = x->batch > 0 ? x->batch : 1;
+  if (y) {
+    TO_CHECK(y->dtype == dt, TO_ERR_ARG, "infer: x and y have different dtypes");
+    TO_CHECK(y->rank == 1 && y->dims[0] == nL && y->batch == x->batch, TO_ERR_SHAPE,
+             "infer: y must be " + std::to_string(nL) + "-vectors of x's batch, got " + shape_str(y));
+  }
+  if (out) {
+    TO_CHECK(out->dtype == dt, TO_ERR_ARG, "infer: x and out have different dtypes");
+    TO_CHECK(out->rank == 1 && out->dims[0] == nL && out->batch == x->batch, TO_ERR_SHAPE,
+             "infer: out must be " + std::to_string(nL) + "-vectors of x's batch, got " + shape_str(out));
+    TO_CHECK(out->contiguous(), TO_ERR_ARG, "infer: out must be contiguous");
+  }
+  ensure(x);
+  if (y) ensure(y);
+  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); }
+  if (out) {
+    ensure(out);
+    before_write(out);
+    out->id = fresh_id();
+  }
+  // rows with unit element stride (a strided vector view is packed first); the rows themselves may lie anywhere
+  Holder xc(x->dims[0] > 1 && x->strides[0] != 1 ? contiguous(x) : nullptr), yc;
+  const to_tensor xr = xc.t ? xc.t : x;
+  const int64_t x_sm = x->batch > 0 ? xr->bstride : 0;
+  if (y && y->dims[0] > 1 && y->strides[0] != 1) yc.t = contiguous(y);
+  const to_tensor yr = yc.t ? yc.t : y;
+  const int64_t y_sm = y && y->batch > 0 ? yr->bstride : 0;
+  // C[B, n] = A[B, K] . W^T : B operand element (k, j) = W[j*K + k]
+  auto layer = [&](const void* A, int64_t a_sm, to_tensor W, void* C) {
+    GemmProblem p{};
+    p.dtype = dt;
+    p.A = A; p.B = W->ptr; p.C = C;
+    p.M = B; p.N = W->dims[0]; p.K = W->dims[1];
+    p.a_sm = a_sm; p.a_sk = 1; p.b_sk = 1; p.b_sn = p.K; p.c_sm = p.N;
+    p.batch = 1;
+    p.alpha = 1.0; p.beta = 0.0;
+    return p;
+  };
+  std::vector<Holder> act(n_layers);
+  const void* prev = xr->ptr;
+  int64_t prev_sm = x_sm;
+  for (int l = 0; l + 1 < n_layers; ++l) {
+    const int64_t n = w[l]->dims[0];
+    act[l].t = new_tensor(1, &n, B, dt);
+    GemmProblem p = layer(prev, prev_sm, w[l], act[l].t->ptr);
+    p.bias = b[l]->ptr;
+    p.act = 1;
+    if (gemm_epilogue_ok(p)) {
+      if (gemm_small_route(p)) launch_gemm_small(p, S());
+      else run_gemm(p);
+    } else {  // (the tiled fp64 kernel: alpha / beta only)
+      p.bias = nullptr;
+      p.act = 0;
+      run_gemm(p);
+      launch_bias_logistic_rows(dt, act[l].t->ptr, b[l]->ptr, B, n, S());
+    }
+    prev = act[l].t->ptr;
+    prev_sm = n;
+  }
+  const to_tensor WL = w[n_layers - 1], bL = b[n_layers - 1];
+  Holder cls, conf, z;
+  if (classes) cls.t = new_tensor(1, &B, 0);  // B int32 in a float-typed pool buffer
+  if (confusion) {
+    const int64_t nl = nL * nL * 2;              // n_L^2 uint64
+    conf.t = new_tensor(1, &nl, 0);
+    TO_HIP(hipMemsetAsync(conf.t->ptr, 0, (size_t)(nL * nL) * 8, S()));
+  }
+  int* cls_p = cls.t ? static_cast<int*>(cls.t->ptr) : nullptr;
+  auto* conf_p = conf.t ? static_cast<unsigned long long*>(conf.t->ptr) : nullptr;
+  void* out_p = out ? out->ptr : nullptr;
+  const void* y_p = y ? yr->ptr : nullptr;
+  const bool softmax = out_act == TO_ACT_SOFTMAX;
+  if (nL <= INFER_NARROW_MAX) {
+    launch_infer_narrow(dt, prev, prev_sm, B, WL->dims[1], WL->ptr, bL->ptr, (int)nL, softmax, out_p, y_p, y_sm, cls_p,
+                        conf_p, S());
+  } else {
+    void* zp = out_p;  // the row launch reads each element of z before it writes the same element of out
+    if (!zp) {
+      z.t = new_tensor(1, &nL, B, dt);
+      zp = z.t->ptr;
+    }
+    run_gemm(layer(prev, prev_sm, WL, zp));
+    TO_CHECK(nL <= 2147483647LL, TO_ERR_SHAPE, "infer: output layer too wide");
+    launch_infer_rows(dt, zp, B, bL->ptr, (int)nL, softmax, out_p, y_p, y_sm, cls_p, conf_p, S());
+  }
+  if (classes) {
+    std::vector<int32_t> ids((size_t)B);
+    device_to_host(ids.data(), cls_p, (size_t)B * sizeof(int32_t), S());
+    for (int64_t r = 0; r < B; ++r) classes[r] = ids[(size_t)r];
+  }
+  if (confusion) device_to_host(confusion, conf_p, (size_t)(nL * nL) * sizeof(int64_t), S());
+}
+
+to_status to_fflayer_stack_infer(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                 to_tensor x, to_tensor y_or_null, to_tensor out_or_null, int64_t* classes_or_null,
+                                 int64_t* confusion_or_null) {
+  API_BEGIN
+  fflayer_stack_infer_impl(n_layers, w, b, hidden_act, out_act, x, y_or_null, out_or_null, classes_or_null,
+                           confusion_or_null);
   API_END
 }
 

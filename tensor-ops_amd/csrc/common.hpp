@@ -419,6 +419,18 @@ int online_sgd_status();
 void online_sgd_reset_status();
 void launch_loss_grad_rows(int dtype, const void* z, const void* y, void* dz, void* loss, int64_t B, int64_t n,
                            int kind, hipStream_t s);
+// infer_head.hip: the output head of to_fflayer_stack_infer.  out (optional) = act(A W^T + b) with act softmax or logistic,
+// classes[r] (optional, int32) = argMax of out's row r, conf[pred * n + actual] += 1 per row (optional; actual = argMax of
+// y's row, y row stride y_sm).  narrow: the last layer's contraction too, n <= INFER_NARROW_MAX, A rows a_sm apart;
+// rows: z = A W^T already computed (contiguous [B, n], no bias), any n, z may be out itself.
+constexpr int INFER_NARROW_MAX = 32;
+void launch_infer_narrow(int dtype, const void* A, int64_t a_sm, int64_t B, int64_t K, const void* W, const void* bias,
+                         int n, bool softmax, void* out, const void* y, int64_t y_sm, int* classes,
+                         unsigned long long* conf, hipStream_t s);
+void launch_infer_rows(int dtype, const void* z, int64_t B, const void* bias, int n, bool softmax, void* out,
+                       const void* y, int64_t y_sm, int* classes, unsigned long long* conf, hipStream_t s);
+// x[r][j] = logistic(x[r][j] + bias[j]) in place (a hidden layer whose GEMM carried no epilogue)
+void launch_bias_logistic_rows(int dtype, void* x, const void* bias, int64_t B, int64_t n, hipStream_t s);
 
 }  // namespace to
 

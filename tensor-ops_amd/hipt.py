@@ -422,6 +422,29 @@ class HipT:
                                idx.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(h)))
         return DT(h)
 
+    def infer_stack(self, ws, bs, x, out_act="softmax", y=None, want_out=False, want_classes=True):
+        """`runNetwork` of a genNet stack (logistic hidden layers) over the batch of x, with `validate` / `confusion`'s
+        folds (to_fflayer_stack_infer): (out DT or None, classes int64[B] or None, confusion [n_L, n_L] indexed
+        [predicted, actual] or None -- given y only)."""
+        act = {"softmax": 2, "logistic": 0}[out_act]
+        shape, batch = x._shape()
+        rows = max(batch, 1)
+        nL = ws[-1].shape[0]
+        out = None
+        if want_out:
+            d, r = dims_arr((nL,))
+            h = _out()
+            check(lib().to_alloc(self.to_dtype, r, d, batch, C.byref(h)))
+            out = DT(h)
+        classes = np.empty(rows, dtype=np.int64) if want_classes else None
+        conf = np.zeros((nL, nL), dtype=np.int64) if y is not None else None
+        i64 = C.POINTER(C.c_int64)
+        check(lib().to_fflayer_stack_infer(len(ws), _arr(ws), _arr(bs), 0, act, x.h, y.h if y is not None else None,
+                                           out.h if out is not None else None,
+                                           classes.ctypes.data_as(i64) if classes is not None else None,
+                                           conf.ctypes.data_as(i64) if conf is not None else None))
+        return out, classes, conf
+
     # -- batching -------------------------------------------------------------------------
     def batch_sum(self, x):
         h = _out()

@@ -377,6 +377,51 @@ to_status to_fflayer_stack_infer(int n_layers, const to_tensor* w, const to_tens
                                  to_tensor x, to_tensor y_or_null, to_tensor out_or_null,
                                  int64_t* classes_or_null, int64_t* confusion_or_null);
 
+/* Recurrent stacks (Recurrent.hs): `runNetwork` threaded over T steps, `netGrad` (BPTT, `unroll` >>> `rollup`) summed over
+ * the sequences of a hidden batch, and `trainNetwork'`, each ONE call.  Per-layer arrays in input-to-output order, like the
+ * ffLayer entries.  Layer l is
+ *   state_act[l] == TO_ACT_LOGISTIC   `fullyConnected` (Recurrent.hs:91-119): z = W x + W' s + b, new state logistic(z),
+ *                                     output z through the layer's `*~ act`; s[l] [n_l], ws[l] = W' [n_l, n_l];
+ *   state_act[l] == TO_RNN_STATELESS  an ffLayer (Recurrent.hs:126-138); s[l] and ws[l] (and gs[l], gws[l]) null;
+ * w[l] = W [n_l, n_{l-1}], b[l] [n_l].  hidden_act TO_ACT_LOGISTIC; run: out_act TO_ACT_SOFTMAX or TO_ACT_LOGISTIC; grad /
+ * sgd: (out_act, loss) (TO_ACT_SOFTMAX, TO_LOSS_CROSS_ENTROPY) or (TO_ACT_LOGISTIC, TO_LOSS_SQUARED_ERROR); anything else
+ * is TO_ERR_UNSUPPORTED, nothing written.  The reference's order: `Prod t ss` lists later layers' states first (`~*~`:
+ * ss2 ++ ss1) and each fullyConnected carries its parameters as (W', W, b); here layer l's state is s[l] and its parameters
+ * ws[l], w[l], b[l] whatever the position.
+ * X [B; T, i] (or [T, i]: one sequence): B independent sequences, step 0 consumed first -- plain time order; the
+ * reference's reversed order (Recurrent.hs:289-293) is a detail of its netGrad and does not appear here.  Y and out
+ * [B; T, n_L] of X's batch.
+ *   run   every step's output row into out (contiguous); s_out_or_null[l] (optional per stateful layer, contiguous
+ *         [B; n_l] of X's batch) the final state.  s[l] unbatched (every sequence starts from it) or [B; n_l]: the s_out
+ *         of one call is the s of the next, a long sequence fed in chunks.
+ *   grad  objective sum_b sum_t loss(out_{b,t}, Y_{b,t}); gs / gws / gw / gb get the cotangents of the (unbatched)
+ *         initial states and of the parameters; gx_or_null [B; T, i] the per-sequence, per-step input cotangents;
+ *         losses_or_null [B; T] the per-(sequence, step) losses.
+ *   sgd   `trainNetwork'` in place: s -= rate_state gs, every parameter -= rate_params g.  A refused call updates nothing.
+ * Initial states of grad / sgd must be unbatched (TO_ERR_SHAPE).  fp32 or fp64, any B, T >= 1 and widths: never
+ * TO_ERR_UNSUPPORTED for a valid stack.  Pending operands are produced first; refused during graph capture (TO_ERR_STATE);
+ * blocks before returning; keeps no handle.
+ * Routes.  Time-independent work -- input projections, heads, weight gradients, input cotangents -- is one contraction over
+ * all B*T rows.  A stateful layer's recurrence is either ONE persistent launch per direction for all T steps
+ * (csrc/rnn_seq.hip; its range: n_l <= 1024, fp32 and fp64, any B and T -- the launch count of a call does not depend on T
+ * there) or per step (one GEMM with the addend + one elementwise launch per step and direction).  to_set_rnn_persistent:
+ * 0 per step; 1 automatic (default): persistent where the kernel holds W' in LDS (fp32 n_l <= 201, fp64 n_l <= 142), the
+ * threshold measured in DESIGN.md section 3.3, per step otherwise; 2 persistent wherever in range.  Process-wide.
+ * to_rnn_stats counts the calls with a stateful layer: all of its recurrences persistent, or at least one per step. */
+enum { TO_RNN_STATELESS = -1 };
+to_status to_rnn_stack_run(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
+                           const to_tensor* b, int hidden_act, int out_act, to_tensor X, to_tensor out,
+                           const to_tensor* s_out_or_null);
+to_status to_rnn_stack_grad(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
+                            const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
+                            const to_tensor* gs, const to_tensor* gws, const to_tensor* gw, const to_tensor* gb,
+                            to_tensor gx_or_null, to_tensor losses_or_null);
+to_status to_rnn_stack_sgd(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
+                           const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
+                           double rate_state, double rate_params, to_tensor losses_or_null);
+to_status to_set_rnn_persistent(int on, int* previous_or_null);
+to_status to_rnn_stats(int64_t* persistent_runs, int64_t* stepwise_runs);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 /* Average duration (ms) of kernels enqueued between the two calls, measured with
  * HIP events on the library's stream. */

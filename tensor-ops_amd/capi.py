@@ -118,6 +118,16 @@ SIGNATURES = {
                                     c_tensor, c_tensor, C.c_int64, i64p, C.c_double],
     "to_fflayer_stack_infer": [C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, c_tensor, c_tensor,
                                c_tensor, i64p, i64p],
+    "to_rnn_stack_run": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor),
+                         C.POINTER(c_tensor), C.c_int, C.c_int, c_tensor, c_tensor, C.POINTER(c_tensor)],
+    "to_rnn_stack_grad": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor),
+                          C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int, c_tensor, c_tensor, C.POINTER(c_tensor),
+                          C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor), c_tensor, c_tensor],
+    "to_rnn_stack_sgd": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor),
+                         C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int, c_tensor, c_tensor, C.c_double, C.c_double,
+                         c_tensor],
+    "to_set_rnn_persistent": [C.c_int, C.POINTER(C.c_int)],
+    "to_rnn_stats": [i64p, i64p],
     "to_graph_online_sgd": [c_graph, c_tensor, c_tensor, c_tensor, c_tensor, C.c_int64, i64p, C.POINTER(C.c_int)],
     "to_online_sgd_stats": [i64p, i64p],
     "to_timer_start": [],

@@ -431,6 +431,19 @@ void launch_infer_rows(int dtype, const void* z, int64_t B, const void* bias, in
                        const void* y, int64_t y_sm, int* classes, unsigned long long* conf, hipStream_t s);
 // x[r][j] = logistic(x[r][j] + bias[j]) in place (a hidden layer whose GEMM carried no epilogue)
 void launch_bias_logistic_rows(int dtype, void* x, const void* bias, int64_t B, int64_t n, hipStream_t s);
+// rnn_seq.hip: the recurrence of a stateful layer over all T steps in one launch (to_rnn_stack_*).  M [H][H]: W'^T
+// (forward: Z = P -> z in place, St blocks 1..T = logistic(z)) or W' (reverse: Z = G -> dz in place, reading St blocks
+// 1..T).  Z [T][B][H], St [T+1][B][H] (block 0: the initial states).  H <= RNN_SEQ_MAX_H, any B and T.
+constexpr int64_t RNN_SEQ_MAX_H = 1024;
+struct RnnSeqPlan {
+  int R = 1;          // sequences per workgroup
+  int64_t grid = 0;   // workgroups
+  bool m_lds = false; // M held in LDS
+  size_t lds = 0;     // dynamic LDS bytes
+};
+bool rnn_seq_plan(int dtype, int64_t H, int64_t B, RnnSeqPlan* p);
+void launch_rnn_seq(int dtype, bool reverse, const RnnSeqPlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T,
+                    int64_t H, hipStream_t s);
 
 }  // namespace to
 

@@ -445,6 +445,75 @@ class HipT:
                                            conf.ctypes.data_as(i64) if conf is not None else None))
         return out, classes, conf
 
+    # -- recurrent stacks (to_rnn_stack_*) ----------------------------------------------------
+    _RNN_OUT = {"softmax": 2, "logistic": 0}
+    _RNN_LOSS = {"crossEntropy": 1, "squaredError": 0}
+
+    def _alloc(self, shape, batch):
+        d, r = dims_arr(tuple(shape))
+        h = _out()
+        check(lib().to_alloc(self.to_dtype, r, d, batch, C.byref(h)))
+        return DT(h)
+
+    @staticmethod
+    def _rnn_arrays(layers):
+        """layers: [(s, W', W, b)] in input-to-output order; s = W' = None for a stateless ffLayer"""
+        n = len(layers)
+        sact = (C.c_int * n)(*[0 if s is not None else -1 for s, _, _, _ in layers])
+        col = [(capi.c_tensor * n)(*[(t.h if t is not None else None) for t in ts]) for ts in zip(*layers)]
+        return n, sact, col
+
+    def rnn_stack_run(self, layers, X, out_act="softmax", want_states=False):
+        """`runNetwork` threaded over the T steps of X [B; T, i] (to_rnn_stack_run): (out [B; T, n_L], final states --
+        one per layer, None for a stateless one -- or None)"""
+        n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
+        T, _ = X.shape
+        batch = X.batch
+        out = self._alloc((T, layers[-1][2].shape[0]), batch)
+        finals = [self._alloc((lay[2].shape[0],), batch) if (want_states and lay[0] is not None) else None for lay in layers]
+        s_out = (capi.c_tensor * n)(*[(f.h if f is not None else None) for f in finals]) if want_states else None
+        check(lib().to_rnn_stack_run(n, sact, s, ws, w, b, 0, self._RNN_OUT[out_act], X.h, out.h, s_out))
+        return out, (finals if want_states else None)
+
+    def rnn_stack_grad(self, layers, X, Y, out_act="softmax", loss="crossEntropy", want_gx=False, want_losses=False):
+        """BPTT of the stack summed over the sequences of X (to_rnn_stack_grad): (gs, gws, gw, gb -- lists per layer, None
+        for a stateless layer's state entries --, gx [B; T, i] or None, losses [B; T] or None)"""
+        n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
+        gS = [self._alloc(lay[0].shape, 0) if lay[0] is not None else None for lay in layers]
+        gWS = [self._alloc(lay[1].shape, 0) if lay[1] is not None else None for lay in layers]
+        gW = [self._alloc(lay[2].shape, 0) for lay in layers]
+        gB = [self._alloc(lay[3].shape, 0) for lay in layers]
+        T, i = X.shape
+        gx = self._alloc((T, i), X.batch) if want_gx else None
+        losses = self._alloc((T,), X.batch) if want_losses else None
+        arr = lambda ts: (capi.c_tensor * n)(*[(t.h if t is not None else None) for t in ts])  # noqa: E731
+        check(lib().to_rnn_stack_grad(n, sact, s, ws, w, b, 0, self._RNN_OUT[out_act], self._RNN_LOSS[loss], X.h, Y.h,
+                                      arr(gS), arr(gWS), arr(gW), arr(gB), gx.h if gx is not None else None,
+                                      losses.h if losses is not None else None))
+        return gS, gWS, gW, gB, gx, losses
+
+    def rnn_stack_sgd(self, layers, X, Y, rate_state, rate_params, out_act="softmax", loss="crossEntropy",
+                      want_losses=False):
+        """`trainNetwork'` in place (to_rnn_stack_sgd); the per-(sequence, step) losses if asked for"""
+        n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
+        losses = self._alloc((X.shape[0],), X.batch) if want_losses else None
+        check(lib().to_rnn_stack_sgd(n, sact, s, ws, w, b, 0, self._RNN_OUT[out_act], self._RNN_LOSS[loss], X.h, Y.h,
+                                     float(rate_state), float(rate_params), losses.h if losses is not None else None))
+        return losses
+
+    @staticmethod
+    def rnn_persistent(on):
+        """to_set_rnn_persistent: 0 per step, 1 automatic, 2 wherever in range; returns the previous setting"""
+        prev = C.c_int()
+        check(lib().to_set_rnn_persistent(int(on), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
+    def rnn_stats():
+        p, q = C.c_int64(), C.c_int64()
+        check(lib().to_rnn_stats(C.byref(p), C.byref(q)))
+        return p.value, q.value
+
     # -- batching -------------------------------------------------------------------------
     def batch_sum(self, x):
         h = _out()

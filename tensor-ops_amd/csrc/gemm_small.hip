@@ -11,6 +11,8 @@
 // Serves the batched ffLayer step (config 3): X.W1^T, dZ^T.X, H.W2^T, dZ2^T.H, dZ2.W2.
 #include "common.hpp"
 
+#include <type_traits>
+
 namespace to {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -102,7 +104,17 @@ __device__ __forceinline__ double max_s(double a, double b) { return fmax(a, b);
 // and they share one dynamic allocation: their static arrays together would not fit)
 // tid: the thread's index within the NW waves that run this body (threadIdx.x, unless a larger workgroup runs several
 // bodies side by side: the seam kernel's two 8-wave head tiles inside a 16-wave workgroup)
-template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0, bool EXT = false>   // ONESHOT: 0, or the chunks one batch holds
+// PARTS (one-shot bodies only): who orders the batch's loads against its MFMAs.
+//   0: the compiler (what every instance but the weight-gradient pair's 32x32 body runs).  Left alone, its scheduler
+//      does NOT keep the one-shot: it issues 16 of the 64 loads of that body, then drips the rest between the MFMAs, and
+//      from the 14th MFMA on each MFMA waits for a load issued a few instructions earlier (tools/asm_schedule.py).
+//   P >= 1: this file.  The slice goes out in P parts of ONESHOT / P chunks; part p + 1 is issued before the MFMAs of
+//      part p and scheduling barriers pin that order, so the waits the compiler puts in front of part p's MFMAs leave
+//      exactly the younger parts in flight.  P = 1 is the true one-shot.  The stamp points sit on the same barriers: a
+//      development build (SM_STAMP) generates the same load / MFMA order as the product (tests/test_step_schedule.py).
+// STAG: the four waves of a SIMD (w, w + 4, w + 8, w + 12) issue their loads at falling priority, so the CU's one
+//      vector-memory path completes whole waves in turn instead of a sixteenth of everybody's.
+template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0, bool EXT = false, int PARTS = 0, bool STAG = false>   // ONESHOT: 0, or the chunks one batch holds
 __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const int bid, const long bz, S* ext_lds = nullptr,
                                                 const int tid_in = -1) {
   constexpr int ES = (int)sizeof(S);
@@ -216,6 +228,48 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
         asum += a[c][j];
       }
   };
+  // the staged one-shot (PARTS >= 1): the same loads and the same MFMAs, in the same order per accumulator, as
+  // load_stage + mma_stage -- chunk by chunk, j by j -- so the results are bit-identical whatever PARTS is
+  constexpr int CP = PARTS ? ST / PARTS : ST;   // chunks a part
+  static_assert(PARTS == 0 || (ONESHOT && ST % PARTS == 0), "PARTS divides the one-shot batch");
+  auto load_part = [&](auto part, int k0) {
+    constexpr int p = decltype(part)::value;
+#pragma unroll
+    for (int c = p * CP; c < (p + 1) * CP; ++c) {
+      const int kb = k0 + CK * c + 4 * half;
+      if (AMODE == 0 && g.a_vec) {
+        ld4(ra, mv & (kb < kend), a_base + kb * ES, a0[c]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a0[c][j] = ld1(ra, sel(mv & (kb + j < kend), a_base + (kb + j) * a_sk4));
+      }
+      if (BMODE == 1 && g.b_vec) {
+        ld4(rb, nv & (kb < kend), b_base + kb * ES, b0[c]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b0[c][j] = ld1(rb, sel(nv & (kb + j < kend), b_base + (kb + j) * b_sk4));
+      }
+      __builtin_amdgcn_sched_barrier(0);   // chunks leave in the order the MFMAs take them
+    }
+  };
+  auto mma_part = [&](auto part) {
+    constexpr int p = decltype(part)::value;
+#pragma unroll
+    for (int c = p * CP; c < (p + 1) * CP; ++c) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if constexpr (ES == 8) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[c][j], b0[c][j], acc, 0, 0, 0);
+        else if constexpr (TS == 32) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[c][j], b0[c][j], acc, 0, 0, 0);
+        else acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[c][j], b0[c][j], acc, 0, 0, 0);
+      }
+      // the row sums' adds stay BEHIND their chunk's MFMAs: hoisted (the compiler's choice), the add of the part's last
+      // A element sat in front of its third MFMA and made that wait for the whole part
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) asum += a0[c][j];
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
   // row of accumulator register r of this lane's k-group within the 16x16 tile (see the header comment)
   auto row16 = [&](int kg, int r) { return ES == 8 ? kg + 4 * r : 4 * kg + r; };
   // Epilogue operands (Cin, the activation derivative's h, the bias) do not depend on the product: their
@@ -243,12 +297,46 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
   constexpr int SK = CK * ST;
   SM_STAMP(1);   // (set-up done, the epilogue's operands asked for)
   if constexpr (ONESHOT) {
-    if (kbeg < kend) {  // kper <= SK by construction (launch_gemm_small)
-      load_stage(a0, b0, kbeg);
+    if constexpr (PARTS == 0) {
+      if (kbeg < kend) {  // kper <= SK by construction (launch_gemm_small)
+        load_stage(a0, b0, kbeg);
 #ifdef TOPS_AB_KNOBS
-      if (stamp_on) { SM_STAMP(2); __builtin_amdgcn_s_waitcnt(0x0F70); SM_STAMP(3); }   // (the batch issued; all of it landed -- stamped wave only)
+        if (stamp_on) { SM_STAMP(2); __builtin_amdgcn_s_waitcnt(0x0F70); SM_STAMP(3); }   // (the batch issued; all of it landed -- stamped wave only)
 #endif
-      mma_stage(a0, b0);
+        mma_stage(a0, b0);
+      }
+    } else if (kbeg < kend) {
+      if constexpr (STAG) {
+        // (s_setprio takes an immediate and ignores EXEC: a uniform branch per level)
+        const int lvl = __builtin_amdgcn_readfirstlane(wave) >> 2;
+        if (lvl == 0) __builtin_amdgcn_s_setprio(3);
+        else if (lvl == 1) __builtin_amdgcn_s_setprio(2);
+        else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
+      }
+      load_part(std::integral_constant<int, 0>{}, kbeg);
+      auto stage = [&](auto part) {
+        constexpr int p = decltype(part)::value;
+        if constexpr (p + 1 < PARTS) load_part(std::integral_constant<int, p + 1>{}, kbeg);
+        if constexpr (STAG && p == (PARTS >= 2 ? PARTS - 2 : 0)) __builtin_amdgcn_s_setprio(0);   // (the last loads are out)
+        __builtin_amdgcn_sched_barrier(0);
+        // stamps without a wait of their own: 2 = the loads ahead of the first MFMA are issued, 3 = the first part's
+        // MFMAs are issued (so its operands had landed)
+        if constexpr (p == 0) SM_STAMP(2);
+        mma_part(part);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (p == 0) SM_STAMP(3);
+      };
+      stage(std::integral_constant<int, 0>{});
+      if constexpr (PARTS > 1) stage(std::integral_constant<int, 1>{});
+      if constexpr (PARTS > 2) stage(std::integral_constant<int, 2>{});
+      if constexpr (PARTS > 3) stage(std::integral_constant<int, 3>{});
+      if constexpr (PARTS > 4) {
+        stage(std::integral_constant<int, 4>{});
+        stage(std::integral_constant<int, 5>{});
+        stage(std::integral_constant<int, 6>{});
+        stage(std::integral_constant<int, 7>{});
+      }
+      static_assert(PARTS == 1 || PARTS == 2 || PARTS == 4 || PARTS == 8, "one, two, four or eight parts");
     }
   } else {
     S a1[ST][4], b1[ST][4];
@@ -421,12 +509,13 @@ __global__ __launch_bounds__(NW * 64) void gemm_small_kernel(SmallArgsT<S> g) {
 // ~4 us of dispatch and cache maintenance whatever its size, so grouping is worth one such floor.
 // The block is sized for the larger configuration; the surplus waves of the smaller one exit at once
 // (a finished wave no longer counts at s_barrier).
-template <class S, int A1, int B1, int NW1, int TS1, int OS1, int A2, int B2, int NW2, int TS2, int OS2>
+// P1 / STAG1: PARTS / STAG of the first problem's body (the second keeps the compiler's order).
+template <class S, int A1, int B1, int NW1, int TS1, int OS1, int A2, int B2, int NW2, int TS2, int OS2, int P1 = 0, bool STAG1 = false>
 __global__ __launch_bounds__((NW1 > NW2 ? NW1 : NW2) * 64) void gemm_small_pair_kernel(SmallArgsT<S> g1,
                                                                                          SmallArgsT<S> g2, int n1) {
   if ((int)blockIdx.x < n1) {
     if (NW1 < NW2 && (int)(threadIdx.x >> 6) >= NW1) return;
-    gemm_small_body<S, A1, B1, NW1, TS1, OS1>(g1, (int)blockIdx.x, 0);
+    gemm_small_body<S, A1, B1, NW1, TS1, OS1, false, P1, STAG1>(g1, (int)blockIdx.x, 0);
   } else {
     if (NW2 < NW1 && (int)(threadIdx.x >> 6) >= NW2) return;
     gemm_small_body<S, A2, B2, NW2, TS2, OS2>(g2, (int)blockIdx.x - n1, 0);
@@ -859,6 +948,7 @@ static long long* small_stamps(int which) {
     for (int i = 0; i < 16; ++i) p[i] = 0;
     static long long* keep = p;
     atexit([] {
+      // (a staged body -- PARTS >= 1 -- stamps 2 and 3 without a wait: the loads ahead of the first MFMA are out; the first part's MFMAs are issued)
       static const char* names[9] = {"entry", "set-up done", "operand batch issued", "operand batch landed", "MFMAs done, partial in LDS",
                                      "all partials there (barrier)", "reduced + epilogue / loss head, stores issued", "tail done", "stores acknowledged"};
       std::fprintf(stderr, "[small stamps %d] tile 0, thread 0, us since its workgroup began:", want);
@@ -1217,6 +1307,13 @@ void launch_gemm_small(const GemmProblem& p, hipStream_t s) {
   else launch_small_t<float>(p, s);
 }
 
+// What the weight-gradient pair's 32x32 body ships with (gemm_small_body, PARTS / STAG).  Measured on the step, kernel
+// average over 511 launches: the compiler's order 10.3 us, all 64 loads first (1 or 2 parts) 10.1, four
+// parts 9.7, eight parts -- two chunks ahead of the first MFMA, one chunk ahead from then on -- 9.5-9.6; the stagger moved
+// none of them by more than the run-to-run spread.
+constexpr int SMALL_PAIR_PARTS = 8;
+constexpr bool SMALL_PAIR_STAG = false;
+
 // Two weight-gradient GEMMs (dZ^T . A: A m-contiguous view of dZ, B n-contiguous) in one launch when the
 // heuristics pick the (16-wave one-shot 32x32, 8-wave 16x16) pair of configurations -- the shapes of a
 // wide hidden layer next to a narrow output layer.  Returns false when the pair is not of that form.
@@ -1250,7 +1347,28 @@ bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStr
   dim3 grid(n1 + n2), block(1024);
   // (both one-shot: the two-stage pipeline of the 16x16 body does not fit the 128 registers of a 1024-thread
   //  workgroup; the same K -- the batch -- puts both problems in the one-shot range together anyway)
-  launch_k((gemm_small_pair_kernel<float, 1, 0, 16, 32, 8, 1, 0, 8, 16, 8>), grid, block, 0, s, g1, g2, n1);
+  // who orders the big problem's 64 loads against its 32 MFMAs (gemm_small_body, PARTS / STAG; DESIGN.md 3.4 has the
+  // measurement): SMALL_PAIR_PARTS parts, staggered or not, is what ships; a development build can run every form.
+#define TOPS_PAIR(P, ST) launch_k((gemm_small_pair_kernel<float, 1, 0, 16, 32, 8, 1, 0, 8, 16, 8, P, ST>), grid, block, 0, s, g1, g2, n1)
+#ifdef TOPS_AB_KNOBS
+  static const int parts = [] { const char* e = ab_getenv("TOPS_SMALL_PARTS"); return e ? atoi(e) : SMALL_PAIR_PARTS; }();
+  static const int stag = [] { const char* e = ab_getenv("TOPS_SMALL_STAGGER"); return e ? atoi(e) : (int)SMALL_PAIR_STAG; }();
+  switch (parts * 2 + (stag ? 1 : 0)) {
+    case 0: TOPS_PAIR(0, false); break;   // (the compiler's order: what ran before the order was pinned)
+    case 2: TOPS_PAIR(1, false); break;
+    case 3: TOPS_PAIR(1, true); break;
+    case 4: TOPS_PAIR(2, false); break;
+    case 5: TOPS_PAIR(2, true); break;
+    case 8: TOPS_PAIR(4, false); break;
+    case 9: TOPS_PAIR(4, true); break;
+    case 16: TOPS_PAIR(8, false); break;
+    case 17: TOPS_PAIR(8, true); break;
+    default: TO_CHECK(false, TO_ERR_ARG, "TOPS_SMALL_PARTS is 0, 1, 2, 4 or 8 (TOPS_SMALL_STAGGER needs parts >= 1)");
+  }
+#else
+  TOPS_PAIR(SMALL_PAIR_PARTS, SMALL_PAIR_STAG);
+#endif
+#undef TOPS_PAIR
   TO_HIP(hipGetLastError());
   count_launch();
   return true;

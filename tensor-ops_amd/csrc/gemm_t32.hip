@@ -12,6 +12,13 @@
 // no barrier until the four partial tiles meet in LDS.  The MFMA stream (16 x v_mfma_f32_32x32x2_f32 per 32-k chunk = 1,024
 // cycles) hides the 8 DMA and 8 (k-contiguous) or 32 (row-contiguous) LDS reads of the next chunk.
 //
+// Eight waves a tile (the forward kernel, grids of at most one round of CUs).  One wave per SIMD runs wait -> fragment reads ->
+// DMA issue -> sixteen dependent MFMAs in series, 1,630 cycles a chunk for 1,024 of MFMAs; with a second wave on each SIMD
+// (w and w + 4) one's MFMA chain runs under the other's wait.  K is split eight ways in the same units of 16, every wave has ONE
+// chunk in flight in ONE 8 KiB stage (the bytes a CU has in flight stay what four waves x two chunks were: more in flight
+// only queues at the L2s), the eight partial tiles are added in wave order.  Measured on the step: the
+// stamped wave's K loop 4.2 -> 2.7 us, the tile 6.1 -> 5.8 us, the kernel 8.95 -> 8.35 us; with two stages a wave 8.9.
+//
 // Operand forms: KC = k-contiguous (X rows, W rows: image [x][32 k], 16-byte quads XOR-swizzled by x, fragments by
 // ds_read_b128 -- a lane takes four consecutive k and feeds them to four MFMA steps; A and B agree on which) and XC =
 // row-contiguous (dZ^T, X as the right operand: image [k][32 x], fragments by ds_read_b32).  MFMA step s = 4 i + j of a
@@ -91,8 +98,15 @@ __device__ __forceinline__ bool t32_tile_of(int tiles_m, int tiles_n, int gm, in
 // x & 7 (the first version) gives each group's even rows four keys: every slot hit twice, 8 LDS cycles a read instead of 4.
 __device__ __forceinline__ int t32_key(int x) { return (x >> 1) & 7; }
 
-template <bool AKC, bool BKC, bool ARAG = false, bool WT = false>
+// NW waves a tile (4: one per SIMD; 8: waves w and w + 4 share a SIMD, so one's MFMA chain runs while the other waits for its
+// DMA, reads fragments and issues the next chunk's DMA), NS stages a wave.  K is split NW ways in the same units of 16 and the
+// partial tiles are added in wave order 0 .. NW - 1.  Threads 0..255 run the epilogue (a float4 each).
+// EARLY: the first chunk's DMA leaves ahead of the epilogue's prefetch (which then sits between chunk 0 and chunk 1 in the
+// vmcnt order: the wait for chunk 0 covers it, nothing else changes).
+template <bool AKC, bool BKC, bool ARAG = false, bool WT = false, int NW = T32_NW, int NS = T32_NS, bool EARLY = false>
 __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, float* smem) {
+  constexpr int WAVE_F = NS * T32_STAGE;   // floats of LDS per wave
+  static_assert(WAVE_F >= 1024 + 64, "a wave's stage memory holds its partial tile and its row sums");
   static_assert(!ARAG || !AKC, "the dword form is for a row-contiguous A");
   constexpr int NA = ARAG ? 16 : 4, PER = NA + 4;   // DMA instructions per chunk
   const int tid = threadIdx.x, lane = tid & 63;
@@ -108,23 +122,26 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
   // the epilogue's operands do not depend on the product: their loads go out first
   const int erow = tid >> 3, ec4 = (tid & 7) * 4;
   const long grow = m0 + erow, gcol = n0 + ec4;
-  const bool evalid = grow < g.M && gcol < g.N;         // (N % 4 == 0: a quad is in or out)
+  const bool evalid = (NW == 4 || tid < 256) && grow < g.M && gcol < g.N;         // (N % 4 == 0: a quad is in or out)
   f32x4 pf_ci = {0.f, 0.f, 0.f, 0.f}, pf_hd = {0.f, 0.f, 0.f, 0.f}, pf_bias = {0.f, 0.f, 0.f, 0.f};
-  if (evalid) {
-    if (g.Cin) pf_ci = *reinterpret_cast<const f32x4*>(g.Cin + grow * g.c_sm + gcol);
-    if (g.dact) pf_hd = *reinterpret_cast<const f32x4*>(g.dact + grow * g.c_sm + gcol);
-    if (g.bias) pf_bias = *reinterpret_cast<const f32x4*>(g.bias + gcol);
-  }
+  auto prefetch_epilogue = [&] {
+    if (evalid) {
+      if (g.Cin) pf_ci = *reinterpret_cast<const f32x4*>(g.Cin + grow * g.c_sm + gcol);
+      if (g.dact) pf_hd = *reinterpret_cast<const f32x4*>(g.dact + grow * g.c_sm + gcol);
+      if (g.bias) pf_bias = *reinterpret_cast<const f32x4*>(g.bias + gcol);
+    }
+  };
+  if constexpr (!EARLY) prefetch_epilogue();
 
   // this wave's run of k, in units of 16
   const int U = (g.K + 15) / 16;
-  const int k0 = (int)((long)U * wave / T32_NW) * 16;
-  int k1 = (int)((long)U * (wave + 1) / T32_NW) * 16;
+  const int k0 = (int)((long)U * wave / NW) * 16;
+  int k1 = (int)((long)U * (wave + 1) / NW) * 16;
   if (k1 > g.K) k1 = g.K;
   const int nC = k1 > k0 ? (k1 - k0 + T32_BK - 1) / T32_BK : 0;
 
   typedef __attribute__((address_space(3))) void* lptr_t;
-  float* wsm = smem + wave * T32_WAVE;
+  float* wsm = smem + wave * WAVE_F;
   const unsigned lds_w = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(lptr_t)wsm);
 
   // per-lane byte offsets of the four 1-KiB pieces of an operand's image, relative to the chunk's scalar base
@@ -166,7 +183,7 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
   auto issue = [&, a_sx_l, M_l](int c) {
     const int seq = c;
     const int kc = k0 + c * T32_BK;
-    const unsigned st = lds_w + (unsigned)(seq % T32_NS) * (T32_STAGE * 4);
+    const unsigned st = lds_w + (unsigned)(seq % NS) * (T32_STAGE * 4);
     const char* ba = sa + (long)c * step_a;
     const char* bb = sb + (long)c * step_b;
     const bool full = kc + T32_BK <= k1;
@@ -222,9 +239,17 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
   float asum = 0.f;                      // sum over k of this lane's A elements (row sums of A: bias gradients)
   const bool want_rs = g.rowsum != nullptr && tile_n == 0;
 
-  const int PD = g.pd;
+  const int PD = g.pd < NS ? g.pd : NS;
   const int pro = nC < PD ? nC : PD;
-  for (int c = 0; c < pro; ++c) issue(c);
+  if constexpr (EARLY) {
+    if (pro > 0) issue(0);
+    __builtin_amdgcn_sched_barrier(0);
+    prefetch_epilogue();
+    __builtin_amdgcn_sched_barrier(0);
+    for (int c = 1; c < pro; ++c) issue(c);
+  } else {
+    for (int c = 0; c < pro; ++c) issue(c);
+  }
   stamp(1);
 
   // chunk c has landed when at most the DMA groups of the chunks issued after it are outstanding
@@ -239,7 +264,7 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
   // a half chunk (<= 16 k left of the wave's run) needs the first eight MFMA steps only
   auto steps_of = [&](int c) { return (k1 - (k0 + c * T32_BK)) > 16 ? 4 : 2; };
   auto read_frags = [&](int c, float (&fa)[16], float (&fb)[16]) {
-    const float* sp = wsm + (c % T32_NS) * T32_STAGE;
+    const float* sp = wsm + (c % NS) * T32_STAGE;
     const int nI = steps_of(c);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -302,9 +327,12 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
   if (want_rs) wsm[1024 + lane] = asum;
   __syncthreads();
   stamp(4);
-  f32x4 s = *reinterpret_cast<const f32x4*>(smem + erow * 32 + ec4);
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  if (NW == 4 || tid < 256) {
+    s = *reinterpret_cast<const f32x4*>(smem + erow * 32 + ec4);
 #pragma unroll
-  for (int w = 1; w < T32_NW; ++w) s += *reinterpret_cast<const f32x4*>(smem + w * T32_WAVE + erow * 32 + ec4);
+    for (int w = 1; w < NW; ++w) s += *reinterpret_cast<const f32x4*>(smem + w * WAVE_F + erow * 32 + ec4);
+  }
   if (evalid) {
     f32x4 v = s * g.alpha;
     if (g.Cin) v += pf_ci * g.beta;
@@ -333,7 +361,7 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
     if (m < g.M) {
       float t = 0.f;
 #pragma unroll
-      for (int w = 0; w < T32_NW; ++w) t += smem[w * T32_WAVE + 1024 + tid] + smem[w * T32_WAVE + 1024 + 32 + tid];
+      for (int w = 0; w < NW; ++w) t += smem[w * WAVE_F + 1024 + tid] + smem[w * WAVE_F + 1024 + 32 + tid];
       if (g.rowsum_acc) g.rowsum[m] = (g.rowsum_in ? g.rowsum_in[m] : g.rowsum[m]) + g.rowsum_alpha * t;
       else g.rowsum[m] = t;
     }
@@ -497,10 +525,10 @@ __global__ __launch_bounds__(256) void gemm_t32_head_kernel(T32Args g, T32HeadAr
   }
 }
 
-template <bool AKC, bool BKC>
-__global__ __launch_bounds__(256) void gemm_t32_kernel(T32Args g) {
+template <bool AKC, bool BKC, int NW = T32_NW, int NS = T32_NS, bool EARLY = false>
+__global__ __launch_bounds__(NW * 64) void gemm_t32_kernel(T32Args g) {
   extern __shared__ __attribute__((aligned(1024))) float t32_smem[];
-  gemm_t32_body<AKC, BKC>(g, (int)blockIdx.x, t32_smem);
+  gemm_t32_body<AKC, BKC, false, false, NW, NS, EARLY>(g, (int)blockIdx.x, t32_smem);
 }
 
 // Two weight-gradient contractions (dZ^T . A: both operands row-contiguous, K = the batch) in ONE launch: the first
@@ -611,24 +639,53 @@ static long t32_grid(const T32Args& g) {
 
 static void t32_attr(const void* k) { TO_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, T32_NW * T32_WAVE * 4)); }
 
+// The eight-wave form: only where the tile grid is at most one round of the device's CUs -- above that two
+// four-wave workgroups share a CU and already give every SIMD a second wave.  T32_W8_NS stages a wave: with ONE chunk in
+// flight per wave the bytes a CU has in flight are what the four-wave form's two chunks a wave were.
+constexpr int T32_W8_DEFAULT = 1;   // 1: route one-round grids to eight waves
+constexpr int T32_W8_NS = 1;
+constexpr bool T32_EARLY = true;    // the first chunk's DMA ahead of the epilogue prefetch
+
+template <int NW, int NS, bool EARLY>
+static void t32_launch_nw(const T32Args& g, bool akc, bool bkc, hipStream_t s) {
+  constexpr size_t lds = (size_t)NW * NS * T32_STAGE * 4;
+  static bool attr = false;
+  if (!attr) {
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<true, true, NW, NS, EARLY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<true, false, NW, NS, EARLY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<false, true, NW, NS, EARLY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<false, false, NW, NS, EARLY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
+  }
+  const dim3 grid((unsigned)t32_grid(g)), block(NW * 64);
+  if (akc && bkc) launch_k((gemm_t32_kernel<true, true, NW, NS, EARLY>), grid, block, lds, s, g);
+  else if (akc) launch_k((gemm_t32_kernel<true, false, NW, NS, EARLY>), grid, block, lds, s, g);
+  else if (bkc) launch_k((gemm_t32_kernel<false, true, NW, NS, EARLY>), grid, block, lds, s, g);
+  else launch_k((gemm_t32_kernel<false, false, NW, NS, EARLY>), grid, block, lds, s, g);
+}
+
 void launch_gemm_t32(const GemmProblem& p, hipStream_t s) {
   T32Args g;
   bool akc, bkc;
   TO_CHECK(t32_fill(p, g, akc, bkc), TO_ERR_STATE, "launch_gemm_t32: not applicable");
-  static bool attr = false;
-  if (!attr) {
-    t32_attr(reinterpret_cast<const void*>(gemm_t32_kernel<true, true>));
-    t32_attr(reinterpret_cast<const void*>(gemm_t32_kernel<true, false>));
-    t32_attr(reinterpret_cast<const void*>(gemm_t32_kernel<false, true>));
-    t32_attr(reinterpret_cast<const void*>(gemm_t32_kernel<false, false>));
-    attr = true;
+  static const int cus = [] { hipDeviceProp_t pr; int d = 0; return (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess) ? pr.multiProcessorCount : 0; }();
+  static const int waves = [] { const char* e = ab_getenv("TOPS_T32_WAVES"); return e ? atoi(e) : (T32_W8_DEFAULT ? 8 : 4); }();
+  const bool w8 = waves == 8 && t32_grid(g) <= cus;
+#ifdef TOPS_AB_KNOBS
+  static const int w8_ns = [] { const char* e = ab_getenv("TOPS_T32_W8_NS"); return e ? atoi(e) : T32_W8_NS; }();
+  static const int early = [] { const char* e = ab_getenv("TOPS_T32_EARLY"); return e ? atoi(e) : (int)T32_EARLY; }();
+  switch ((w8 ? (w8_ns == 1 ? 2 : 4) : 0) + (early ? 1 : 0)) {
+    case 0: t32_launch_nw<T32_NW, T32_NS, false>(g, akc, bkc, s); break;
+    case 1: t32_launch_nw<T32_NW, T32_NS, true>(g, akc, bkc, s); break;
+    case 2: t32_launch_nw<8, 1, false>(g, akc, bkc, s); break;
+    case 3: t32_launch_nw<8, 1, true>(g, akc, bkc, s); break;
+    case 4: t32_launch_nw<8, 2, false>(g, akc, bkc, s); break;
+    default: t32_launch_nw<8, 2, true>(g, akc, bkc, s); break;
   }
-  const dim3 grid((unsigned)t32_grid(g)), block(256);
-  const size_t lds = (size_t)T32_NW * T32_WAVE * 4;
-  if (akc && bkc) launch_k(gemm_t32_kernel<true, true>, grid, block, lds, s, g);
-  else if (akc) launch_k(gemm_t32_kernel<true, false>, grid, block, lds, s, g);
-  else if (bkc) launch_k(gemm_t32_kernel<false, true>, grid, block, lds, s, g);
-  else launch_k(gemm_t32_kernel<false, false>, grid, block, lds, s, g);
+#else
+  if (w8) t32_launch_nw<8, T32_W8_NS, T32_EARLY>(g, akc, bkc, s);
+  else t32_launch_nw<T32_NW, T32_NS, T32_EARLY>(g, akc, bkc, s);
+#endif
   TO_HIP(hipGetLastError());
   count_launch();
 }

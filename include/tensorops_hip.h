@@ -422,6 +422,42 @@ to_status to_rnn_stack_sgd(int n_layers, const int* state_act, const to_tensor* 
 to_status to_set_rnn_persistent(int on, int* previous_or_null);
 to_status to_rnn_stats(int64_t* persistent_runs, int64_t* stepwise_runs);
 
+/* `induceNetwork` (FeedForward.hs:150-164) of the same ffLayer stacks, iterated: gradient descent on the INPUT with the
+ * parameters fixed (app/MNIST.hs:357-365 runs 5000 such steps in a row), for every row of the hidden batch, in ONE call:
+ *   x_0 = x[r];   g_k = d/dx loss(net(x_k), y[r]);   x_{k+1} = x_k - rate * g_k,   k = 0 .. iters-1
+ *   out[r] = x_iters     gx[r] = g_{iters-1}     losses[r, k] = loss(net(x_k), y[r])   (the loss BEFORE step k+1)
+ * hidden_act TO_ACT_LOGISTIC; (out_act, loss) (TO_ACT_SOFTMAX, TO_LOSS_CROSS_ENTROPY) or (TO_ACT_LOGISTIC,
+ * TO_LOSS_SQUARED_ERROR), anything else TO_ERR_UNSUPPORTED with nothing written; the losses are to_fflayer_stack_grad's.
+ * Targets are arbitrary vectors, not only one-hot.  No clamping of x: the reference has none.
+ *   x               [B; i0] or unbatched [i0] (one row);
+ *   y               [B; n_L] of x's batch, or unbatched [n_L]: one target for every row;
+ *   out             caller-allocated, contiguous, of x's shape, batch and dtype; MAY BE x ITSELF (in place);
+ *   gx_or_null      like out: the gradient of the last iteration -- with iters = 1 it is `head' (netGrad ...)`, the input
+ *                   cotangent that to_fflayer_stack_grad does not return.  Needs iters >= 1 (TO_ERR_ARG);
+ *   losses_or_null  contiguous [B; iters] (unbatched [iters] for an unbatched x).
+ * iters >= 0; iters == 0 copies x to out bit for bit and touches nothing else.  fp32 or fp64, any B, any widths, one layer
+ * or more: never TO_ERR_UNSUPPORTED for a valid stack and pair.  Parameters and y are only read; pending operands are
+ * produced first; refused during graph capture (TO_ERR_STATE); blocks before it returns; keeps no handle.  A refused or
+ * failed call leaves out, gx and losses untouched.
+ * Routes.  Per iteration (A): one GEMM a layer forward (bias + logistic in its epilogue), the loss head, the cotangents
+ * back, and the last contraction with the step in its epilogue; takes every stack, launches grow with iters.  Persistent
+ * (B, csrc/induce_seq.hip): all iterations of all rows in ONE launch, the parameters in LDS, layer 1 split by columns over
+ * G <= 32 workgroups of one XCD that exchange o1 partial sums an iteration (G = 1: no exchange).  Its range: 1..6 layers,
+ * n_L <= 64, the smallest G whose workgroups fit 160 KiB of LDS -- fp32 784-300-100-10 at G = 32, fp64 784-300-100-10 does
+ * not fit (route A) -- and, for G > 1, a device on which the workgroups of the group share an XCD (probed; elsewhere the
+ * call takes route A).  A wait of the persistent kernel that times out (TOPS_ONLINE_TIMEOUT_S, 2 s) is TO_ERR_HIP naming the
+ * iteration; there is no retry and no silent fall-back.  On either route a row's bits depend neither on B nor on the row's
+ * place in the batch, and iters = a followed by iters = b on the result equals iters = a + b bit for bit.
+ * to_set_induce_persistent: 0 route A; 1 automatic (default): route B where it is known to be ahead -- until the scan of
+ * DESIGN.md section 3.3 has been run on a device that is a plan of one workgroup a row (G = 1) with B <= 256, route A
+ * otherwise; 2 route B wherever its plan fits, A otherwise.  Process-wide.  to_induce_stats counts calls (iters >= 1) by
+ * the route that ran. */
+to_status to_fflayer_stack_induce(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                  int loss, to_tensor x, to_tensor y, double rate, int64_t iters, to_tensor out,
+                                  to_tensor gx_or_null, to_tensor losses_or_null);
+to_status to_set_induce_persistent(int on, int* previous_or_null);
+to_status to_induce_stats(int64_t* persistent_runs, int64_t* per_iteration_runs);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 /* Average duration (ms) of kernels enqueued between the two calls, measured with
  * HIP events on the library's stream. */

@@ -128,6 +128,10 @@ SIGNATURES = {
                          c_tensor],
     "to_set_rnn_persistent": [C.c_int, C.POINTER(C.c_int)],
     "to_rnn_stats": [i64p, i64p],
+    "to_fflayer_stack_induce": [C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int, c_tensor,
+                                c_tensor, C.c_double, C.c_int64, c_tensor, c_tensor, c_tensor],
+    "to_set_induce_persistent": [C.c_int, C.POINTER(C.c_int)],
+    "to_induce_stats": [i64p, i64p],
     "to_graph_online_sgd": [c_graph, c_tensor, c_tensor, c_tensor, c_tensor, C.c_int64, i64p, C.POINTER(C.c_int)],
     "to_online_sgd_stats": [i64p, i64p],
     "to_timer_start": [],

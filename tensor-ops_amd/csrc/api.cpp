@@ -3043,6 +3043,222 @@ to_status to_rnn_stats(int64_t* persistent_runs, int64_t* stepwise_runs) {
   API_END
 }
 
+// ---- `induceNetwork` iterated (FeedForward.hs:150-164; app/MNIST.hs:357-365: 5000 dependent steps on the input) --------
+// Route A, per iteration: the forward of to_fflayer_stack_infer, launch_loss_grad_rows, the cotangents back through the
+// layers and the last contraction with the step in its epilogue (x <- 1 x + (-rate) dz_1 W_1: alpha = -rate, beta = 1,
+// Cin = C = x; when gx is wanted the last iteration runs the plain product as well, into gx).  Takes every valid stack; its launch count grows with iters.  Route B, persistent (induce_seq.hip): all
+// iterations of all rows in ONE launch, where its plan fits (and, for a plan of several workgroups a row, where the
+// placement probe holds).  Both iterate on a private copy of x; the caller's tensors are written once, at the end.
+static int g_induce_persistent = 1;                       // to_set_induce_persistent: 0 per iteration, 1 auto, 2 wherever in range
+static int64_t g_induce_persistent_runs = 0, g_induce_iter_runs = 0;
+
+// The automatic rule.  NOT MEASURED YET: tools/induce_scan.py has not been run on a device for this change (see
+// profiles/r08_induce_scan.txt and DESIGN.md section 3.3), so the default takes the persistent route only where its
+// advantage follows from counting and needs no measurement to hold: a plan of ONE workgroup a row (no exchange, no
+// placement precondition, nobody to wait for) with at most 256 rows, where every row has a workgroup of its own and an
+// iteration is a handful of passes over LDS against six or more dependent launches on route A.  Plans of several
+// workgroups a row (the reference's 784-300-100-10 in fp32) and longer batches stay on route A by default until the scan
+// has been run and says otherwise; to_set_induce_persistent(2) forces them.
+static bool induce_auto_persistent(const InduceSeqPlan& plan, int64_t B) {
+  return plan.G == 1 && B <= 256;
+}
+
+static void induce_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss,
+                        to_tensor x, to_tensor y, double rate, int64_t iters, to_tensor out, to_tensor gx, to_tensor losses) {
+  const std::string F = "to_fflayer_stack_induce: ";
+  require_init();
+  no_capture("to_fflayer_stack_induce");
+  NONNULL(w); NONNULL(b); NONNULL(x); NONNULL(y); NONNULL(out);
+  TO_CHECK(n_layers >= 1, TO_ERR_ARG, F + "need at least one layer");
+  TO_CHECK(iters >= 0, TO_ERR_ARG, F + "negative iteration count");
+  TO_CHECK(!gx || iters >= 1, TO_ERR_ARG, F + "gx is the gradient of the last iteration: it needs iters >= 1");
+  stack_hidden_act_check(hidden_act);
+  const bool sm_ce = out_act == TO_ACT_SOFTMAX && loss == TO_LOSS_CROSS_ENTROPY;
+  const bool lg_se = out_act == TO_ACT_LOGISTIC && loss == TO_LOSS_SQUARED_ERROR;
+  TO_CHECK(sm_ce || lg_se, TO_ERR_UNSUPPORTED, F + "(softmax, crossEntropy) or (logistic, squaredError) only");
+  TO_CHECK(x->rank == 1 && x->dims[0] >= 1, TO_ERR_SHAPE, F + "x must be a (batched) vector, got " + shape_str(x));
+  const int dt = x->dtype;
+  const int64_t i0 = x->dims[0];
+  const int64_t nL = stack_params_check(n_layers, w, b, nullptr, nullptr, dt, i0);
+  const int64_t B = x->batch > 0 ? x->batch : 1;
+  TO_CHECK(y->dtype == dt, TO_ERR_ARG, F + "x and y have different dtypes");
+  TO_CHECK(y->rank == 1 && y->dims[0] == nL && (y->batch == 0 || y->batch == x->batch), TO_ERR_SHAPE,
+           F + "y must be " + std::to_string(nL) + "-vectors of x's batch (or one unbatched target), got " + shape_str(y));
+  auto like_x = [&](to_tensor t, const char* what) {
+    TO_CHECK(t->dtype == dt, TO_ERR_ARG, F + "x and " + what + " have different dtypes");
+    TO_CHECK(t->rank == 1 && t->dims[0] == i0 && t->batch == x->batch, TO_ERR_SHAPE,
+             F + what + " must have x's shape and batch, got " + shape_str(t));
+    TO_CHECK(t->contiguous(), TO_ERR_ARG, F + what + " must be contiguous");
+  };
+  like_x(out, "out");
+  if (gx) like_x(gx, "gx");
+  if (losses) {
+    TO_CHECK(losses->dtype == dt, TO_ERR_ARG, F + "x and losses have different dtypes");
+    TO_CHECK(losses->rank == 1 && losses->dims[0] == iters && losses->batch == x->batch, TO_ERR_SHAPE,
+             F + "losses must be [B; " + std::to_string(iters) + "] of x's batch, got " + shape_str(losses));
+    TO_CHECK(losses->contiguous(), TO_ERR_ARG, F + "losses must be contiguous");
+  }
+  TO_CHECK(B <= 2147483647LL && B * i0 <= (1LL << 40), TO_ERR_SHAPE, F + "too many rows");
+
+  // ---- operands produced; destinations claimed -----------------------------------------------------------------------
+  ensure(x);
+  ensure(y);
+  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); }
+  auto claim = [](to_tensor t) { ensure(t); before_write(t); t->id = fresh_id(); };
+  const int64_t es = dt == TO_F64 ? 8 : 4;
+  auto at = [es](void* p, int64_t elems) { return static_cast<void*>(static_cast<char*>(p) + elems * es); };
+  if (iters == 0) {  // x to out bit for bit; nothing else is touched, neither route counted
+    if (out != x) {
+      claim(out);
+      if (out->ptr != x->ptr) {
+        const int64_t dd[2] = {B, i0}, ss[2] = {x->batch > 0 ? x->bstride : 0, x->strides[0]};
+        launch_copy_strided(dt, x->ptr, out->ptr, 2, dd, ss, S());
+      }
+    }
+    TO_HIP(hipStreamSynchronize(S()));
+    return;
+  }
+  claim(out);
+  if (gx) claim(gx);
+  if (losses) claim(losses);
+
+  // the private copy of x the iterations run on, contiguous [B][i0]
+  const int64_t dx[2] = {B, i0};
+  Holder cur(new_tensor(2, dx, 0, dt));
+  {
+    const int64_t ss[2] = {x->batch > 0 ? x->bstride : 0, x->strides[0]};
+    launch_copy_strided(dt, x->ptr, cur.t->ptr, 2, dx, ss, S());
+  }
+  Holder gxs, lt;
+  if (gx) gxs.t = new_tensor(2, dx, 0, dt);
+  const int64_t dl[2] = {B, iters};
+  if (losses) lt.t = new_tensor(2, dl, 0, dt);
+  // targets with unit element stride; rows y_sm apart (0: one target for every row)
+  Holder yc(y->dims[0] > 1 && y->strides[0] != 1 ? contiguous(y) : nullptr);
+  const to_tensor yr = yc.t ? yc.t : y;
+  const int64_t y_sm = y->batch > 0 ? yr->bstride : 0;
+
+  int64_t dims[INDUCE_MAX_LAYERS + 1] = {0};
+  InduceSeqPlan plan;
+  bool persistent = false;
+  if (g_induce_persistent != 0 && n_layers <= INDUCE_MAX_LAYERS) {
+    dims[0] = i0;
+    for (int l = 0; l < n_layers; ++l) dims[l + 1] = w[l]->dims[0];
+    persistent = induce_seq_plan(dt, n_layers, dims, B, iters, &plan) &&
+                 (g_induce_persistent == 2 || induce_auto_persistent(plan, B)) &&
+                 (plan.G == 1 || online_sgd_placement_ok(S()));   // (the exchange's precondition: one XCD's L2)
+  }
+
+  if (persistent) {
+    const void *wp[INDUCE_MAX_LAYERS], *bp[INDUCE_MAX_LAYERS];
+    for (int l = 0; l < n_layers; ++l) { wp[l] = w[l]->ptr; bp[l] = b[l]->ptr; }
+    launch_induce_seq(dt, plan, n_layers, dims, wp, bp, cur.t->ptr, yr->ptr, y_sm, gxs.t ? gxs.t->ptr : nullptr,
+                      lt.t ? lt.t->ptr : nullptr, B, iters, rate, sm_ce ? 1 : 2, S());
+    TO_HIP(hipStreamSynchronize(S()));   // the watchdog's verdict is read before anything of the caller's is written
+    int64_t bad_row = 0;
+    const int64_t bad = induce_seq_status(&bad_row);
+    TO_CHECK(bad == 0, TO_ERR_HIP,
+             F + "the persistent kernel gave up waiting for a workgroup at iteration " + std::to_string(bad - 1) + " of row " +
+                 std::to_string(bad_row) + " (out, gx and losses are untouched)");
+    g_induce_persistent_runs++;
+  } else {
+    // route A.  y as [B][nL] rows (launch_loss_grad_rows reads one target per row)
+    Holder yt;
+    const void* yp = yr->ptr;
+    if (B > 1 && (y->batch == 0 || y_sm != nL)) {
+      const int64_t dy[2] = {B, nL};
+      yt.t = new_tensor(2, dy, 0, dt);
+      if (y->batch == 0) {
+        launch_bcast_axis(dt, yr->ptr, yt.t->ptr, 1, B, nL, 0, S());
+      } else {
+        const int64_t ss[2] = {y_sm, 1};
+        launch_copy_strided(dt, yr->ptr, yt.t->ptr, 2, dy, ss, S());
+      }
+      yp = yt.t->ptr;
+    }
+    std::vector<Holder> act(n_layers), dz(n_layers);   // act[l]: [B][n_l], the last one z_L; dz[l]: the cotangent of z_l
+    for (int l = 0; l < n_layers; ++l) {
+      const int64_t d2[2] = {B, w[l]->dims[0]};
+      act[l].t = new_tensor(2, d2, 0, dt);
+      dz[l].t = new_tensor(2, d2, 0, dt);
+    }
+    Holder lcol;   // losses as [iters][B]: column k of the caller's [B][iters] is one contiguous run here
+    if (losses) {
+      const int64_t d2[2] = {iters, B};
+      lcol.t = new_tensor(2, d2, 0, dt);
+    }
+    void* xp = cur.t->ptr;
+    for (int64_t k = 0; k < iters; ++k) {
+      const void* prev = xp;
+      int64_t prev_n = i0;
+      for (int l = 0; l < n_layers; ++l) {   // a_l = logistic(a_{l-1} W_l^T + b_l); the last layer: z_L
+        const int64_t n = w[l]->dims[0];
+        GemmProblem p = rnn_problem(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, act[l].t->ptr, B, n, prev_n);
+        p.bias = b[l]->ptr;
+        if (l + 1 < n_layers) p.act = 1;
+        rnn_gemm(p);
+        prev = act[l].t->ptr;
+        prev_n = n;
+      }
+      launch_loss_grad_rows(dt, act[n_layers - 1].t->ptr, yp, dz[n_layers - 1].t->ptr, lcol.t ? at(lcol.t->ptr, k * B) : nullptr,
+                            B, nL, sm_ce ? 0 : 1, S());
+      for (int l = n_layers - 1; l > 0; --l) {   // dz_{l-1} = (dz_l W_l) (.) a_{l-1} (1 - a_{l-1})
+        const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
+        GemmProblem q = rnn_problem(dt, dz[l].t->ptr, n, 1, w[l]->ptr, m, 1, dz[l - 1].t->ptr, B, m, n);
+        q.dact = act[l - 1].t->ptr;
+        rnn_gemm(q);
+      }
+      const int64_t n1 = w[0]->dims[0];
+      GemmProblem q = rnn_problem(dt, dz[0].t->ptr, n1, 1, w[0]->ptr, i0, 1, xp, B, i0, n1);
+      if (gx && k + 1 == iters) {
+        // the plain product is wanted too: one more contraction, once a call.  The step itself is taken by the SAME launch
+        // as in every other iteration (below), so that out's bits do not depend on whether gx was asked for -- an axpy
+        // behind the plain product would round alpha * acc + x differently from the epilogue
+        GemmProblem qg = q;
+        qg.C = gxs.t->ptr;
+        rnn_gemm(qg);
+      }
+      q.alpha = -rate;   // x <- 1 x + (-rate) dz_1 W_1 in the contraction's epilogue
+      q.beta = 1.0;
+      q.Cin = xp;
+      rnn_gemm(q);
+    }
+    if (losses) {   // [iters][B] -> [B][iters]
+      const int64_t ss[2] = {1, B};
+      launch_copy_strided(dt, lcol.t->ptr, lt.t->ptr, 2, dl, ss, S());
+    }
+    g_induce_iter_runs++;
+  }
+  TO_HIP(hipMemcpyAsync(out->ptr, cur.t->ptr, (size_t)(B * i0 * es), hipMemcpyDeviceToDevice, S()));
+  if (gx) TO_HIP(hipMemcpyAsync(gx->ptr, gxs.t->ptr, (size_t)(B * i0 * es), hipMemcpyDeviceToDevice, S()));
+  if (losses) TO_HIP(hipMemcpyAsync(losses->ptr, lt.t->ptr, (size_t)(B * iters * es), hipMemcpyDeviceToDevice, S()));
+  TO_HIP(hipStreamSynchronize(S()));
+}
+
+to_status to_fflayer_stack_induce(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                  int loss, to_tensor x, to_tensor y, double rate, int64_t iters, to_tensor out,
+                                  to_tensor gx_or_null, to_tensor losses_or_null) {
+  API_BEGIN
+  induce_impl(n_layers, w, b, hidden_act, out_act, loss, x, y, rate, iters, out, gx_or_null, losses_or_null);
+  API_END
+}
+
+to_status to_set_induce_persistent(int on, int* previous_or_null) {
+  API_BEGIN
+  TO_CHECK(on >= 0 && on <= 2, TO_ERR_ARG,
+           "to_set_induce_persistent: 0 (per iteration), 1 (automatic) or 2 (wherever in range)");
+  if (previous_or_null) *previous_or_null = g_induce_persistent;
+  g_induce_persistent = on;
+  API_END
+}
+
+to_status to_induce_stats(int64_t* persistent_runs, int64_t* per_iteration_runs) {
+  API_BEGIN
+  if (persistent_runs) *persistent_runs = g_induce_persistent_runs;
+  if (per_iteration_runs) *per_iteration_runs = g_induce_iter_runs;
+  API_END
+}
+
 // Is the captured step the trainNetwork step of an ffLayer stack on ONE sample?  Reads the launches the planner made of it:
 //   forward   l = 1..L-1 : a_l = logistic(W_l a_{l-1} + b_l)              (GEMV, bias + activation in the epilogue)
 //             l = L      : z_L = W_L a_{L-1} + b_L -> loss head -> dz_L   [-> tail: dz_{L-1}]

@@ -444,6 +444,21 @@ struct RnnSeqPlan {
 bool rnn_seq_plan(int dtype, int64_t H, int64_t B, RnnSeqPlan* p);
 void launch_rnn_seq(int dtype, bool reverse, const RnnSeqPlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T,
                     int64_t H, hipStream_t s);
+// induce_seq.hip: every iteration of `induceNetwork` on every row in one launch (to_fflayer_stack_induce, route B).
+// X [B][i0] contiguous: x_0 on entry, x_iters on exit; gx [B][i0] (optional) the last iteration's gradient; losses
+// [B][iters] (optional).  A plan with G > 1 may only be launched where online_sgd_placement_ok() holds.
+constexpr int INDUCE_MAX_LAYERS = 6;
+struct InduceSeqPlan {
+  int G = 1;          // workgroups that share a row (layer 1 split by columns)
+  int cw = 0;         // columns of layer 1 per workgroup
+  size_t lds = 0;     // dynamic LDS bytes
+  int64_t grid = 0;   // workgroups
+};
+bool induce_seq_plan(int dtype, int L, const int64_t* dims, int64_t B, int64_t iters, InduceSeqPlan* plan);
+void launch_induce_seq(int dtype, const InduceSeqPlan& plan, int L, const int64_t* dims, const void* const* W,
+                       const void* const* b, void* X, const void* Y, int64_t y_sm, void* gx, void* losses, int64_t B,
+                       int64_t iters, double rate, int head, hipStream_t s);
+int64_t induce_seq_status(int64_t* row);   // 0, or the iteration (1-based) at which a wait timed out
 
 }  // namespace to
 

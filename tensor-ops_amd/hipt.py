@@ -514,6 +514,34 @@ class HipT:
         check(lib().to_rnn_stats(C.byref(p), C.byref(q)))
         return p.value, q.value
 
+    # -- induceNetwork iterated (to_fflayer_stack_induce) ----------------------------------------
+    def induce_stack(self, ws, bs, x, y, rate, iters, out_act="softmax", loss="crossEntropy", want_gx=False,
+                     want_losses=False, in_place=False):
+        """`induceNetwork` applied `iters` times to every row of x with the parameters fixed (to_fflayer_stack_induce):
+        (out -- x itself when in_place --, gx of the last iteration or None, losses [B; iters] or None)"""
+        shape, batch = x._shape()
+        out = x if in_place else self._alloc(shape, batch)
+        gx = self._alloc(shape, batch) if want_gx else None
+        losses = self._alloc((iters,), batch) if want_losses else None
+        check(lib().to_fflayer_stack_induce(len(ws), _arr(ws), _arr(bs), 0, self._RNN_OUT[out_act], self._RNN_LOSS[loss],
+                                            x.h, y.h, float(rate), int(iters), out.h,
+                                            gx.h if gx is not None else None, losses.h if losses is not None else None))
+        return out, gx, losses
+
+    @staticmethod
+    def induce_persistent(on):
+        """to_set_induce_persistent: 0 per iteration, 1 automatic, 2 wherever in range; returns the previous setting"""
+        prev = C.c_int()
+        check(lib().to_set_induce_persistent(int(on), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
+    def induce_stats():
+        """(persistent runs, per-iteration runs)"""
+        p, q = C.c_int64(), C.c_int64()
+        check(lib().to_induce_stats(C.byref(p), C.byref(q)))
+        return p.value, q.value
+
     # -- batching -------------------------------------------------------------------------
     def batch_sum(self, x):
         h = _out()

@@ -203,7 +203,7 @@ struct OuterArgs {
 // C[m][n] = alpha sum_{k < K} a[m][k] b[k][n] (+ beta Cin + bias[n], activation), K <= 16: an outer product (K = 1) or the weight
 // gradient of a minibatch of a few samples.  A thread owns W consecutive columns and keeps b[.][n .. n + W) in registers; the rows
 // of its share pass by once -- the bound is the store of C.
-template <class S, int W, int KB>   // KB: 1, 8 or 16 -- the rank rounded up (the b rows beyond K are zero)
+template <class S, int W, int KB>   // KB: 1, 8 or 16 -- the rank rounded up (the b rows AND the a values beyond K are zero)
 __global__ __launch_bounds__(256) void outer_kernel(OuterArgs g) {
   typedef typename V4<S>::type S4;
   const long n = ((long)blockIdx.x * 256 + threadIdx.x) * W;
@@ -217,7 +217,8 @@ __global__ __launch_bounds__(256) void outer_kernel(OuterArgs g) {
   for (int k = 0; k < KB; ++k)
 #pragma unroll
     for (int e = 0; e < W; ++e) bv[k][e] = k < g.K ? (S)g.alpha * b[k * g.b_sk + (n + e) * g.b_sn] : S(0);
-  long ak[KB];   // (element offsets of a row's K values; beyond K: the first one again, times a zero)
+  long ak[KB];   // (element offsets of a row's K values; beyond K the load is the first one again and a zero is SELECTED in its place:
+                 //  `a[m][0] * 0` would turn an infinity or a NaN at a[m][0] into a NaN in every output of the row)
 #pragma unroll
   for (int k = 0; k < KB; ++k) ak[k] = (k < g.K ? k : 0) * g.a_sk;
 #pragma unroll
@@ -229,7 +230,8 @@ __global__ __launch_bounds__(256) void outer_kernel(OuterArgs g) {
     for (int e = 0; e < W; ++e) v[e] = bi[e];
 #pragma unroll
     for (int k = 0; k < KB; ++k) {
-      const S am = a[m * g.a_sm + ak[k]];
+      const S ld = a[m * g.a_sm + ak[k]];
+      const S am = k < g.K ? ld : S(0);
 #pragma unroll
       for (int e = 0; e < W; ++e) v[e] += am * bv[k][e];
     }

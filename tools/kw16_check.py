@@ -5,6 +5,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from tensor_ops_amd.hipt import HipT
+from tools import poison   # (FUZZ_POISON=1: every case once with +-inf / NaN in the operands, once more clean)
 T = HipT(0)
 
 
@@ -19,20 +20,22 @@ def check():
                 if (ta and m % 4) or (not tb and n % 4):
                     continue
                 rng = np.random.default_rng(m + 3 * k + 7 * n + ta * 2 + tb)
-                a = rng.integers(-2, 3, size=(m, k)).astype(np.float32)
-                b = rng.integers(-2, 3, size=(k, n)).astype(np.float32)
-                da = T.transp(T.put(np.ascontiguousarray(a.T))) if ta else T.put(a)
-                db = T.transp(T.put(np.ascontiguousarray(b.T))) if tb else T.put(b)
-                l0 = T.stats()["launches"]
-                got = T.gmul(1, 1, 1, da, db).numpy()
-                nl = T.stats()["launches"] - l0
-                want = (a.astype(np.float64) @ b.astype(np.float64)).astype(np.float32)
-                ok = np.array_equal(got, want)
-                bad += not ok
-                if not ok:
-                    w = np.argwhere(got != want)
-                    print(m, k, n, "ta", ta, "tb", tb, "launches", nl, "MISMATCH %d of %d, max %g; rows %s cols %s" % (
-                        len(w), got.size, np.abs(got - want).max(), np.unique(w[:, 0])[:12], np.unique(w[:, 1])[:12]))
+                a0 = rng.integers(-2, 3, size=(m, k)).astype(np.float32)
+                b0 = rng.integers(-2, 3, size=(k, n)).astype(np.float32)
+                for a, b in poison.rounds(a0, b0):
+                    da = T.transp(T.put(np.ascontiguousarray(a.T))) if ta else T.put(a)
+                    db = T.transp(T.put(np.ascontiguousarray(b.T))) if tb else T.put(b)
+                    l0 = T.stats()["launches"]
+                    got = T.gmul(1, 1, 1, da, db).numpy()
+                    nl = T.stats()["launches"] - l0
+                    want = poison.want_product(a, b, np.float32) if poison.ON else (a.astype(np.float64) @ b.astype(np.float64)).astype(np.float32)
+                    ok = poison.same(got, want) if poison.ON else np.array_equal(got, want)
+                    bad += not ok
+                    if not ok:
+                        w = np.argwhere(got != want)
+                        print(m, k, n, "ta", ta, "tb", tb, "launches", nl, "MISMATCH %d of %d, max %g; rows %s cols %s" % (
+                            len(w), got.size, np.abs(got - want).max(), np.unique(w[:, 0])[:12], np.unique(w[:, 1])[:12]))
+    poison.report("kw16_check")
     print("kw16_check mismatches", bad)
     sys.exit(1 if bad else 0)
 

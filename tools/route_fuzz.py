@@ -6,6 +6,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from tensor_ops_amd.hipb import HipB
+from tools import poison   # (FUZZ_POISON=1: every case once with +-inf / NaN in the operands, once more clean)
 F64 = os.environ.get("ROUTE_DTYPE") == "f64"
 DT = np.float64 if F64 else np.float32
 B = HipB(0, dtype=DT); T = B.T
@@ -34,18 +35,24 @@ for c in range(cases):
     if 2.0 * m * n * k > 6e9 or max(m * k, k * n, m * n) > 1.5e8:
         continue
     ta, tb, beta = int(rng.integers(0, 2)), int(rng.integers(0, 2)), int(rng.integers(0, 3)) == 0
-    a = rng.integers(-2, 3, (m, k)).astype(DT); b = rng.integers(-2, 3, (k, n)).astype(DT)
-    da = T.transp(T.put(np.ascontiguousarray(a.T))) if ta else T.put(a)
-    db = T.transp(T.put(np.ascontiguousarray(b.T))) if tb else T.put(b)
-    want = a.astype(np.float64) @ b.astype(np.float64)
-    if beta:
-        cc = rng.integers(-4, 5, (m, n)).astype(DT)
-        got = B.gemm(-2.0, da, db, (3.0, T.put(cc))).numpy()
-        want = -2.0 * want + 3.0 * cc
-    else:
-        got = T.gmul(1, 1, 1, da, db).numpy()
-    ok = np.array_equal(got.astype(np.float64), want)
-    bad += not ok
-    if not ok:
-        print("BAD %d x %d x %d ta %d tb %d beta %d  max err %g" % (m, k, n, ta, tb, beta, np.max(np.abs(got - want))), flush=True)
+    a0 = rng.integers(-2, 3, (m, k)).astype(DT); b0 = rng.integers(-2, 3, (k, n)).astype(DT)
+    cc = rng.integers(-4, 5, (m, n)).astype(DT) if beta else None
+    for a, b in poison.rounds(a0, b0):
+        da = T.transp(T.put(np.ascontiguousarray(a.T))) if ta else T.put(a)
+        db = T.transp(T.put(np.ascontiguousarray(b.T))) if tb else T.put(b)
+        if poison.ON:
+            want = poison.want_product(a, b, np.float64, *((-2.0, 3.0, cc) if beta else ()))
+        else:
+            want = a.astype(np.float64) @ b.astype(np.float64)
+        if beta:
+            got = B.gemm(-2.0, da, db, (3.0, T.put(cc))).numpy()
+            if not poison.ON:
+                want = -2.0 * want + 3.0 * cc
+        else:
+            got = T.gmul(1, 1, 1, da, db).numpy()
+        ok = poison.same(got.astype(np.float64), want) if poison.ON else np.array_equal(got.astype(np.float64), want)
+        bad += not ok
+        if not ok:
+            print("BAD %d x %d x %d ta %d tb %d beta %d  max err %g" % (m, k, n, ta, tb, beta, np.max(np.abs(got - want))), flush=True)
+poison.report("route_fuzz")
 print("route_fuzz cases %d seed %d mismatches %d" % (cases, seed, bad))

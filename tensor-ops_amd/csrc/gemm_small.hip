@@ -89,6 +89,26 @@ __device__ __forceinline__ double log_s(double x) { return log(x); }
 __device__ __forceinline__ float max_s(float a, float b) { return fmaxf(a, b); }
 __device__ __forceinline__ double max_s(double a, double b) { return fmax(a, b); }
 
+// The value of lane (l ^ OFF) within the lane's row of sixteen, OFF = 8, 4, 2, 1: what the loss head's sixteen-lane
+// butterflies exchange.  fp32: a row-local DPP move (a few cycles; the compiler folds it into the add or the max) instead
+// of __shfl_xor's ds_bpermute_b32, an LDS round trip with an lgkmcnt wait -- twelve of those in one dependent chain were
+// most of the head.  Every lane of the wave is active where the head runs.  fp64 keeps the shuffle.
+template <int OFF>
+__device__ __forceinline__ float xor16(float x) {
+  const int v = __float_as_int(x);
+  if constexpr (OFF == 1) return __int_as_float(__builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));        // quad_perm:[1,0,3,2]
+  else if constexpr (OFF == 2) return __int_as_float(__builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));   // quad_perm:[2,3,0,1]
+  else if constexpr (OFF == 8) return __int_as_float(__builtin_amdgcn_update_dpp(v, v, 0x128, 0xF, 0xF, false));  // row_ror:8
+  else {
+    static_assert(OFF == 4, "xor 8, 4, 2 or 1");
+    // lanes 0-3 and 8-11 of the row (banks 0 and 2) read four lanes up, lanes 4-7 and 12-15 four lanes down
+    const int up = __builtin_amdgcn_update_dpp(v, v, 0x104, 0xF, 0x5, false);                                     // row_shl:4
+    return __int_as_float(__builtin_amdgcn_update_dpp(up, v, 0x114, 0xF, 0xA, false));                            // row_shr:4
+  }
+}
+template <int OFF>
+__device__ __forceinline__ double xor16(double x) { return __shfl_xor(x, OFF, 64); }
+
 // AMODE 0: A k-contiguous (a_sk == 1)   1: A m-contiguous / general strides
 // BMODE 0: B n-contiguous / general     1: B k-contiguous (b_sk == 1)
 // Within a chunk of 8 k the MFMA j of half-wave `half` consumes k = k0 + 4*half + j, for A and B alike.
@@ -409,16 +429,16 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
         const bool valid = row < g.M && col < g.N;
         v = v * g.alpha + pf_bias;
         const S t = valid ? g.target[row * g.c_sm + col] : S(0);
+        // (the same pairs in the same order as the shuffles they replace -- xor 8, 4, 2, 1 -- so the same bits)
         auto sum16 = [](S x) {
-#pragma unroll
-          for (int off = 8; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+          x += xor16<8>(x); x += xor16<4>(x); x += xor16<2>(x); x += xor16<1>(x);
           return x;
         };
         S out, l;
         if (g.loss_rows == 1) {
           S mx = valid ? v : S(-INFINITY);
-#pragma unroll
-          for (int off = 8; off > 0; off >>= 1) mx = max_s(mx, __shfl_xor(mx, off, 64));
+          mx = max_s(mx, xor16<8>(mx)); mx = max_s(mx, xor16<4>(mx));
+          mx = max_s(mx, xor16<2>(mx)); mx = max_s(mx, xor16<1>(mx));
           const S e = valid ? exp_s(v - mx) : S(0);
           const S se = sum16(e), sy = sum16(t);
           const S pr = e / se;
@@ -502,6 +522,18 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
 template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0>
 __global__ __launch_bounds__(NW * 64) void gemm_small_kernel(SmallArgsT<S> g) {
   gemm_small_body<S, AMODE, BMODE, NW, TS, ONESHOT>(g, (int)blockIdx.x, (long)blockIdx.z);
+}
+
+// The step's loss-head launch (z = H W2^T + b2, the loss head on each row, the hidden layer's cotangent as the fused tail)
+// where K <= 8 waves x 2 chunks of 16 and both operands are k-contiguous with 16-byte aligned rows: the one-shot body of two
+// chunks a wave.  The two-stage pipeline it replaces issued four chunks a wave for such a K -- two of them masked to zeros,
+// eight MFMAs on nothing and four more 16-byte loads a wave in front of the reduction barrier -- and carried the dword-load
+// path for operands that cannot take quads; here the launcher has checked that both can (a_vec, b_vec), so that path is
+// not in the instruction stream.  Same MFMAs on the same data in the same order: the same bits.
+__global__ __launch_bounds__(8 * 64) void gemm_small_head_kernel(SmallArgsT<float> g) {
+  g.a_vec = 1;
+  g.b_vec = 1;
+  gemm_small_body<float, 0, 1, 8, 16, 2>(g, (int)blockIdx.x, (long)blockIdx.z);
 }
 
 // Two independent latency-bound GEMMs in ONE launch (the weight gradients of two layers once both
@@ -1094,7 +1126,18 @@ static void launch_small_t(const GemmProblem& p, hipStream_t s) {
       return;
     }
   }
-  if (c.os == 8 && c.nw == 16) {
+  // the loss head of a short K on the lean one-shot instance (gemm_small_head_kernel); every other shape stays where it was
+  static const int head_lean = [] { const char* e = ab_getenv("TOPS_SMALL_HEAD_LEAN"); return e ? atoi(e) : 1; }();
+  bool lean = false;
+  if constexpr (!F64)
+    lean = head_lean && g.loss_rows && c.ts == 16 && c.nw == 8 && c.os == 0 && amode == 0 && bmode == 1 && g.a_vec && g.b_vec &&
+           p.K <= 8 * 2 * 16;
+  if (lean) {
+    if constexpr (!F64) {   // (plan_small's kper is already the slice of at most two chunks)
+      const dim3 grid((unsigned)(g.tiles_m * g.tiles_n), 1, (unsigned)p.batch), block(8 * 64);
+      launch_k(gemm_small_head_kernel, grid, block, 0, s, g);
+    }
+  } else if (c.os == 8 && c.nw == 16) {
     if constexpr (!F64) launch_nw<S, 16, 32, 8>(g, p, amode, bmode, s);
   } else if (c.os == 8) {
     launch_nw<S, 8, 16, 8>(g, p, amode, bmode, s);
@@ -1340,6 +1383,18 @@ bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStr
   g1.dbg = small_stamps(1);
   g2.dbg = small_stamps(3);
 #endif
+  // A very short K -- a step on a handful of rows (K = the batch < 128): both problems pick one wave per 16x16 tile and the
+  // two-stage body.  The same body, tile for tile, as their two separate launches, in one launch: the step stays at three
+  // launches down to 16 rows (tests/test_gpu_step_chains.py); the results are those of the separate launches, bit for bit.
+  if (c1.ts == 16 && c1.nw == 1 && c1.os == 0 && c1.amode == 1 && c1.bmode == 0 && !c1.f64_t32 &&
+      c2.ts == 16 && c2.nw == 1 && c2.os == 0 && c2.amode == 1 && c2.bmode == 0 && !c2.f64_t32 && !g1.loss_rows && !g2.loss_rows) {
+    const long t1 = (long)g1.tiles_m * g1.tiles_n, t2 = (long)g2.tiles_m * g2.tiles_n;
+    if (t1 + t2 > 65535) return false;
+    launch_k((gemm_small_pair_kernel<float, 1, 0, 1, 16, 0, 1, 0, 1, 16, 0>), dim3((unsigned)(t1 + t2)), dim3(64), 0, s, g1, g2, (int)t1);
+    TO_HIP(hipGetLastError());
+    count_launch();
+    return true;
+  }
   if (!(c1.ts == 32 && c1.nw == 16 && c1.os == 8 && c1.amode == 1 && c1.bmode == 0)) return false;
   if (!(c2.ts == 16 && c2.nw == 8 && c2.os == 8 && c2.amode == 1 && c2.bmode == 0)) return false;
   if (g1.loss_rows || g2.loss_rows) return false;

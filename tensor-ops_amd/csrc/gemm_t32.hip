@@ -48,6 +48,7 @@ struct T32Args {   // (pointers first, then 8-byte, then 4-byte members: a float
   float* rowsum;
   const float* rowsum_in;
   unsigned long long* dbg;   // development builds (TOPS_T32_STAMPS=1): ticks of the 100 MHz clock at six points of workgroups 0 and last
+                             // (thread 0: slots 0..15), and of every wave's "K loop done" / "partial written" (lane 0: slots 16..47)
   long a_sx, b_sx;   // element stride between consecutive rows of the operand's IMAGE: KC: between x; XC: between k
   long c_sm;
   int M, N, K;
@@ -103,8 +104,18 @@ __device__ __forceinline__ int t32_key(int x) { return (x >> 1) & 7; }
 // partial tiles are added in wave order 0 .. NW - 1.  Threads 0..255 run the epilogue (a float4 each).
 // EARLY: the first chunk's DMA leaves ahead of the epilogue's prefetch (which then sits between chunk 0 and chunk 1 in the
 // vmcnt order: the wait for chunk 0 covers it, nothing else changes).
-template <bool AKC, bool BKC, bool ARAG = false, bool WT = false, int NW = T32_NW, int NS = T32_NS, bool EARLY = false>
+// REGU (the eight-wave form with one chunk in flight): a wave whose run is an ODD number of 16-k units -- K = 784 is 49
+// units: 7 x 6 + 7 -- used to pay a whole DMA round trip for the half chunk at its end, serially behind its others, and
+// the tile waited for it at the barrier.  Here that last unit does not go through LDS: the wave loads it straight into the
+// MFMA fragment layout (KC: two 16-byte loads an operand; XC: eight dwords) AHEAD of chunk 0's DMA, and runs its eight
+// MFMAs -- the wave's first additions -- while chunk 0 is still in flight, where it would only have waited.  Every DMA
+// chunk that remains is a whole one.  vmcnt order: unit loads, chunk 0's PER DMA instructions, [wait: PER may stay
+// outstanding], the unit's MFMAs, the epilogue prefetch, and from there as without REGU (every later wait is for all).
+// The unit's loads are inline assembly like the DMA: the compiler does not count the DMA instructions, so a wait of its
+// own making would be vmcnt(0) and hold the MFMAs until chunk 0 is there.
+template <bool AKC, bool BKC, bool ARAG = false, bool WT = false, int NW = T32_NW, int NS = T32_NS, bool EARLY = false, bool REGU = false>
 __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, float* smem) {
+  static_assert(!REGU || (NW == 8 && NS == 1 && EARLY && !ARAG), "the register unit belongs to the eight-wave, one-stage, early-DMA form");
   constexpr int WAVE_F = NS * T32_STAGE;   // floats of LDS per wave
   static_assert(WAVE_F >= 1024 + 64, "a wave's stage memory holds its partial tile and its row sums");
   static_assert(!ARAG || !AKC, "the dword form is for a row-contiguous A");
@@ -114,6 +125,13 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
   const int l31 = lane & 31, half = lane >> 5;
   unsigned long long* const dbg = (g.dbg && tid == 0 && (bid == 0 || bid == (int)gridDim.x - 1)) ? g.dbg + (bid == 0 ? 0 : 8) : nullptr;
   auto stamp = [&](int i) { if (dbg) dbg[i] = __builtin_amdgcn_s_memrealtime(); };
+#ifdef TOPS_AB_KNOBS
+  // lane 0 of EVERY wave of the two stamped workgroups: 0 = its K loop done, 1 = its partial tile written (slots 16..47)
+  unsigned long long* const wdbg = (g.dbg && lane == 0 && wave < 8 && (bid == 0 || bid == (int)gridDim.x - 1)) ? g.dbg + 16 + (bid == 0 ? 0 : 16) + 2 * wave : nullptr;
+#define T32_WSTAMP(i) do { if (wdbg) wdbg[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#else
+#define T32_WSTAMP(i) do { } while (0)
+#endif
   int tile_m, tile_n;
   if (!t32_tile_of(g.tiles_m, g.tiles_n, g.gm, g.gn, bid, tile_m, tile_n)) return -1;
   stamp(0);
@@ -138,7 +156,15 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
   const int k0 = (int)((long)U * wave / NW) * 16;
   int k1 = (int)((long)U * (wave + 1) / NW) * 16;
   if (k1 > g.K) k1 = g.K;
-  const int nC = k1 > k0 ? (k1 - k0 + T32_BK - 1) / T32_BK : 0;
+  // kd: where the DMA chunks of the run end -- k1, or (REGU, an odd run) the start of the unit that goes through registers
+  int kd = k1;
+  bool ru = false;   // (uniform)
+  if constexpr (REGU) {
+    const int nU = (k1 - k0 + 15) / 16;
+    ru = (nU & 1) != 0;
+    if (ru) kd = k0 + (nU - 1) * 16;
+  }
+  const int nC = kd > k0 ? (kd - k0 + T32_BK - 1) / T32_BK : 0;
 
   typedef __attribute__((address_space(3))) void* lptr_t;
   float* wsm = smem + wave * WAVE_F;
@@ -186,7 +212,7 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
     const unsigned st = lds_w + (unsigned)(seq % NS) * (T32_STAGE * 4);
     const char* ba = sa + (long)c * step_a;
     const char* bb = sb + (long)c * step_b;
-    const bool full = kc + T32_BK <= k1;
+    const bool full = kc + T32_BK <= kd;
     if (full && interior) {
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
@@ -207,7 +233,7 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int kl = 2 * e + half;
-          const bool ok = kc + kl < k1 && m0 + l31 < M_l;
+          const bool ok = kc + kl < kd && m0 + l31 < M_l;
           const char* src = ok ? ba + ((long)kl * a_sx_l + m0 + l31) * 4 : zero;
           asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(st + e * 256) : "memory");
           asm volatile("global_load_lds_dword %0, off offset:0" ::"v"(src) : "memory");
@@ -215,7 +241,7 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
       } else {
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-          const bool ok = AKC ? (kc + 4 * (ls ^ t32_key(8 * p + lr)) < k1) : (kc + 8 * p + lr < k1 && xa_ok);
+          const bool ok = AKC ? (kc + 4 * (ls ^ t32_key(8 * p + lr)) < kd) : (kc + 8 * p + lr < kd && xa_ok);
           const char* src = ok ? ba + oa[p] : zero;
           asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(st + p * 1024) : "memory");
           T32_DMA_V(src);
@@ -223,7 +249,7 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
       }
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
-        const bool ok = BKC ? (kc + 4 * (ls ^ t32_key(8 * p + lr)) < k1) : (kc + 8 * p + lr < k1 && xb_ok);
+        const bool ok = BKC ? (kc + 4 * (ls ^ t32_key(8 * p + lr)) < kd) : (kc + 8 * p + lr < kd && xb_ok);
         const char* src = ok ? bb + ob[p] : zero;
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(st + 4096 + p * 1024) : "memory");
         T32_DMA_V(src);
@@ -241,9 +267,83 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
 
   const int PD = g.pd < NS ? g.pd : NS;
   const int pro = nC < PD ? nC : PD;
+  // REGU: the unit [kd, k1) in fragment layout -- MFMA step 4 i + j takes k = kd + 4 (2 i + half) + j, i = 0, 1 -- as quads
+  // (k-contiguous operand) or dwords (row-contiguous).  A lane without a valid source (k beyond the run, which ends at K
+  // or before; a row-contiguous x beyond the extent) loads the zeros, never a stray value; a k-contiguous row beyond the
+  // extent is clamped to the last one, as in the DMA path (it only reaches rows / columns that are not stored).
+  f32x4 ua4[2], ub4[2];
+  float ua1[8], ub1[8];
+  if constexpr (REGU) {
+    if (ru) {
+      const float* zero = g_t32_zero;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int kq = kd + 4 * (2 * i + half);
+        if constexpr (AKC) {
+          long x = m0 + l31;
+          if (x >= g.M) x = g.M - 1;
+          const float* src = kq < k1 ? g.A + x * g.a_sx + kq : zero;
+          asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(ua4[i]) : "v"(src) : "memory");
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float* src = (kq + j < k1 && m0 + l31 < g.M) ? g.A + (long)(kq + j) * g.a_sx + m0 + l31 : zero;
+            asm volatile("global_load_dword %0, %1, off" : "=&v"(ua1[4 * i + j]) : "v"(src) : "memory");
+          }
+        }
+        if constexpr (BKC) {
+          long x = n0 + l31;
+          if (x >= g.N) x = g.N - 1;
+          const float* src = kq < k1 ? g.B + x * g.b_sx + kq : zero;
+          asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(ub4[i]) : "v"(src) : "memory");
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float* src = (kq + j < k1 && n0 + l31 < g.N) ? g.B + (long)(kq + j) * g.b_sx + n0 + l31 : zero;
+            asm volatile("global_load_dword %0, %1, off" : "=&v"(ub1[4 * i + j]) : "v"(src) : "memory");
+          }
+        }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
   if constexpr (EARLY) {
     if (pro > 0) issue(0);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (REGU) {
+      if (ru) {
+        // the unit has landed when at most chunk 0's DMA instructions are outstanding; the values are tied to the wait so
+        // that nothing reads them ahead of it
+        if (pro > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        float fu[8], gu[8];
+        if constexpr (AKC) {
+          asm volatile("" : "+v"(ua4[0]), "+v"(ua4[1]) :: "memory");
+#pragma unroll
+          for (int i = 0; i < 2; ++i) { fu[4 * i] = ua4[i].x; fu[4 * i + 1] = ua4[i].y; fu[4 * i + 2] = ua4[i].z; fu[4 * i + 3] = ua4[i].w; }
+        } else {
+          asm volatile("" : "+v"(ua1[0]), "+v"(ua1[1]), "+v"(ua1[2]), "+v"(ua1[3]), "+v"(ua1[4]), "+v"(ua1[5]), "+v"(ua1[6]), "+v"(ua1[7]) :: "memory");
+#pragma unroll
+          for (int q = 0; q < 8; ++q) fu[q] = ua1[q];
+        }
+        if constexpr (BKC) {
+          asm volatile("" : "+v"(ub4[0]), "+v"(ub4[1]) :: "memory");
+#pragma unroll
+          for (int i = 0; i < 2; ++i) { gu[4 * i] = ub4[i].x; gu[4 * i + 1] = ub4[i].y; gu[4 * i + 2] = ub4[i].z; gu[4 * i + 3] = ub4[i].w; }
+        } else {
+          asm volatile("" : "+v"(ub1[0]), "+v"(ub1[1]), "+v"(ub1[2]), "+v"(ub1[3]), "+v"(ub1[4]), "+v"(ub1[5]), "+v"(ub1[6]), "+v"(ub1[7]) :: "memory");
+#pragma unroll
+          for (int q = 0; q < 8; ++q) gu[q] = ub1[q];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fu[q], gu[q], acc, 0, 0, 0);
+          if (want_rs) asum += fu[q];
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
     prefetch_epilogue();
     __builtin_amdgcn_sched_barrier(0);
     for (int c = 1; c < pro; ++c) issue(c);
@@ -262,7 +362,7 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
   // a half chunk (<= 16 k left of the wave's run) needs the first eight MFMA steps only
-  auto steps_of = [&](int c) { return (k1 - (k0 + c * T32_BK)) > 16 ? 4 : 2; };
+  auto steps_of = [&](int c) { return (kd - (k0 + c * T32_BK)) > 16 ? 4 : 2; };
   auto read_frags = [&](int c, float (&fa)[16], float (&fb)[16]) {
     const float* sp = wsm + (c % NS) * T32_STAGE;
     const int nI = steps_of(c);
@@ -319,12 +419,14 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   stamp(3);
+  T32_WSTAMP(0);
 
   // ---- the four partial tiles meet in LDS (each wave in its own stage memory: nothing of another wave is overwritten) ----
   // accumulator register r of lane (l31, half): row (r & 3) + 8 (r >> 2) + 4 half, column l31
 #pragma unroll
   for (int r = 0; r < 16; ++r) wsm[((r & 3) + 8 * (r >> 2) + 4 * half) * 32 + l31] = acc[r];
   if (want_rs) wsm[1024 + lane] = asum;
+  T32_WSTAMP(1);
   __syncthreads();
   stamp(4);
   f32x4 s = {0.f, 0.f, 0.f, 0.f};
@@ -367,6 +469,7 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
     }
   }
   stamp(5);
+#undef T32_WSTAMP
   return tile_m;
 }
 
@@ -525,10 +628,10 @@ __global__ __launch_bounds__(256) void gemm_t32_head_kernel(T32Args g, T32HeadAr
   }
 }
 
-template <bool AKC, bool BKC, int NW = T32_NW, int NS = T32_NS, bool EARLY = false>
+template <bool AKC, bool BKC, int NW = T32_NW, int NS = T32_NS, bool EARLY = false, bool REGU = false>
 __global__ __launch_bounds__(NW * 64) void gemm_t32_kernel(T32Args g) {
   extern __shared__ __attribute__((aligned(1024))) float t32_smem[];
-  gemm_t32_body<AKC, BKC, false, false, NW, NS, EARLY>(g, (int)blockIdx.x, t32_smem);
+  gemm_t32_body<AKC, BKC, false, false, NW, NS, EARLY, REGU>(g, (int)blockIdx.x, t32_smem);
 }
 
 // Two weight-gradient contractions (dZ^T . A: both operands row-contiguous, K = the batch) in ONE launch: the first
@@ -590,8 +693,8 @@ static bool t32_fill(const GemmProblem& p, T32Args& g, bool& akc, bool& bkc, boo
   g.pd = pd;
   static unsigned long long* dbg = [] {
     unsigned long long* p = nullptr;
-    if (ab_getenv("TOPS_T32_STAMPS") && hipHostMalloc(reinterpret_cast<void**>(&p), 16 * sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
-      for (int i = 0; i < 16; ++i) p[i] = 0;
+    if (ab_getenv("TOPS_T32_STAMPS") && hipHostMalloc(reinterpret_cast<void**>(&p), 48 * sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
+      for (int i = 0; i < 48; ++i) p[i] = 0;
       static unsigned long long* keep = p;
       atexit([] {
         if (keep[15]) {   // the joined launch: slots 8..15 belong to the head of row block 0
@@ -606,6 +709,12 @@ static bool t32_fill(const GemmProblem& p, T32Args& g, bool& akc, bool& bkc, boo
                                "partials met %.2f, done %.2f; began %.2f us after workgroup 0\n", w ? "last" : "first",
                        (k[1] - k[0]) * 0.01, (k[2] - k[0]) * 0.01, (k[3] - k[0]) * 0.01, (k[4] - k[0]) * 0.01, (k[5] - k[0]) * 0.01,
                        ((double)k[0] - (double)keep[0]) * 0.01);
+          // every wave of that workgroup (the last one to write its partial closes the barrier)
+          const unsigned long long* wv = keep + 16 + 16 * w;
+          std::fprintf(stderr, "[t32]   per wave, K loop done / partial written:");
+          for (int q = 0; q < 8; ++q)
+            if (wv[2 * q]) std::fprintf(stderr, "  w%d %.2f / %.2f", q, ((double)wv[2 * q] - (double)k[0]) * 0.01, ((double)wv[2 * q + 1] - (double)k[0]) * 0.01);
+          std::fprintf(stderr, "\n");
         }
       });
     }
@@ -645,23 +754,24 @@ static void t32_attr(const void* k) { TO_HIP(hipFuncSetAttribute(k, hipFuncAttri
 constexpr int T32_W8_DEFAULT = 1;   // 1: route one-round grids to eight waves
 constexpr int T32_W8_NS = 1;
 constexpr bool T32_EARLY = true;    // the first chunk's DMA ahead of the epilogue prefetch
+constexpr bool T32_REGU = true;     // the eight-wave form: an odd run's last 16-k unit through registers (gemm_t32_body, REGU)
 
-template <int NW, int NS, bool EARLY>
+template <int NW, int NS, bool EARLY, bool REGU = false>
 static void t32_launch_nw(const T32Args& g, bool akc, bool bkc, hipStream_t s) {
   constexpr size_t lds = (size_t)NW * NS * T32_STAGE * 4;
   static bool attr = false;
   if (!attr) {
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<true, true, NW, NS, EARLY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<true, false, NW, NS, EARLY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<false, true, NW, NS, EARLY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<false, false, NW, NS, EARLY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<true, true, NW, NS, EARLY, REGU>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<true, false, NW, NS, EARLY, REGU>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<false, true, NW, NS, EARLY, REGU>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_t32_kernel<false, false, NW, NS, EARLY, REGU>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
   const dim3 grid((unsigned)t32_grid(g)), block(NW * 64);
-  if (akc && bkc) launch_k((gemm_t32_kernel<true, true, NW, NS, EARLY>), grid, block, lds, s, g);
-  else if (akc) launch_k((gemm_t32_kernel<true, false, NW, NS, EARLY>), grid, block, lds, s, g);
-  else if (bkc) launch_k((gemm_t32_kernel<false, true, NW, NS, EARLY>), grid, block, lds, s, g);
-  else launch_k((gemm_t32_kernel<false, false, NW, NS, EARLY>), grid, block, lds, s, g);
+  if (akc && bkc) launch_k((gemm_t32_kernel<true, true, NW, NS, EARLY, REGU>), grid, block, lds, s, g);
+  else if (akc) launch_k((gemm_t32_kernel<true, false, NW, NS, EARLY, REGU>), grid, block, lds, s, g);
+  else if (bkc) launch_k((gemm_t32_kernel<false, true, NW, NS, EARLY, REGU>), grid, block, lds, s, g);
+  else launch_k((gemm_t32_kernel<false, false, NW, NS, EARLY, REGU>), grid, block, lds, s, g);
 }
 
 void launch_gemm_t32(const GemmProblem& p, hipStream_t s) {
@@ -674,16 +784,20 @@ void launch_gemm_t32(const GemmProblem& p, hipStream_t s) {
 #ifdef TOPS_AB_KNOBS
   static const int w8_ns = [] { const char* e = ab_getenv("TOPS_T32_W8_NS"); return e ? atoi(e) : T32_W8_NS; }();
   static const int early = [] { const char* e = ab_getenv("TOPS_T32_EARLY"); return e ? atoi(e) : (int)T32_EARLY; }();
+  static const int regu = [] { const char* e = ab_getenv("TOPS_T32_REGU"); return e ? atoi(e) : (int)T32_REGU; }();   // (one stage, early DMA only)
   switch ((w8 ? (w8_ns == 1 ? 2 : 4) : 0) + (early ? 1 : 0)) {
     case 0: t32_launch_nw<T32_NW, T32_NS, false>(g, akc, bkc, s); break;
     case 1: t32_launch_nw<T32_NW, T32_NS, true>(g, akc, bkc, s); break;
     case 2: t32_launch_nw<8, 1, false>(g, akc, bkc, s); break;
-    case 3: t32_launch_nw<8, 1, true>(g, akc, bkc, s); break;
+    case 3:
+      if (regu) t32_launch_nw<8, 1, true, true>(g, akc, bkc, s);
+      else t32_launch_nw<8, 1, true, false>(g, akc, bkc, s);
+      break;
     case 4: t32_launch_nw<8, 2, false>(g, akc, bkc, s); break;
     default: t32_launch_nw<8, 2, true>(g, akc, bkc, s); break;
   }
 #else
-  if (w8) t32_launch_nw<8, T32_W8_NS, T32_EARLY>(g, akc, bkc, s);
+  if (w8) t32_launch_nw<8, T32_W8_NS, T32_EARLY, T32_REGU>(g, akc, bkc, s);
   else t32_launch_nw<T32_NW, T32_NS, T32_EARLY>(g, akc, bkc, s);
 #endif
   TO_HIP(hipGetLastError());

@@ -320,9 +320,12 @@ to_status to_p2p_shutdown(void);
  * summed over the hidden batch of x/y, written into the caller's gW[l] / gb[l]
  * (e.g. views of the flat all-reduce buffer).  Mathematically the same as gradTOp on
  * the generic path; the per-op launches are collapsed into GEMMs with fused epilogues.
- * hidden_act: TO_ACT_LOGISTIC; (out_act, loss): (TO_ACT_SOFTMAX, TO_LOSS_CROSS_ENTROPY)
- * or (TO_ACT_LOGISTIC, TO_LOSS_SQUARED_ERROR).  losses_or_null: per-sample loss [B]. */
-enum { TO_ACT_LOGISTIC = 0, TO_ACT_SOFTMAX = 2 };
+ * hidden_act: TO_ACT_LOGISTIC or TO_ACT_TANH (`actMap tanh`: h = tanh(z), backward d * (1 - h^2) on the stored h), one for
+ * every non-final layer; (out_act, loss): (TO_ACT_SOFTMAX, TO_LOSS_CROSS_ENTROPY) or (TO_ACT_LOGISTIC,
+ * TO_LOSS_SQUARED_ERROR); TO_ACT_TANH is not an output activation (TO_ERR_UNSUPPORTED, nothing written).  A tanh step
+ * takes the launches of the logistic step of the same shape.  losses_or_null: per-sample loss [B].
+ * This holds for hidden_act of every to_fflayer_stack_* and to_rnn_stack_* entry below. */
+enum { TO_ACT_LOGISTIC = 0, TO_ACT_SOFTMAX = 2, TO_ACT_TANH = 3 };
 enum { TO_LOSS_SQUARED_ERROR = 0, TO_LOSS_CROSS_ENTROPY = 1 };
 to_status to_fflayer_stack_grad(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act,
                                 int out_act, int loss, to_tensor x, to_tensor y, const to_tensor* gw,
@@ -339,7 +342,7 @@ to_status to_fflayer_stack_sgd(int n_layers, const to_tensor* w, const to_tensor
  * app/Dots.hs:74-80) -- of the same stacks over rows idx[0..n_idx) (null: rows 0..n_idx-1) of the resident batched X / Y,
  * parameters updated in place, as ONE persistent launch: the workgroups keep the parameters in LDS between samples,
  * layer 1 split by rows and layer 2 by columns over up to 32 workgroups of one XCD, one exchange per sample
- * (csrc/online_sgd.hip).  fp32 or fp64, 2..6 layers, input <= 2048, head <= 64 outputs, everything a workgroup holds within
+ * (csrc/online_sgd.hip).  hidden_act TO_ACT_LOGISTIC or TO_ACT_TANH; fp32 or fp64, 2..6 layers, input <= 2048, head <= 64 outputs, everything a workgroup holds within
  * 160 KiB of LDS: TO_ERR_UNSUPPORTED otherwise, with the parameters untouched (the generic path -- one recorded and
  * fused step per sample -- always works).  Blocks until the stream of samples is done. */
 to_status to_fflayer_stack_online_sgd(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
@@ -349,7 +352,8 @@ to_status to_fflayer_stack_online_sgd(int n_layers, const to_tensor* w, const to
 /* The same, found by the library itself.  `g` is a captured ONE-SAMPLE training step (whatever the host's DSL recorded
  * in a scope: gradTOp of its network, the update, to_copy_into of the new parameters), x_buf / y_buf the buffers that
  * step reads its sample from.  If the launches the planner made of that step are exactly the trainNetwork step of an
- * ffLayer stack -- GEMVs with bias + logistic, a recognised loss head, the cotangents back through the layers, every
+ * ffLayer stack -- GEMVs with bias + logistic (a captured TANH step is not recognised: *handled = 0; call
+ * to_fflayer_stack_online_sgd with TO_ACT_TANH instead), a recognised loss head, the cotangents back through the layers, every
  * layer's outer-product update in place -- and the stack fits the persistent kernel, the samples idx[0..n_idx) of X / Y
  * are trained in one launch and *handled = 1; otherwise *handled = 0 and nothing has been done (replay `g` per sample).
  * The host says nothing about what its network is made of.  TOPS_ONLINE_KERNEL=0 disables it. */
@@ -360,7 +364,7 @@ to_status to_graph_online_sgd(to_graph g, to_tensor x_buf, to_tensor y_buf, to_t
 to_status to_online_sgd_stats(int64_t* runs, int64_t* samples);
 
 /* `runNetwork` (FeedForward.hs:123-129, 216-235) of the same stacks over the hidden batch of x -- a_l = act_l (W_l a_{l-1}
- * + b_l), hidden_act TO_ACT_LOGISTIC, out_act TO_ACT_SOFTMAX or TO_ACT_LOGISTIC -- with the validation folds of
+ * + b_l), hidden_act TO_ACT_LOGISTIC or TO_ACT_TANH, out_act TO_ACT_SOFTMAX or TO_ACT_LOGISTIC -- with the validation folds of
  * app/MNIST.hs:366-389 in the same call.  fp32 or fp64, any batch (an unbatched x is one row), any layer widths: never
  * TO_ERR_UNSUPPORTED for a valid stack.  What it writes, each optional, at least one asked for (else TO_ERR_ARG):
  *   out_or_null        caller-allocated [B; n_L] of x's dtype (contiguous): the network's output rows;
@@ -382,8 +386,10 @@ to_status to_fflayer_stack_infer(int n_layers, const to_tensor* w, const to_tens
  * ffLayer entries.  Layer l is
  *   state_act[l] == TO_ACT_LOGISTIC   `fullyConnected` (Recurrent.hs:91-119): z = W x + W' s + b, new state logistic(z),
  *                                     output z through the layer's `*~ act`; s[l] [n_l], ws[l] = W' [n_l, n_l];
+ *   state_act[l] == TO_ACT_TANH       the same with the new state tanh(z); the layers of one stack mix freely;
  *   state_act[l] == TO_RNN_STATELESS  an ffLayer (Recurrent.hs:126-138); s[l] and ws[l] (and gs[l], gws[l]) null;
- * w[l] = W [n_l, n_{l-1}], b[l] [n_l].  hidden_act TO_ACT_LOGISTIC; run: out_act TO_ACT_SOFTMAX or TO_ACT_LOGISTIC; grad /
+ * w[l] = W [n_l, n_{l-1}], b[l] [n_l].  hidden_act (the `*~ act` behind every non-final layer of either kind, whatever its
+ * state_act) TO_ACT_LOGISTIC or TO_ACT_TANH; run: out_act TO_ACT_SOFTMAX or TO_ACT_LOGISTIC; grad /
  * sgd: (out_act, loss) (TO_ACT_SOFTMAX, TO_LOSS_CROSS_ENTROPY) or (TO_ACT_LOGISTIC, TO_LOSS_SQUARED_ERROR); anything else
  * is TO_ERR_UNSUPPORTED, nothing written.  The reference's order: `Prod t ss` lists later layers' states first (`~*~`:
  * ss2 ++ ss1) and each fullyConnected carries its parameters as (W', W, b); here layer l's state is s[l] and its parameters
@@ -406,7 +412,8 @@ to_status to_fflayer_stack_infer(int n_layers, const to_tensor* w, const to_tens
  * (csrc/rnn_seq.hip; its range: n_l <= 1024, fp32 and fp64, any B and T -- the launch count of a call does not depend on T
  * there) or per step (one GEMM with the addend + one elementwise launch per step and direction).  to_set_rnn_persistent:
  * 0 per step; 1 automatic (default): persistent where the kernel holds W' in LDS (fp32 n_l <= 201, fp64 n_l <= 142), the
- * threshold measured in DESIGN.md section 3.3, per step otherwise; 2 persistent wherever in range.  Process-wide.
+ * threshold measured in DESIGN.md section 3.3 -- on logistic states; a tanh state takes the same routes by the same
+ * threshold, which has NOT been measured for tanh --, per step otherwise; 2 persistent wherever in range.  Process-wide.
  * to_rnn_stats counts the calls with a stateful layer: all of its recurrences persistent, or at least one per step. */
 enum { TO_RNN_STATELESS = -1 };
 to_status to_rnn_stack_run(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
@@ -426,7 +433,7 @@ to_status to_rnn_stats(int64_t* persistent_runs, int64_t* stepwise_runs);
  * parameters fixed (app/MNIST.hs:357-365 runs 5000 such steps in a row), for every row of the hidden batch, in ONE call:
  *   x_0 = x[r];   g_k = d/dx loss(net(x_k), y[r]);   x_{k+1} = x_k - rate * g_k,   k = 0 .. iters-1
  *   out[r] = x_iters     gx[r] = g_{iters-1}     losses[r, k] = loss(net(x_k), y[r])   (the loss BEFORE step k+1)
- * hidden_act TO_ACT_LOGISTIC; (out_act, loss) (TO_ACT_SOFTMAX, TO_LOSS_CROSS_ENTROPY) or (TO_ACT_LOGISTIC,
+ * hidden_act TO_ACT_LOGISTIC or TO_ACT_TANH; (out_act, loss) (TO_ACT_SOFTMAX, TO_LOSS_CROSS_ENTROPY) or (TO_ACT_LOGISTIC,
  * TO_LOSS_SQUARED_ERROR), anything else TO_ERR_UNSUPPORTED with nothing written; the losses are to_fflayer_stack_grad's.
  * Targets are arbitrary vectors, not only one-hot.  No clamping of x: the reference has none.
  *   x               [B; i0] or unbatched [i0] (one row);
@@ -439,7 +446,7 @@ to_status to_rnn_stats(int64_t* persistent_runs, int64_t* stepwise_runs);
  * or more: never TO_ERR_UNSUPPORTED for a valid stack and pair.  Parameters and y are only read; pending operands are
  * produced first; refused during graph capture (TO_ERR_STATE); blocks before it returns; keeps no handle.  A refused or
  * failed call leaves out, gx and losses untouched.
- * Routes.  Per iteration (A): one GEMM a layer forward (bias + logistic in its epilogue), the loss head, the cotangents
+ * Routes.  Per iteration (A): one GEMM a layer forward (bias + activation in its epilogue), the loss head, the cotangents
  * back, and the last contraction with the step in its epilogue; takes every stack, launches grow with iters.  Persistent
  * (B, csrc/induce_seq.hip): all iterations of all rows in ONE launch, the parameters in LDS, layer 1 split by columns over
  * G <= 32 workgroups of one XCD that exchange o1 partial sums an iteration (G = 1: no exchange).  Its range: 1..6 layers,
@@ -450,7 +457,8 @@ to_status to_rnn_stats(int64_t* persistent_runs, int64_t* stepwise_runs);
  * place in the batch, and iters = a followed by iters = b on the result equals iters = a + b bit for bit.
  * to_set_induce_persistent: 0 route A; 1 automatic (default): route B where it is known to be ahead -- until the scan of
  * DESIGN.md section 3.3 has been run on a device that is a plan of one workgroup a row (G = 1) with B <= 256, route A
- * otherwise; 2 route B wherever its plan fits, A otherwise.  Process-wide.  to_induce_stats counts calls (iters >= 1) by
+ * otherwise; 2 route B wherever its plan fits, A otherwise (the rule does not look at hidden_act and has not been measured
+ * for tanh).  Process-wide.  to_induce_stats counts calls (iters >= 1) by
  * the route that ran. */
 to_status to_fflayer_stack_induce(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
                                   int loss, to_tensor x, to_tensor y, double rate, int64_t iters, to_tensor out,

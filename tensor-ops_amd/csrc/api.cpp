@@ -2178,12 +2178,13 @@ struct LossHead {  // loss gradient fused into the last layer's GEMM epilogue wh
   const void* tail_h = nullptr;
   void* tail_out = nullptr;
   int tail_n = 0;
+  int tail_kind = 0;  // GemmProblem::tail_kind
   bool tail_done = false;
 };
 static bool fused_gemm(int dtype, const void* A, int64_t a_sm, int64_t a_sk, const void* B, int64_t b_sk,
                        int64_t b_sn, void* C, int64_t M, int64_t N, int64_t K, const void* bias,
                        int act, const void* dact, void* rowsum = nullptr, hipStream_t stream = nullptr,
-                       LossHead* head = nullptr) {
+                       LossHead* head = nullptr, int dact_kind = 0) {
   GemmProblem p{};
   p.dtype = dtype;
   p.A = A; p.B = B; p.C = C;
@@ -2191,7 +2192,7 @@ static bool fused_gemm(int dtype, const void* A, int64_t a_sm, int64_t a_sk, con
   p.a_sm = a_sm; p.a_sk = a_sk; p.b_sk = b_sk; p.b_sn = b_sn; p.c_sm = N;
   p.batch = 1;
   p.alpha = 1.0; p.beta = 0.0;
-  p.bias = bias; p.act = act; p.dact = dact;
+  p.bias = bias; p.act = act; p.dact = dact; p.dact_kind = dact_kind;
   hipStream_t st = stream ? stream : S();
   // latency-bound shapes (incl. the tiny ones of a one-sample step) run on the small-GEMM kernel: it carries
   // every fused epilogue for both element types (the tiled fp64 kernel has none)
@@ -2202,6 +2203,7 @@ static bool fused_gemm(int dtype, const void* A, int64_t a_sm, int64_t a_sk, con
       p.loss_rows = head->kind; p.target = head->target; p.loss_out = head->loss_out;
       if (head->tail_out && gemm_small_fuses_tail(p, head->tail_n)) {
         p.tail_w = head->tail_w; p.tail_h = head->tail_h; p.tail_out = head->tail_out; p.tail_n = head->tail_n;
+        p.tail_kind = head->tail_kind;
         head->tail_done = true;
       }
       head->done = true;
@@ -2215,9 +2217,13 @@ static bool fused_gemm(int dtype, const void* A, int64_t a_sm, int64_t a_sk, con
   return false;
 }
 
-// The checks the ffLayer stack entry points share.  Hidden layers: logistic only.
-static void stack_hidden_act_check(int hidden_act) {
-  TO_CHECK(hidden_act == TO_ACT_LOGISTIC, TO_ERR_UNSUPPORTED, "fused path: hidden activation must be logistic");
+// The checks the ffLayer stack entry points share.  Hidden layers: logistic or tanh.  Returns the activation numbered as
+// the kernels number it (ACT_KIND_*: GemmProblem::dact_kind / tail_kind, the persistent kernels' template parameter;
+// GemmProblem::act is this + 1).
+static int stack_hidden_act_check(int hidden_act) {
+  TO_CHECK(hidden_act == TO_ACT_LOGISTIC || hidden_act == TO_ACT_TANH, TO_ERR_UNSUPPORTED,
+           "fused path: hidden activation must be logistic or tanh");
+  return hidden_act == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC;
 }
 
 // Every layer's W [n_l, n_{l-1}] and b [n_l]: unbatched, contiguous, of the data's dtype, chained from `fan_in`; gradient
@@ -2260,7 +2266,7 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
     before_write(gb[l]);
     if (sgd) { w[l]->id = fresh_id(); b[l]->id = fresh_id(); }
   }
-  stack_hidden_act_check(hidden_act);
+  const int hk = stack_hidden_act_check(hidden_act);
   const bool sm_ce = out_act == TO_ACT_SOFTMAX && loss == TO_LOSS_CROSS_ENTROPY;
   const bool lg_se = out_act == TO_ACT_LOGISTIC && loss == TO_LOSS_SQUARED_ERROR;
   TO_CHECK(sm_ce || lg_se, TO_ERR_UNSUPPORTED,
@@ -2293,7 +2299,7 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
   head.kind = sm_ce ? 1 : 2;
   head.target = y->ptr;
   head.loss_out = losses ? losses->ptr : nullptr;
-  // forward: a_l = logistic(a_{l-1} W_l^T + b_l) for hidden layers, z_L for the last
+  // forward: a_l = act(a_{l-1} W_l^T + b_l) for hidden layers (act: hidden_act), z_L for the last
   std::vector<Holder> act(n_layers);  // act[l]: [B; n_l]; the last holds z_L, then is reused as dz_L
   const void* prev = x->ptr;
   int64_t prev_n = x->dims[0];
@@ -2304,15 +2310,16 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
     // (last layer: the loss head runs in the same launch when the row fits one 16-wide tile)
     const bool last = l + 1 == n_layers;
     if (last && n_layers >= 2 && fuse_tail) {
-      // the loss-head launch also produces dz_{L-1} = (dz_L . W_L) * h (1 - h) for its rows
+      // the loss-head launch also produces dz_{L-1} = (dz_L . W_L) * act'(h) for its rows
       tail.t = new_tensor(1, &prev_n, B, dt);
       head.tail_w = w[l]->ptr;
       head.tail_h = act[l - 1].t->ptr;
       head.tail_out = tail.t->ptr;
       head.tail_n = (int)prev_n;
+      head.tail_kind = hk;
     }
     fused_gemm(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, act[l].t->ptr, B, n, prev_n, b[l]->ptr,
-               last ? 0 : 1, nullptr, nullptr, nullptr, last ? &head : nullptr);
+               last ? 0 : hk + 1, nullptr, nullptr, nullptr, last ? &head : nullptr);
     prev = act[l].t->ptr;
     prev_n = n;
   }
@@ -2346,7 +2353,7 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
     return p;
   };
   // backward, phase 1: every dz_l (the propagation reads W_l, which phase 2 may overwrite in place)
-  // dz_{l-1}[B,m] = (dz_l[B,n] . W_l[n,m]) * h (1 - h), h = act[l-1]
+  // dz_{l-1}[B,m] = (dz_l[B,n] . W_l[n,m]) * act'(h), h = act[l-1]  (h (1 - h), or 1 - h h for tanh)
   std::vector<Holder> dz(n_layers);
   dz[n_layers - 1].t = cur.take();
   for (int l = n_layers - 1; l > 0; --l) {
@@ -2355,7 +2362,8 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
       dz[l - 1].t = tail.take();  // came out of the loss-head launch
     } else {
       dz[l - 1].t = new_tensor(1, &m, B, dt);
-      fused_gemm(dt, dz[l].t->ptr, n, 1, w[l]->ptr, m, 1, dz[l - 1].t->ptr, B, m, n, nullptr, 0, act[l - 1].t->ptr);
+      fused_gemm(dt, dz[l].t->ptr, n, 1, w[l]->ptr, m, 1, dz[l - 1].t->ptr, B, m, n, nullptr, 0, act[l - 1].t->ptr, nullptr,
+                 nullptr, nullptr, hk);
     }
   }
   // phase 2: the weight gradients, independent of each other.  The two last ones go out as ONE launch when
@@ -2425,7 +2433,8 @@ static void online_sgd_impl(int n_layers, const to_tensor* w, const to_tensor* b
   no_capture("to_fflayer_stack_online_sgd");
   NONNULL(w); NONNULL(b); NONNULL(X); NONNULL(Y);
   TO_CHECK(n_layers >= 2 && n_layers <= 6, TO_ERR_UNSUPPORTED, "online SGD kernel: 2..6 layers");
-  TO_CHECK(hidden_act == TO_ACT_LOGISTIC, TO_ERR_UNSUPPORTED, "online SGD kernel: hidden activation must be logistic");
+  TO_CHECK(hidden_act == TO_ACT_LOGISTIC || hidden_act == TO_ACT_TANH, TO_ERR_UNSUPPORTED,
+           "online SGD kernel: hidden activation must be logistic or tanh");
   const bool sm_ce = out_act == TO_ACT_SOFTMAX && loss == TO_LOSS_CROSS_ENTROPY;
   const bool lg_se = out_act == TO_ACT_LOGISTIC && loss == TO_LOSS_SQUARED_ERROR;
   TO_CHECK(sm_ce || lg_se, TO_ERR_UNSUPPORTED, "online SGD kernel: (softmax, crossEntropy) or (logistic, squaredError) only");
@@ -2476,7 +2485,8 @@ static void online_sgd_impl(int n_layers, const to_tensor* w, const to_tensor* b
     idx_dev = static_cast<const long long*>(order.t->ptr);
   }
   online_sgd_reset_status();
-  launch_online_sgd(dt, n_layers, dims, wp, bp, X->ptr, Y->ptr, idx_dev, n_idx, rate, sm_ce ? 1 : 2, S());
+  launch_online_sgd(dt, n_layers, dims, wp, bp, X->ptr, Y->ptr, idx_dev, n_idx, rate, sm_ce ? 1 : 2,
+                    hidden_act == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC, S());
   TO_HIP(hipStreamSynchronize(S()));  // the order buffer goes back to the pool; the watchdog's verdict is read
   TO_CHECK(online_sgd_status() == 0, TO_ERR_HIP,
            "online SGD kernel: a workgroup barrier timed out at sample " + std::to_string(online_sgd_status() - 1) +
@@ -2492,7 +2502,7 @@ to_status to_fflayer_stack_online_sgd(int n_layers, const to_tensor* w, const to
 }
 
 // `runNetwork` (FeedForward.hs:123-129) of an ffLayer stack over a batch and the folds of `validate` / `confusion`
-// (app/MNIST.hs:366-389).  Hidden layers: one GEMM each, bias + logistic in its epilogue where the kernel carries one,
+// (app/MNIST.hs:366-389).  Hidden layers: one GEMM each, bias + activation (logistic / tanh) in its epilogue where the kernel carries one,
 // else a plain GEMM and one elementwise launch.  The head (infer_head.hip): n_L <= 32 the last layer's contraction and
 // everything after it in one launch; wider, the last GEMM into scratch (or `out` itself) and one row launch.
 static void fflayer_stack_infer_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
@@ -2503,7 +2513,7 @@ static void fflayer_stack_infer_impl(int n_layers, const to_tensor* w, const to_
   TO_CHECK(n_layers >= 1, TO_ERR_ARG, "need at least one layer");
   TO_CHECK(out || classes || confusion, TO_ERR_ARG, "infer: no output asked for (out, classes or confusion)");
   TO_CHECK(!confusion || y, TO_ERR_ARG, "infer: the confusion matrix needs the targets y");
-  stack_hidden_act_check(hidden_act);
+  const int hk = stack_hidden_act_check(hidden_act);
   TO_CHECK(out_act == TO_ACT_SOFTMAX || out_act == TO_ACT_LOGISTIC, TO_ERR_UNSUPPORTED,
            "infer: the output activation must be softmax or logistic");
   TO_CHECK(x->rank == 1 && x->dims[0] >= 1, TO_ERR_SHAPE, "infer: x must be a (batched) vector, got " + shape_str(x));
@@ -2555,7 +2565,7 @@ static void fflayer_stack_infer_impl(int n_layers, const to_tensor* w, const to_
     act[l].t = new_tensor(1, &n, B, dt);
     GemmProblem p = layer(prev, prev_sm, w[l], act[l].t->ptr);
     p.bias = b[l]->ptr;
-    p.act = 1;
+    p.act = hk + 1;
     if (gemm_epilogue_ok(p)) {
       if (gemm_small_route(p)) launch_gemm_small(p, S());
       else run_gemm(p);
@@ -2563,7 +2573,7 @@ static void fflayer_stack_infer_impl(int n_layers, const to_tensor* w, const to_
       p.bias = nullptr;
       p.act = 0;
       run_gemm(p);
-      launch_bias_logistic_rows(dt, act[l].t->ptr, b[l]->ptr, B, n, S());
+      launch_bias_act_rows(dt, act[l].t->ptr, b[l]->ptr, B, n, hk, S());
     }
     prev = act[l].t->ptr;
     prev_sm = n;
@@ -2612,10 +2622,10 @@ to_status to_fflayer_stack_infer(int n_layers, const to_tensor* w, const to_tens
 }
 
 // ---- recurrent stacks: `runNetwork` / `netGrad` / `trainNetwork'` of Recurrent.hs as one call -------------------------
-// Layer l is `fullyConnected` (Recurrent.hs:91-119; z = W x + W' s + b, new state logistic(z), output z through the layer's
-// `*~ act`) or a stateless ffLayer (:126-138).  Internally everything is TIME-MAJOR, row r = t * B + b, so that every
+// Layer l is `fullyConnected` (Recurrent.hs:91-119; z = W x + W' s + b, new state state_act[l](z) -- logistic or tanh, each
+// layer its own --, output z through the layer's `*~ act`, hidden_act) or a stateless ffLayer (:126-138).  Internally everything is TIME-MAJOR, row r = t * B + b, so that every
 // time-independent piece is ONE contraction over all B*T rows: the input projections (bias in the epilogue), the head,
-// the weight gradients dZ^T X and dZ^T S_prev (+ the bias row sums) and the input cotangents dZ W (logistic' of the layer
+// the weight gradients dZ^T X and dZ^T S_prev (+ the bias row sums) and the input cotangents dZ W (hidden_act' of the layer
 // below in the epilogue).  A stateful layer's states live in St [T+1][B][n] with block 0 = the initial states: S_prev and
 // S are the two offset views St[0..T) and St[1..T] of one buffer.  What is left is each stateful layer's recurrence:
 // persistent (rnn_seq.hip, one launch per layer and direction for all T steps) or per step (one GEMM with the addend,
@@ -2632,7 +2642,7 @@ static bool rnn_persistent_for(int dt, int64_t H, int64_t B, RnnSeqPlan* plan) {
   return g_rnn_persistent == 2 || plan->m_lds;
 }
 
-// C = A . B(op) with the epilogue of p (bias, act = logistic, dact = h (1 - h), beta * Cin); a kernel without one gets
+// C = A . B(op) with the epilogue of p (bias, act = logistic / tanh, dact = h (1 - h) / 1 - h h by dact_kind, beta * Cin); a kernel without one gets
 // the plain product and the epilogue as separate launches.  C is contiguous [M, N].
 static void rnn_gemm(GemmProblem p) {
   if (gemm_epilogue_ok(p)) {
@@ -2640,7 +2650,7 @@ static void rnn_gemm(GemmProblem p) {
     else run_gemm(p);
     return;
   }
-  const int act = p.act;
+  const int act = p.act, dact_kind = p.dact_kind;
   const void* dact = p.dact;
   if (p.bias) {  // C = bias rows, then C += A B
     TO_CHECK(p.beta == 0.0, TO_ERR_STATE, "internal: bias with an addend");
@@ -2649,12 +2659,12 @@ static void rnn_gemm(GemmProblem p) {
     p.Cin = p.C;
   }
   TO_CHECK(!(act && dact), TO_ERR_STATE, "internal: act and dact in one epilogue");
-  p.bias = nullptr; p.act = 0; p.dact = nullptr;
+  p.bias = nullptr; p.act = 0; p.dact = nullptr; p.dact_kind = 0;
   run_gemm(p);
   if (act || dact) {
     EwArgs a{};
     a.dtype = p.dtype;
-    a.kind = act ? EW_LOGISTIC : EW_MUL_H1MH;
+    a.kind = act ? (act == 2 ? EW_TANH : EW_LOGISTIC) : (dact_kind ? EW_MUL_1MH2 : EW_MUL_H1MH);
     a.n = act ? 1 : 2;
     a.x[0] = p.C;
     a.x[1] = dact;
@@ -2705,9 +2715,11 @@ static void rnn_stack_impl(int n_layers, const int* state_act, const to_tensor* 
   NONNULL(state_act); NONNULL(s); NONNULL(ws); NONNULL(w); NONNULL(b); NONNULL(X);
   TO_CHECK(n_layers >= 1, TO_ERR_ARG, F + "need at least one layer");
   for (int l = 0; l < n_layers; ++l)
-    TO_CHECK(state_act[l] == TO_ACT_LOGISTIC || state_act[l] == TO_RNN_STATELESS, TO_ERR_UNSUPPORTED,
-             F + "layer " + std::to_string(l) + ": the state activation must be logistic (or TO_RNN_STATELESS)");
-  stack_hidden_act_check(hidden_act);
+    TO_CHECK(state_act[l] == TO_ACT_LOGISTIC || state_act[l] == TO_ACT_TANH || state_act[l] == TO_RNN_STATELESS,
+             TO_ERR_UNSUPPORTED,
+             F + "layer " + std::to_string(l) + ": the state activation must be logistic or tanh (or TO_RNN_STATELESS)");
+  const int hk = stack_hidden_act_check(hidden_act);
+  auto state_kind = [&](int l) { return state_act[l] == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC; };
   const bool sm_ce = out_act == TO_ACT_SOFTMAX && loss == TO_LOSS_CROSS_ENTROPY;
   const bool lg_se = out_act == TO_ACT_LOGISTIC && loss == TO_LOSS_SQUARED_ERROR;
   if (mode == 0)
@@ -2824,7 +2836,8 @@ static void rnn_stack_impl(int n_layers, const int* state_act, const to_tensor* 
   const void* Yt = mode ? to_time_major(Y, yh) : nullptr;
 
   // ---- forward -------------------------------------------------------------------------------------------------------
-  std::vector<Holder> Z(n_layers), St(n_layers), WT(n_layers);
+  std::vector<Holder> Z(n_layers), St(n_layers), WT(n_layers), Ah(n_layers);
+  std::vector<const void*> outp(n_layers, nullptr);   // what the layer above reads: hidden_act(z_l), all rows
   std::vector<RnnSeqPlan> plan(n_layers);
   std::vector<char> persist(n_layers, 0);
   bool any_state = false, all_persistent = true;
@@ -2839,7 +2852,7 @@ static void rnn_stack_impl(int n_layers, const int* state_act, const to_tensor* 
     // the input projection (stateless hidden layer: its activation) over all rows
     GemmProblem p = rnn_problem(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, Z[l].t->ptr, rows, n, prev_n);
     p.bias = b[l]->ptr;
-    if (!stateful && !last) p.act = 1;
+    if (!stateful && !last) p.act = hk + 1;
     if (last && !stateful && mode == 0) { p.bias = nullptr; no_bias_for_head = b[l]->ptr; }
     rnn_gemm(p);
     if (stateful) {
@@ -2860,19 +2873,30 @@ static void rnn_stack_impl(int n_layers, const int* state_act, const to_tensor* 
         const int64_t dd[2] = {n, n}, ss[2] = {1, n};  // W'^T: M[k][j] = W'[j][k]
         WT[l].t = new_tensor(2, dd, 0, dt);
         launch_copy_strided(dt, ws[l]->ptr, WT[l].t->ptr, 2, dd, ss, S());
-        launch_rnn_seq(dt, false, plan[l], WT[l].t->ptr, z, st, B, T, n, S());
+        launch_rnn_seq(dt, false, plan[l], WT[l].t->ptr, z, st, B, T, n, state_kind(l), S());
       } else {
-        for (int64_t t = 0; t < T; ++t) {  // z_t = P_t + s_{t-1} W'^T (in place), s_t = logistic(z_t)
+        for (int64_t t = 0; t < T; ++t) {  // z_t = P_t + s_{t-1} W'^T (in place), s_t = state_act(z_t)
           GemmProblem q = rnn_problem(dt, at(st, t * B * n), n, 1, ws[l]->ptr, 1, n, at(z, t * B * n), B, n, n);
           q.beta = 1.0;
           q.Cin = q.C;
           rnn_gemm(q);
-          ew2(dt, EW_LOGISTIC, at(st, (t + 1) * B * n), at(z, t * B * n), nullptr, B * n);
+          ew2(dt, state_kind(l) == ACT_KIND_TANH ? EW_TANH : EW_LOGISTIC, at(st, (t + 1) * B * n), at(z, t * B * n), nullptr,
+              B * n);
         }
       }
     }
-    // what the layer above reads: a hidden stateful layer's output logistic(z) IS its state
-    prev = stateful && !last ? at(St[l].t->ptr, B * n) : Z[l].t->ptr;
+    // what the layer above reads: a hidden stateful layer's output hidden_act(z) IS its state when the two activations
+    // are the same function; otherwise it is one more elementwise pass over all rows of z
+    if (stateful && !last && state_kind(l) == hk) {
+      prev = at(St[l].t->ptr, B * n);
+    } else if (stateful && !last) {
+      Ah[l].t = new_tensor(2, d2, 0, dt);
+      ew2(dt, hk == ACT_KIND_TANH ? EW_TANH : EW_LOGISTIC, Ah[l].t->ptr, Z[l].t->ptr, nullptr, rows * n);
+      prev = Ah[l].t->ptr;
+    } else {
+      prev = Z[l].t->ptr;
+    }
+    outp[l] = prev;
     prev_n = n;
   }
   if (any_state) (all_persistent ? g_rnn_persistent_runs : g_rnn_stepwise_runs)++;
@@ -2936,16 +2960,17 @@ static void rnn_stack_impl(int n_layers, const int* state_act, const to_tensor* 
     const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
     const bool stateful = state_act[l] != TO_RNN_STATELESS;
     void* dz = dz_cur.t->ptr;
-    if (stateful) {  // dz_t = G_t + (dz_{t+1} W') (.) s_t (1 - s_t), in place over G
+    if (stateful) {  // dz_t = G_t + (dz_{t+1} W') (.) state_act'(s_t), in place over G
       void* st = St[l].t->ptr;
       if (persist[l]) {
-        launch_rnn_seq(dt, true, plan[l], ws[l]->ptr, dz, st, B, T, n, S());
-      } else {  // per step: D = (dz_{t+1} W') (.) s_t (1 - s_t), then dz_t += D
+        launch_rnn_seq(dt, true, plan[l], ws[l]->ptr, dz, st, B, T, n, state_kind(l), S());
+      } else {  // per step: D = (dz_{t+1} W') (.) state_act'(s_t), then dz_t += D
         const int64_t d2[2] = {B, n};
         Holder dtmp(new_tensor(2, d2, 0, dt));
         for (int64_t t = T - 2; t >= 0; --t) {
           GemmProblem q = rnn_problem(dt, at(dz, (t + 1) * B * n), n, 1, ws[l]->ptr, n, 1, dtmp.t->ptr, B, n, n);
           q.dact = at(st, (t + 1) * B * n);
+          q.dact_kind = state_kind(l);
           rnn_gemm(q);
           ew2(dt, EW_AFFINE, at(dz, t * B * n), at(dz, t * B * n), dtmp.t->ptr, B * n);
         }
@@ -2957,7 +2982,7 @@ static void rnn_stack_impl(int n_layers, const int* state_act, const to_tensor* 
       run_gemm(rnn_problem(dt, dsum.t->ptr, n, 1, ws[l]->ptr, n, 1, g_s[l], 1, n, n));
     }
     // gW = dZ^T A_in (+ gb = the row sums of dZ)
-    const void* a_in = l > 0 ? (state_act[l - 1] != TO_RNN_STATELESS ? at(St[l - 1].t->ptr, B * m) : Z[l - 1].t->ptr) : Xt;
+    const void* a_in = l > 0 ? outp[l - 1] : Xt;
     GemmProblem p = rnn_problem(dt, dz, 1, n, a_in, m, 1, g_w[l], n, m, rows);
     p.rowsum = g_b[l];
     if (gemm_small_route(p)) {
@@ -2967,7 +2992,7 @@ static void rnn_stack_impl(int n_layers, const int* state_act, const to_tensor* 
       run_gemm(p);
       launch_sum_axis(dt, dz, g_b[l], 1, rows, n, 0, n, 1, S());
     }
-    // the cotangent of the layer's input: dZ W (. logistic' of the layer below, whose output is a_in)
+    // the cotangent of the layer's input: dZ W (. hidden_act' of the layer below, whose output is a_in)
     if (l > 0 || gx) {
       Holder next;
       void* dst = l > 0 ? nullptr : scratch_or(gx, m, gxh);
@@ -2977,7 +3002,7 @@ static void rnn_stack_impl(int n_layers, const int* state_act, const to_tensor* 
         dst = next.t->ptr;
       }
       GemmProblem q = rnn_problem(dt, dz, n, 1, w[l]->ptr, m, 1, dst, rows, m, n);
-      if (l > 0) q.dact = a_in;
+      if (l > 0) { q.dact = a_in; q.dact_kind = hk; }
       rnn_gemm(q);
       if (l == 0) from_time_major(dst, gx, m);
       else { Holder drop(dz_cur.take()); dz_cur.t = next.take(); }
@@ -3072,7 +3097,7 @@ static void induce_impl(int n_layers, const to_tensor* w, const to_tensor* b, in
   TO_CHECK(n_layers >= 1, TO_ERR_ARG, F + "need at least one layer");
   TO_CHECK(iters >= 0, TO_ERR_ARG, F + "negative iteration count");
   TO_CHECK(!gx || iters >= 1, TO_ERR_ARG, F + "gx is the gradient of the last iteration: it needs iters >= 1");
-  stack_hidden_act_check(hidden_act);
+  const int hk = stack_hidden_act_check(hidden_act);
   const bool sm_ce = out_act == TO_ACT_SOFTMAX && loss == TO_LOSS_CROSS_ENTROPY;
   const bool lg_se = out_act == TO_ACT_LOGISTIC && loss == TO_LOSS_SQUARED_ERROR;
   TO_CHECK(sm_ce || lg_se, TO_ERR_UNSUPPORTED, F + "(softmax, crossEntropy) or (logistic, squaredError) only");
@@ -3153,7 +3178,7 @@ static void induce_impl(int n_layers, const to_tensor* w, const to_tensor* b, in
     const void *wp[INDUCE_MAX_LAYERS], *bp[INDUCE_MAX_LAYERS];
     for (int l = 0; l < n_layers; ++l) { wp[l] = w[l]->ptr; bp[l] = b[l]->ptr; }
     launch_induce_seq(dt, plan, n_layers, dims, wp, bp, cur.t->ptr, yr->ptr, y_sm, gxs.t ? gxs.t->ptr : nullptr,
-                      lt.t ? lt.t->ptr : nullptr, B, iters, rate, sm_ce ? 1 : 2, S());
+                      lt.t ? lt.t->ptr : nullptr, B, iters, rate, sm_ce ? 1 : 2, hk, S());
     TO_HIP(hipStreamSynchronize(S()));   // the watchdog's verdict is read before anything of the caller's is written
     int64_t bad_row = 0;
     const int64_t bad = induce_seq_status(&bad_row);
@@ -3191,21 +3216,22 @@ static void induce_impl(int n_layers, const to_tensor* w, const to_tensor* b, in
     for (int64_t k = 0; k < iters; ++k) {
       const void* prev = xp;
       int64_t prev_n = i0;
-      for (int l = 0; l < n_layers; ++l) {   // a_l = logistic(a_{l-1} W_l^T + b_l); the last layer: z_L
+      for (int l = 0; l < n_layers; ++l) {   // a_l = hidden_act(a_{l-1} W_l^T + b_l); the last layer: z_L
         const int64_t n = w[l]->dims[0];
         GemmProblem p = rnn_problem(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, act[l].t->ptr, B, n, prev_n);
         p.bias = b[l]->ptr;
-        if (l + 1 < n_layers) p.act = 1;
+        if (l + 1 < n_layers) p.act = hk + 1;
         rnn_gemm(p);
         prev = act[l].t->ptr;
         prev_n = n;
       }
       launch_loss_grad_rows(dt, act[n_layers - 1].t->ptr, yp, dz[n_layers - 1].t->ptr, lcol.t ? at(lcol.t->ptr, k * B) : nullptr,
                             B, nL, sm_ce ? 0 : 1, S());
-      for (int l = n_layers - 1; l > 0; --l) {   // dz_{l-1} = (dz_l W_l) (.) a_{l-1} (1 - a_{l-1})
+      for (int l = n_layers - 1; l > 0; --l) {   // dz_{l-1} = (dz_l W_l) (.) hidden_act'(a_{l-1})
         const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
         GemmProblem q = rnn_problem(dt, dz[l].t->ptr, n, 1, w[l]->ptr, m, 1, dz[l - 1].t->ptr, B, m, n);
         q.dact = act[l - 1].t->ptr;
+        q.dact_kind = hk;
         rnn_gemm(q);
       }
       const int64_t n1 = w[0]->dims[0];
@@ -3395,7 +3421,7 @@ to_status to_graph_online_sgd(to_graph g, to_tensor x_buf, to_tensor y_buf, to_t
       idx_dev = static_cast<const long long*>(order.t->ptr);
     }
     online_sgd_reset_status();
-    launch_online_sgd(f.dtype, f.L, f.dims, f.W, f.b, X->ptr, Y->ptr, idx_dev, n_idx, f.rate, f.head, S());
+    launch_online_sgd(f.dtype, f.L, f.dims, f.W, f.b, X->ptr, Y->ptr, idx_dev, n_idx, f.rate, f.head, ACT_KIND_LOGISTIC, S());
     TO_HIP(hipStreamSynchronize(S()));
     TO_CHECK(online_sgd_status() == 0, TO_ERR_HIP,
              "online SGD kernel: a workgroup barrier timed out at sample " + std::to_string(online_sgd_status() - 1) +

@@ -272,6 +272,7 @@ struct GemmProblem {
   const void* tail_h = nullptr;
   void* tail_out = nullptr;
   int tail_n = 0;
+  int tail_kind = 0;   // what `tail_h` holds, numbered like dact_kind: 1: h = tanh(z), tail_out = (dz . tail_w) * (1 - h^2)
   // Sibling products in one launch (lazy.cpp, round 6): `M` rows are `M / a_table_rows` matrices of a_table_rows rows each
   // that live in SEPARATE allocations -- matrix i's rows start at a_table[i] (a device array of pointers; same strides for
   // all) -- and share B; C is one tall matrix.  Understood by the short-K streaming kernel only (gemm_skinnyk.hip).
@@ -332,6 +333,32 @@ bool gemm_mfma_worthwhile(const GemmProblem& p);
 bool gemm_w4_full_rounds(const GemmProblem& p);
 bool gemm_w4_edge_whole(const GemmProblem& p);  // ragged (multiples of 4) but worth running whole on the pinned kernel
 bool gemm_f64_w4_full_rounds(const GemmProblem& p);
+
+// The hidden / state activations of the one-call stack entries (to_fflayer_stack_*, to_rnn_stack_*), numbered like
+// GemmProblem::dact_kind (GemmProblem::act is this + 1).  The persistent kernels and the loss head's fused tail take the
+// number as a template parameter.  The tanh pair -- the value, and the derivative FROM THE STORED OUTPUT -- is what the GEMM
+// epilogues compute (tanhf / tanh, 1 - h h): every route of an entry computes the same function.  A further activation
+// whose derivative can be written on its output goes here.
+constexpr int ACT_KIND_LOGISTIC = 0, ACT_KIND_TANH = 1;
+__device__ __forceinline__ float tanh_act(float z) { return tanhf(z); }
+__device__ __forceinline__ double tanh_act(double z) { return tanh(z); }
+__device__ __forceinline__ float tanh_dact(float h) { return 1.0f - h * h; }
+__device__ __forceinline__ double tanh_dact(double h) { return 1.0 - h * h; }
+// The two persistent per-sample kernels (online_sgd.hip, induce_seq.hip) share their logistic -- the fast exponential in
+// fp32 -- and the dispatch on the hidden activation: the value, and `s * act'` written on the stored output h.
+// (rnn_seq.hip's logistic calls expf and stays its own.)
+__device__ __forceinline__ float logistic_f(float z) { return 1.0f / (1.0f + __expf(-z)); }
+__device__ __forceinline__ double logistic_f(double z) { return 1.0 / (1.0 + exp(-z)); }
+template <int ACT, class S>
+__device__ __forceinline__ S hid_act(S z) {
+  if constexpr (ACT == ACT_KIND_TANH) return tanh_act(z);
+  else return logistic_f(z);
+}
+template <int ACT, class S>
+__device__ __forceinline__ S hid_dact(S s, S h) {
+  if constexpr (ACT == ACT_KIND_TANH) return s * tanh_dact(h);
+  else return s * h * (S(1.0) - h);
+}
 
 // elementwise
 enum EwKind {
@@ -413,7 +440,7 @@ void launch_rank1_general(int dtype, int n, const void* const* dz, const void* c
 // online_sgd.hip: per-sample SGD over a stream of samples as one persistent launch (fp32 ffLayer stacks)
 bool online_sgd_plan(int dtype, int L, const int64_t* dims, int* G_out, int* rpw_out, size_t* lds_out);
 void launch_online_sgd(int dtype, int L, const int64_t* dims, void* const* W, void* const* b, const void* X, const void* Y,
-                       const long long* idx_dev, int64_t n, double rate, int head, hipStream_t s);
+                       const long long* idx_dev, int64_t n, double rate, int head, int act_kind, hipStream_t s);
 bool online_sgd_placement_ok(hipStream_t s);   // probed once: do workgroups b, b + 8, ... of a grid share an XCD?
 int online_sgd_status();
 void online_sgd_reset_status();
@@ -429,11 +456,11 @@ void launch_infer_narrow(int dtype, const void* A, int64_t a_sm, int64_t B, int6
                          unsigned long long* conf, hipStream_t s);
 void launch_infer_rows(int dtype, const void* z, int64_t B, const void* bias, int n, bool softmax, void* out,
                        const void* y, int64_t y_sm, int* classes, unsigned long long* conf, hipStream_t s);
-// x[r][j] = logistic(x[r][j] + bias[j]) in place (a hidden layer whose GEMM carried no epilogue)
-void launch_bias_logistic_rows(int dtype, void* x, const void* bias, int64_t B, int64_t n, hipStream_t s);
+// x[r][j] = act(x[r][j] + bias[j]) in place, act_kind ACT_KIND_* (a hidden layer whose GEMM carried no epilogue)
+void launch_bias_act_rows(int dtype, void* x, const void* bias, int64_t B, int64_t n, int act_kind, hipStream_t s);
 // rnn_seq.hip: the recurrence of a stateful layer over all T steps in one launch (to_rnn_stack_*).  M [H][H]: W'^T
-// (forward: Z = P -> z in place, St blocks 1..T = logistic(z)) or W' (reverse: Z = G -> dz in place, reading St blocks
-// 1..T).  Z [T][B][H], St [T+1][B][H] (block 0: the initial states).  H <= RNN_SEQ_MAX_H, any B and T.
+// (forward: Z = P -> z in place, St blocks 1..T = act(z), act_kind ACT_KIND_*) or W' (reverse: Z = G -> dz in place, reading
+// St blocks 1..T).  Z [T][B][H], St [T+1][B][H] (block 0: the initial states).  H <= RNN_SEQ_MAX_H, any B and T.
 constexpr int64_t RNN_SEQ_MAX_H = 1024;
 struct RnnSeqPlan {
   int R = 1;          // sequences per workgroup
@@ -443,7 +470,7 @@ struct RnnSeqPlan {
 };
 bool rnn_seq_plan(int dtype, int64_t H, int64_t B, RnnSeqPlan* p);
 void launch_rnn_seq(int dtype, bool reverse, const RnnSeqPlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T,
-                    int64_t H, hipStream_t s);
+                    int64_t H, int act_kind, hipStream_t s);
 // induce_seq.hip: every iteration of `induceNetwork` on every row in one launch (to_fflayer_stack_induce, route B).
 // X [B][i0] contiguous: x_0 on entry, x_iters on exit; gx [B][i0] (optional) the last iteration's gradient; losses
 // [B][iters] (optional).  A plan with G > 1 may only be launched where online_sgd_placement_ok() holds.
@@ -457,7 +484,7 @@ struct InduceSeqPlan {
 bool induce_seq_plan(int dtype, int L, const int64_t* dims, int64_t B, int64_t iters, InduceSeqPlan* plan);
 void launch_induce_seq(int dtype, const InduceSeqPlan& plan, int L, const int64_t* dims, const void* const* W,
                        const void* const* b, void* X, const void* Y, int64_t y_sm, void* gx, void* losses, int64_t B,
-                       int64_t iters, double rate, int head, hipStream_t s);
+                       int64_t iters, double rate, int head, int act_kind, hipStream_t s);
 int64_t induce_seq_status(int64_t* row);   // 0, or the iteration (1-based) at which a wait timed out
 
 }  // namespace to

@@ -134,7 +134,7 @@ __device__ __forceinline__ double xor16(double x) { return __shfl_xor(x, OFF, 64
 //      development build (SM_STAMP) generates the same load / MFMA order as the product (tests/test_step_schedule.py).
 // STAG: the four waves of a SIMD (w, w + 4, w + 8, w + 12) issue their loads at falling priority, so the CU's one
 //      vector-memory path completes whole waves in turn instead of a sixteenth of everybody's.
-template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0, bool EXT = false, int PARTS = 0, bool STAG = false>   // ONESHOT: 0, or the chunks one batch holds
+template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0, bool EXT = false, int PARTS = 0, bool STAG = false, int TAILK = 0>   // ONESHOT: 0, or the chunks one batch holds; TAILK: GemmProblem::tail_kind
 __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const int bid, const long bz, S* ext_lds = nullptr,
                                                 const int tid_in = -1) {
   constexpr int ES = (int)sizeof(S);
@@ -475,7 +475,7 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
   SM_STAMP(6);   // (reduction, epilogue / loss head, stores issued)
   if constexpr (TS == 16) {
     if (g.loss_rows && g.tail_out) {
-      // fused tail: tail_out[16 rows][tail_n] = (dz[16][N] . W[N][tail_n]) * h(1-h); the waves share the
+      // fused tail: tail_out[16 rows][tail_n] = (dz[16][N] . W[N][tail_n]) * h(1-h) (TAILK 1, tanh: * (1 - h h)); the waves share the
       // 16-column tiles of the output, K = N <= 16 is at most four 16x16x4 MFMA steps
       __syncthreads();
       typedef S acc4 __attribute__((ext_vector_type(4)));
@@ -507,8 +507,10 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const long row = (long)tile_m * 16 + row16(kg, r);
-          if (t < ntiles && row < g.M && col < g.tail_n)
-            g.tail_out[row * g.tail_n + col] = acc2[u][r] * tl_hv[u][r] * (S(1) - tl_hv[u][r]);
+          if (t < ntiles && row < g.M && col < g.tail_n) {
+            if constexpr (TAILK == ACT_KIND_TANH) g.tail_out[row * g.tail_n + col] = acc2[u][r] * tanh_dact(tl_hv[u][r]);
+            else g.tail_out[row * g.tail_n + col] = acc2[u][r] * tl_hv[u][r] * (S(1) - tl_hv[u][r]);
+          }
         }
       }
       SM_STAMP(7);   // (tail stores issued)
@@ -519,9 +521,9 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
 #endif
 }
 
-template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0>
+template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0, int TAILK = 0>
 __global__ __launch_bounds__(NW * 64) void gemm_small_kernel(SmallArgsT<S> g) {
-  gemm_small_body<S, AMODE, BMODE, NW, TS, ONESHOT>(g, (int)blockIdx.x, (long)blockIdx.z);
+  gemm_small_body<S, AMODE, BMODE, NW, TS, ONESHOT, false, 0, false, TAILK>(g, (int)blockIdx.x, (long)blockIdx.z);
 }
 
 // The step's loss-head launch (z = H W2^T + b2, the loss head on each row, the hidden layer's cotangent as the fused tail)
@@ -534,6 +536,13 @@ __global__ __launch_bounds__(8 * 64) void gemm_small_head_kernel(SmallArgsT<floa
   g.a_vec = 1;
   g.b_vec = 1;
   gemm_small_body<float, 0, 1, 8, 16, 2>(g, (int)blockIdx.x, (long)blockIdx.z);
+}
+// ... and the same launch behind a tanh hidden layer: the tail multiplies by 1 - h h (a kernel of its own, so that the
+// logistic step's kernel above is the code it was)
+__global__ __launch_bounds__(8 * 64) void gemm_small_head_tanh_kernel(SmallArgsT<float> g) {
+  g.a_vec = 1;
+  g.b_vec = 1;
+  gemm_small_body<float, 0, 1, 8, 16, 2, false, 0, false, ACT_KIND_TANH>(g, (int)blockIdx.x, (long)blockIdx.z);
 }
 
 // Two independent latency-bound GEMMs in ONE launch (the weight gradients of two layers once both
@@ -950,7 +959,7 @@ static int pick_tile_order(const GemmProblem& p, int ts, int tiles_m, int tiles_
   return col_cost < row_cost ? 2 : 1;
 }
 
-template <class S, int NW, int TS, int ONESHOT = 0>
+template <class S, int NW, int TS, int ONESHOT = 0, int TAILK = 0>
 static void launch_nw(SmallArgsT<S>& g, const GemmProblem& p, int amode, int bmode, hipStream_t s) {
   constexpr int CK = (TS == 32) ? 8 : 16;
   const int chunks = (int)((p.K + CK - 1) / CK);
@@ -961,10 +970,10 @@ static void launch_nw(SmallArgsT<S>& g, const GemmProblem& p, int amode, int bmo
   g.tile_order = pick_tile_order(p, TS, g.tiles_m, g.tiles_n);
   dim3 grid(tiles_m * g.tiles_n, 1, (unsigned)p.batch), block(NW * 64);
   switch (amode * 2 + bmode) {
-    case 0: launch_k((gemm_small_kernel<S, 0, 0, NW, TS, ONESHOT>), grid, block, 0, s, g); break;
-    case 1: launch_k((gemm_small_kernel<S, 0, 1, NW, TS, ONESHOT>), grid, block, 0, s, g); break;
-    case 2: launch_k((gemm_small_kernel<S, 1, 0, NW, TS, ONESHOT>), grid, block, 0, s, g); break;
-    default: launch_k((gemm_small_kernel<S, 1, 1, NW, TS, ONESHOT>), grid, block, 0, s, g); break;
+    case 0: launch_k((gemm_small_kernel<S, 0, 0, NW, TS, ONESHOT, TAILK>), grid, block, 0, s, g); break;
+    case 1: launch_k((gemm_small_kernel<S, 0, 1, NW, TS, ONESHOT, TAILK>), grid, block, 0, s, g); break;
+    case 2: launch_k((gemm_small_kernel<S, 1, 0, NW, TS, ONESHOT, TAILK>), grid, block, 0, s, g); break;
+    default: launch_k((gemm_small_kernel<S, 1, 1, NW, TS, ONESHOT, TAILK>), grid, block, 0, s, g); break;
   }
 }
 
@@ -1128,6 +1137,7 @@ static void launch_small_t(const GemmProblem& p, hipStream_t s) {
   }
   // the loss head of a short K on the lean one-shot instance (gemm_small_head_kernel); every other shape stays where it was
   static const int head_lean = [] { const char* e = ab_getenv("TOPS_SMALL_HEAD_LEAN"); return e ? atoi(e) : 1; }();
+  const bool tanh_tail = g.tail_out && p.tail_kind == ACT_KIND_TANH;   // the tail's derivative: a template parameter of the kernel
   bool lean = false;
   if constexpr (!F64)
     lean = head_lean && g.loss_rows && c.ts == 16 && c.nw == 8 && c.os == 0 && amode == 0 && bmode == 1 && g.a_vec && g.b_vec &&
@@ -1135,8 +1145,12 @@ static void launch_small_t(const GemmProblem& p, hipStream_t s) {
   if (lean) {
     if constexpr (!F64) {   // (plan_small's kper is already the slice of at most two chunks)
       const dim3 grid((unsigned)(g.tiles_m * g.tiles_n), 1, (unsigned)p.batch), block(8 * 64);
-      launch_k(gemm_small_head_kernel, grid, block, 0, s, g);
+      if (tanh_tail) launch_k(gemm_small_head_tanh_kernel, grid, block, 0, s, g);
+      else launch_k(gemm_small_head_kernel, grid, block, 0, s, g);
     }
+  } else if (tanh_tail) {   // (a fused tail is always eight waves on 16x16 tiles, two-stage: plan_small)
+    TO_CHECK(c.ts == 16 && c.nw == 8 && c.os == 0, TO_ERR_STATE, "internal: fused tail outside its configuration");
+    launch_nw<S, 8, 16, 0, ACT_KIND_TANH>(g, p, amode, bmode, s);
   } else if (c.os == 8 && c.nw == 16) {
     if constexpr (!F64) launch_nw<S, 16, 32, 8>(g, p, amode, bmode, s);
   } else if (c.os == 8) {
@@ -1176,6 +1190,7 @@ bool launch_gemm_small_chain(const GemmProblem& pa, const GemmProblem& pb, const
   // ~2.3 us.  On an 8-XCD part a grid barrier is an order of magnitude dearer than the boundary it would replace.
   static const int enable = [] { const char* e = ab_getenv("TOPS_STEP_CHAIN"); return e ? atoi(e) : 0; }();
   if (!enable) return false;
+  if (pb.tail_out && pb.tail_kind) return false;   // (the chained kernel carries the logistic tail only)
   const GemmProblem* ps[4] = {&pa, &pb, &pc1, &pc2};
   for (const GemmProblem* p : ps)
     if (p->dtype != TO_F32 || p->batch != 1 || !gemm_small_can(*p)) return false;
@@ -1293,6 +1308,7 @@ bool launch_gemm_small_seam(const GemmProblem& pf, const GemmProblem& ph, hipStr
   // its row block and the launch's own 2.4 us dispatch ramp, instead of overlapping the next launch's ramp.
   // TOPS_STEP_SEAM=1: the last arriver is the head; =2: the workgroup of the row block's last tile is, and waits.
   // round 5: the joined form on four-wave tiles, every workgroup of a row block taking four rows of the head (gemm_t32.hip; TOPS_STEP_SEAM=3)
+  if (ph.tail_out && ph.tail_kind) return false;   // (the joined kernels carry the logistic tail only)
   if (launch_gemm_t32_head(pf, ph, s)) return true;
   static const int enable = [] { const char* e = getenv("TOPS_STEP_SEAM"); const int v = e ? atoi(e) : 0; return v == 1 || v == 2 ? v : 0; }();
   if (!enable || g_seam_disabled || gemm_small_seam_status() != 0) return false;

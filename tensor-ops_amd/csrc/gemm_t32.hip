@@ -858,6 +858,7 @@ bool launch_gemm_t32_head(const GemmProblem& pf, const GemmProblem& ph, hipStrea
   if (ph.N < 1 || ph.N > 16 || (ph.loss_rows != 1 && ph.loss_rows != 2) || !ph.target) return false;
   if (ph.beta != 0.0 || ph.dact || ph.act != 0 || ph.rowsum) return false;
   if (ph.tail_out) {
+    if (ph.tail_kind) return false;   // (the tail here is the logistic's h (1 - h); only the planner calls this, with tail_kind 0)
     if (ph.tail_n != pf.N || ph.tail_h != pf.C || ph.tail_w != ph.B || ph.b_sn != ph.tail_n) return false;
     if (reinterpret_cast<uintptr_t>(ph.tail_out) & 15u) return false;
   }

@@ -10,7 +10,8 @@
 //     and the matching slice x[J_g].  The slice never leaves its workgroup: x[J_g] -= rate * W_1[:, J_g]^T dz_1 is local;
 //   * forward: every workgroup puts its partial product W_1[:, J_g] x[J_g] (o1 numbers) into an exchange buffer and then
 //     sums the G partials in workgroup order (every workgroup gets the same bits): z_1.  ONE exchange per iteration;
-//   * layers 2..L, the head, the loss and the cotangents back to dz_1 are replicated in every workgroup;
+//   * layers 2..L, the head, the loss and the cotangents back to dz_1 are replicated in every workgroup; the hidden
+//     activation is a template parameter of the kernel: logistic (h (1 - h) backward) or tanh (1 - h h; common.hpp);
 //   * G == 1 (the stack fits one workgroup's LDS) is the same kernel without any exchange: independent workgroups, as many
 //     as there are rows (up to 256), each walking its share of the rows.  With G > 1 one group -- the workgroups with
 //     blockIdx.x % 8 == 0 of a grid of 8 G, the others leave at once -- takes the rows one after the other.
@@ -58,8 +59,7 @@ struct InduceArgs {
   long long timeout; // wall_clock64 ticks
 };
 
-__device__ __forceinline__ float logistic_f(float z) { return 1.0f / (1.0f + __expf(-z)); }
-__device__ __forceinline__ double logistic_f(double z) { return 1.0 / (1.0 + exp(-z)); }
+// (logistic_f, hid_act<ACT>, hid_dact<ACT>: common.hpp, shared by the two persistent per-sample kernels)
 __device__ __forceinline__ float exp_f(float z) { return __expf(z); }
 __device__ __forceinline__ double exp_f(double z) { return exp(z); }
 __device__ __forceinline__ float log_f(float z) { return logf(z); }
@@ -137,7 +137,7 @@ __device__ __forceinline__ void matvec_t(const S* __restrict__ W, int ld, int O,
   }
 }
 
-template <class S>
+template <class S, int ACT>
 __global__ __launch_bounds__(IN_THREADS) void induce_seq_kernel(InduceArgs<S> a) {
   int g = 0;
   long grp = blockIdx.x, ngrp = gridDim.x;
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(IN_THREADS) void induce_seq_kernel(InduceArgs<S> a)
             }
           }
           z += bb[0][j];
-          act[1][j] = L == 1 ? z : logistic_f(z);
+          act[1][j] = L == 1 ? z : hid_act<ACT>(z);
         }
         if (!ok) {
           a.status[1] = row;
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(IN_THREADS) void induce_seq_kernel(InduceArgs<S> a)
         const bool last = l + 1 == L;
         matvec(Wl[l], ld[l], a.dims[l + 1], a.dims[l], act[l], [&](int j, S v) {
           const S z = v + bb[l][j];
-          act[l + 1][j] = last ? z : logistic_f(z);
+          act[l + 1][j] = last ? z : hid_act<ACT>(z);
         });
         __syncthreads();
       }
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(IN_THREADS) void induce_seq_kernel(InduceArgs<S> a)
       for (int l = L - 1; l >= 1; --l) {
         matvec_t(Wl[l], ld[l], a.dims[l + 1], a.dims[l], dz[l + 1], scr, [&](int kk, S s) {
           const S h = act[l][kk];
-          dz[l][kk] = s * h * (S(1.0) - h);
+          dz[l][kk] = hid_dact<ACT>(s, h);
         });
         __syncthreads();
       }
@@ -328,7 +328,7 @@ struct InduceState {
 };
 InduceState g_in;
 
-template <class S>
+template <class S, int ACT>
 void launch_induce_t(const InduceSeqPlan& plan, int L, const int64_t* dims, const void* const* W, const void* const* b, void* X,
                      const void* Y, int64_t y_sm, void* gx, void* losses, int64_t B, int64_t iters, double rate, int head,
                      hipStream_t s) {
@@ -356,11 +356,11 @@ void launch_induce_t(const InduceSeqPlan& plan, int L, const int64_t* dims, cons
   a.timeout = (long long)(timeout_s * 100e6);
   static bool attr = false;
   if (!attr) {
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(induce_seq_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(induce_seq_kernel<S, ACT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                160 * 1024));
     attr = true;
   }
-  launch_k(induce_seq_kernel<S>, dim3((unsigned)plan.grid), dim3(IN_THREADS), plan.lds, s, a);
+  launch_k(induce_seq_kernel<S, ACT>, dim3((unsigned)plan.grid), dim3(IN_THREADS), plan.lds, s, a);
 }
 
 }  // namespace
@@ -394,7 +394,8 @@ bool induce_seq_plan(int dtype, int L, const int64_t* dims, int64_t B, int64_t i
 
 void launch_induce_seq(int dtype, const InduceSeqPlan& plan, int L, const int64_t* dims, const void* const* W,
                        const void* const* b, void* X, const void* Y, int64_t y_sm, void* gx, void* losses, int64_t B,
-                       int64_t iters, double rate, int head, hipStream_t s) {
+                       int64_t iters, double rate, int head, int act_kind, hipStream_t s) {
+  TO_CHECK(act_kind == ACT_KIND_LOGISTIC || act_kind == ACT_KIND_TANH, TO_ERR_ARG, "induce kernel: unknown hidden activation");
   TO_CHECK(plan.G >= 1 && plan.G <= 32 && plan.grid >= 1 && plan.grid <= 256 && plan.lds <= 160 * 1024, TO_ERR_STATE,
            "induce kernel: not a plan of induce_seq_plan");
   if (!g_in.status) {
@@ -413,8 +414,13 @@ void launch_induce_seq(int dtype, const InduceSeqPlan& plan, int L, const int64_
     }
     TO_HIP(hipMemsetAsync(g_in.exch, 0, need, s));  // (no tag of an earlier launch may pass for one of this launch)
   }
-  if (dtype == TO_F64) launch_induce_t<double>(plan, L, dims, W, b, X, Y, y_sm, gx, losses, B, iters, rate, head, s);
-  else launch_induce_t<float>(plan, L, dims, W, b, X, Y, y_sm, gx, losses, B, iters, rate, head, s);
+  if (act_kind == ACT_KIND_TANH) {
+    if (dtype == TO_F64) launch_induce_t<double, ACT_KIND_TANH>(plan, L, dims, W, b, X, Y, y_sm, gx, losses, B, iters, rate, head, s);
+    else launch_induce_t<float, ACT_KIND_TANH>(plan, L, dims, W, b, X, Y, y_sm, gx, losses, B, iters, rate, head, s);
+  } else {
+    if (dtype == TO_F64) launch_induce_t<double, ACT_KIND_LOGISTIC>(plan, L, dims, W, b, X, Y, y_sm, gx, losses, B, iters, rate, head, s);
+    else launch_induce_t<float, ACT_KIND_LOGISTIC>(plan, L, dims, W, b, X, Y, y_sm, gx, losses, B, iters, rate, head, s);
+  }
   TO_HIP(hipGetLastError());
   count_launch();
 }

@@ -6,8 +6,9 @@
 //                         fit), eight lanes share a row and the finished row stays within the wave for the epilogue.
 //   infer_rows_kernel   : any n_L.  z (the last GEMM's output, bias not added) -> bias, softmax / logistic, store,
 //                         argMax, confusion: one wave per row, looping over the row in 64-wide chunks.
-//   bias_logistic_kernel: a hidden layer whose GEMM has no fused epilogue (the tiled fp64 kernel): h = logistic(z + b)
-//                         in place, one elementwise launch (what the planner does then, lazy.cpp).
+//   bias_act_kernel     : a hidden layer whose GEMM has no fused epilogue (the tiled fp64 kernel): h = act(z + b), act
+//                         logistic or tanh (a template parameter), in place, one elementwise launch (what the planner
+//                         does then, lazy.cpp).
 // argMax follows arg_max_rows_kernel (reduce_layout.hip) exactly -- the same per-lane fold and the same xor tree -- so a
 // class id is bit for bit what to_arg_max returns for the stored row, ties (earliest index) and NaN included.
 // Every reduction has a fixed order per row: a row's result does not depend on B or on where the row sits in the batch.
@@ -236,11 +237,12 @@ __global__ __launch_bounds__(256) void infer_rows_kernel(const S* z, long B, con
   if (conf) atomicAdd(&conf[(long)pred * n + actual], 1ull);
 }
 
-template <class S>
-__global__ __launch_bounds__(256) void bias_logistic_kernel(S* __restrict__ x, const S* __restrict__ bias, long total,
-                                                            long n) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256)
-    x[i] = S(1) / (S(1) + exp_i(-(x[i] + bias[i % n])));
+template <class S, int ACT>
+__global__ __launch_bounds__(256) void bias_act_kernel(S* __restrict__ x, const S* __restrict__ bias, long total, long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    if constexpr (ACT == ACT_KIND_TANH) x[i] = tanh_act(x[i] + bias[i % n]);
+    else x[i] = S(1) / (S(1) + exp_i(-(x[i] + bias[i % n])));
+  }
 }
 
 template <class S, int NP>
@@ -291,12 +293,17 @@ void launch_infer_rows(int dtype, const void* z, int64_t B, const void* bias, in
   count_launch();
 }
 
-void launch_bias_logistic_rows(int dtype, void* x, const void* bias, int64_t B, int64_t n, hipStream_t s) {
+void launch_bias_act_rows(int dtype, void* x, const void* bias, int64_t B, int64_t n, int act_kind, hipStream_t s) {
   const int64_t total = B * n;
   if (total == 0) return;
+  TO_CHECK(act_kind == ACT_KIND_LOGISTIC || act_kind == ACT_KIND_TANH, TO_ERR_ARG, "bias_act_rows: unknown activation");
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 16);
-  TO_DISPATCH(dtype, launch_k(bias_logistic_kernel<S>, dim3(grid), dim3(256), 0, s, (S*)x, (const S*)bias, (long)total,
-                              (long)n));
+  if (act_kind == ACT_KIND_TANH)
+    TO_DISPATCH(dtype, launch_k(bias_act_kernel<S, ACT_KIND_TANH>, dim3(grid), dim3(256), 0, s, (S*)x, (const S*)bias,
+                                (long)total, (long)n));
+  else
+    TO_DISPATCH(dtype, launch_k(bias_act_kernel<S, ACT_KIND_LOGISTIC>, dim3(grid), dim3(256), 0, s, (S*)x, (const S*)bias,
+                                (long)total, (long)n));
   TO_HIP(hipGetLastError());
   count_launch();
 }

@@ -7,14 +7,15 @@
 // in one kernel whose workgroups keep the parameters in LDS between samples:
 //
 //   * layer 1 (the big one: 300 x 784) is split by ROWS over G <= 32 workgroups; workgroup g owns rows R_g of W1, b1
-//     and computes its slice of h1 = logistic(W1 x + b1);
+//     and computes its slice of h1 = act(W1 x + b1) -- act, the hidden activation, is a template parameter of the kernel:
+//     logistic (h (1 - h) backward) or tanh (1 - h h; common.hpp);
 //   * layer 2 is split by COLUMNS along the same index set: workgroup g owns W2[:, R_g] and contributes the partial
 //     product W2[:, R_g] h1[R_g] -- o2 numbers -- to an exchange buffer.  One barrier per sample; afterwards every
 //     workgroup sums the G partials (in workgroup order: every workgroup gets the same bits) and has z2;
 //   * layers 3..L and the loss head are small and replicated: every workgroup computes them and applies the identical
 //     update to its own copy, so the copies stay bit-identical and no further exchange is needed;
 //   * backward: dz_L from the head, back through the replicated layers, dz2 -> the workgroup's slice of
-//     dz1 = (W2[:, R_g]^T dz2) h1 (1 - h1) needs only what the workgroup owns; then every parameter is updated in LDS
+//     dz1 = (W2[:, R_g]^T dz2) act'(h1) needs only what the workgroup owns; then every parameter is updated in LDS
 //     (`p - r * g`, FeedForward.hs:145-147).  The next sample's input is fetched while this one is computed.
 //
 // All participating workgroups sit on one XCD (the grid is 8 G workgroups, workgroup b runs on XCD b % 8, those with
@@ -56,8 +57,7 @@ struct OnlineArgs {
   long long* dbg;    // development (TOPS_ONLINE_STAMPS): phase time stamps of workgroup 0 at sample 64
 };
 
-__device__ __forceinline__ float logistic_f(float z) { return 1.0f / (1.0f + __expf(-z)); }
-__device__ __forceinline__ double logistic_f(double z) { return 1.0 / (1.0 + exp(-z)); }
+// (logistic_f, hid_act<ACT>, hid_dact<ACT>: common.hpp, shared by the two persistent per-sample kernels)
 __device__ __forceinline__ float exp_f(float z) { return __expf(z); }
 __device__ __forceinline__ double exp_f(double z) { return exp(z); }
 __device__ __forceinline__ float fma_f(float a, float b, float c) { return fmaf(a, b, c); }
@@ -90,7 +90,7 @@ template <class S> __device__ __forceinline__ void st_l2(S* p, S v) { __hip_atom
 template <class S> __device__ __forceinline__ S ld_l2(const S* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // (S = float, or double: the reference's own element type, `HMat Double`, BLAS/HMat.hs:35)
-template <class S>
+template <class S, int ACT>
 __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a) {
   if (blockIdx.x & 7) return;  // XCD 0 only
   const int g = blockIdx.x >> 3, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
         }
         S bcc = (bcc0 + bcc1) + (bcc2 + bcc3);
         bcc = wave_sum(bcc);
-        if (lane == 1) h1s[r + NWV] = logistic_f(bcc + b1s[r + NWV]);
+        if (lane == 1) h1s[r + NWV] = hid_act<ACT>(bcc + b1s[r + NWV]);
       } else {
         for (; k + 192 < i0; k += 256) {
           acc0 = fma_f(w[k], xs[k], acc0);
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
       }
       S acc = (acc0 + acc1) + (acc2 + acc3);
       acc = wave_sum(acc);
-      if (lane == 0) h1s[r] = logistic_f(acc + b1s[r]);
+      if (lane == 0) h1s[r] = hid_act<ACT>(acc + b1s[r]);
     }
     __syncthreads();
     ON_STAMP();
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
       }
       for (; q < a.G; ++q) z0 += part[q * o2 + j];
       const S z = bb[1][j] + ((z0 + z1) + (z2 + z3));
-      act[2][j] = L == 2 ? z : logistic_f(z);
+      act[2][j] = L == 2 ? z : hid_act<ACT>(z);
     }
     __syncthreads();
     ON_STAMP();
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
         for (int k = lane; k < K; k += 64) z = fma_f(w[k], act[l][k], z);
         z = wave_sum(z);
         z += bb[l][j];
-        if (lane == 0) act[l + 1][j] = l + 1 == L ? z : logistic_f(z);
+        if (lane == 0) act[l + 1][j] = l + 1 == L ? z : hid_act<ACT>(z);
       }
       __syncthreads();
     ON_STAMP();
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
         S s = S(0.);
         for (int j = 0; j < O; ++j) s = fma_f(Wr[l][j * (K + 1) + k], dz[l + 1][j], s);
         const S h = act[l][k];
-        dz[l][k] = s * h * (S(1.0) - h);
+        dz[l][k] = hid_dact<ACT>(s, h);
       }
       __syncthreads();
     ON_STAMP();
@@ -379,7 +379,7 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
         s2 = wave_sum(s2);
         if (lane == 1) {
           const S h = h1s[r2];
-          dz1s[r2] = s2 * h * (S(1.0) - h);
+          dz1s[r2] = hid_dact<ACT>(s2, h);
         }
       } else {
         for (int j = lane; j < o2; j += 64) s = fma_f(W2s[j * a.rpw + r], dz[2][j], s);
@@ -387,7 +387,7 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
       s = wave_sum(s);
       if (lane == 0) {
         const S h = h1s[r];
-        dz1s[r] = s * h * (S(1.0) - h);
+        dz1s[r] = hid_dact<ACT>(s, h);
       }
     }
     __syncthreads();
@@ -511,7 +511,7 @@ OnlineState g_on;
 
 }  // namespace
 
-// Can the persistent kernel take this stack?  (fp32, 2..6 layers, logistic hidden layers, a head of at most 64 outputs,
+// Can the persistent kernel take this stack?  (fp32 or fp64, 2..6 layers, logistic or tanh hidden layers, a head of at most 64 outputs,
 // an input of at most 2048 elements, everything a workgroup holds within 160 KiB of LDS)
 bool online_sgd_plan(int dtype, int L, const int64_t* dims, int* G_out, int* rpw_out, size_t* lds_out) {
   const int64_t es = dtype == TO_F64 ? 8 : 4;
@@ -538,7 +538,7 @@ bool online_sgd_plan(int dtype, int L, const int64_t* dims, int* G_out, int* rpw
   return false;
 }
 
-template <class S>
+template <class S, int ACT>
 static void launch_online_t(int L, const int64_t* dims, void* const* W, void* const* b, const void* X, const void* Y,
                             const long long* idx_dev, int64_t n, double rate, int head, int G, int rpw, size_t lds, hipStream_t s) {
   OnlineArgs<S> a{};
@@ -586,11 +586,11 @@ static void launch_online_t(int L, const int64_t* dims, void* const* W, void* co
   }
   static bool attr = false;
   if (!attr) {
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(online_sgd_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(online_sgd_kernel<S, ACT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                160 * 1024));
     attr = true;
   }
-  launch_k(online_sgd_kernel<S>, dim3(8 * G), dim3(ON_THREADS), lds, s, a);
+  launch_k(online_sgd_kernel<S, ACT>, dim3(8 * G), dim3(ON_THREADS), lds, s, a);
 }
 
 // The exchange needs every participating workgroup on ONE XCD (one L2).  The kernel gets that from the dispatcher's
@@ -624,7 +624,9 @@ bool online_sgd_placement_ok(hipStream_t s) {
 }
 
 void launch_online_sgd(int dtype, int L, const int64_t* dims, void* const* W, void* const* b, const void* X, const void* Y,
-                       const long long* idx_dev, int64_t n, double rate, int head, hipStream_t s) {
+                       const long long* idx_dev, int64_t n, double rate, int head, int act_kind, hipStream_t s) {
+  TO_CHECK(act_kind == ACT_KIND_LOGISTIC || act_kind == ACT_KIND_TANH, TO_ERR_UNSUPPORTED,
+           "online SGD kernel: hidden activation must be logistic or tanh");
   int G = 0, rpw = 0;
   size_t lds = 0;
   TO_CHECK(online_sgd_plan(dtype, L, dims, &G, &rpw, &lds), TO_ERR_UNSUPPORTED, "online SGD kernel: stack outside its range");
@@ -645,8 +647,13 @@ void launch_online_sgd(int dtype, int L, const int64_t* dims, void* const* W, vo
   }
   TO_HIP(hipMemsetAsync(g_on.counter, 0, 512, s));
   TO_HIP(hipMemsetAsync(g_on.exch, 0, need, s));  // (no tag of an earlier launch may pass for one of this launch)
-  if (dtype == TO_F64) launch_online_t<double>(L, dims, W, b, X, Y, idx_dev, n, rate, head, G, rpw, lds, s);
-  else launch_online_t<float>(L, dims, W, b, X, Y, idx_dev, n, rate, head, G, rpw, lds, s);
+  if (act_kind == ACT_KIND_TANH) {
+    if (dtype == TO_F64) launch_online_t<double, ACT_KIND_TANH>(L, dims, W, b, X, Y, idx_dev, n, rate, head, G, rpw, lds, s);
+    else launch_online_t<float, ACT_KIND_TANH>(L, dims, W, b, X, Y, idx_dev, n, rate, head, G, rpw, lds, s);
+  } else {
+    if (dtype == TO_F64) launch_online_t<double, ACT_KIND_LOGISTIC>(L, dims, W, b, X, Y, idx_dev, n, rate, head, G, rpw, lds, s);
+    else launch_online_t<float, ACT_KIND_LOGISTIC>(L, dims, W, b, X, Y, idx_dev, n, rate, head, G, rpw, lds, s);
+  }
   TO_HIP(hipGetLastError());
   count_launch();
 }

@@ -1,8 +1,10 @@
 // The recurrence of a `fullyConnected` layer (Recurrent.hs:91-119) over a whole sequence, for to_rnn_stack_*.  Everything
 // of BPTT that does not depend on time (input projections, heads, weight gradients, input cotangents) is one GEMM over all
 // B*T rows in api.cpp; what is left is a chain of T dependent [rows, H] x [H, H] products:
-//   forward  z_t  = P_t + s_{t-1} W'^T,  s_t = logistic(z_t)              (P_t: the input projection, z_t in place over it)
-//   reverse  dz_t = G_t + (dz_{t+1} W') (.) s_t (1 - s_t),  dz_T = 0     (G_t: the output-path cotangent, in place)
+//   forward  z_t  = P_t + s_{t-1} W'^T,  s_t = act(z_t)                   (P_t: the input projection, z_t in place over it)
+//   reverse  dz_t = G_t + (dz_{t+1} W') (.) act'(s_t),  dz_T = 0          (G_t: the output-path cotangent, in place)
+// act: the layer's state activation, a template parameter of the kernel (ACT_KIND_LOGISTIC: s (1 - s); ACT_KIND_TANH:
+// tanh, 1 - s^2 -- common.hpp).
 // Both are out_t[j] = epilogue(sum_k v_{t-1}[k] M[k][j]) with M = W'^T (forward, a transposed copy) or W' (reverse), so one
 // kernel serves both.  rnn_seq_kernel: ONE launch per layer and direction covers all T steps.  Each workgroup owns R
 // whole sequences (rows) and all H columns, so a step's new vector never leaves the workgroup: it is exchanged through
@@ -37,7 +39,7 @@ struct RnnSeqArgs {
   int H, R;
 };
 
-template <class S, bool REV, bool MLDS>
+template <class S, bool REV, bool MLDS, int ACT>
 __global__ __launch_bounds__(RNN_THREADS) void rnn_seq_kernel(RnnSeqArgs<S> a) {
   extern __shared__ __align__(16) unsigned char rnn_lds[];
   const int H = a.H, R = a.R;
@@ -86,11 +88,13 @@ __global__ __launch_bounds__(RNN_THREADS) void rnn_seq_kernel(RnnSeqArgs<S> a) {
         if (!REV) {
           const S z = pre[q] + acc;
           a.Z[off] = z;
-          o = sigm(z);
+          if constexpr (ACT == ACT_KIND_TANH) o = tanh_act(z);
+          else o = sigm(z);
           a.St[off + blk] = o;
         } else {
           const S h = a.St[off + blk];
-          o = fma_r(acc * h, S(1) - h, pre[q]);
+          if constexpr (ACT == ACT_KIND_TANH) o = fma_r(acc, tanh_dact(h), pre[q]);
+          else o = fma_r(acc * h, S(1) - h, pre[q]);
           a.Z[off] = o;
         }
         vn[item] = o;
@@ -103,16 +107,16 @@ __global__ __launch_bounds__(RNN_THREADS) void rnn_seq_kernel(RnnSeqArgs<S> a) {
   }
 }
 
-template <class S, bool REV, bool MLDS>
+template <class S, bool REV, bool MLDS, int ACT>
 void go(const RnnSeqPlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T, int64_t H, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_seq_kernel<S, REV, MLDS>),
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_seq_kernel<S, REV, MLDS, ACT>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)RNN_LDS_MAX));
     attr = true;
   }
   RnnSeqArgs<S> a{(const S*)M, (S*)Z, (S*)St, (long)B, (long)T, (int)H, p.R};
-  launch_k(rnn_seq_kernel<S, REV, MLDS>, dim3((unsigned)p.grid), dim3(RNN_THREADS), p.lds, s, a);
+  launch_k(rnn_seq_kernel<S, REV, MLDS, ACT>, dim3((unsigned)p.grid), dim3(RNN_THREADS), p.lds, s, a);
 }
 
 }  // namespace
@@ -134,15 +138,24 @@ bool rnn_seq_plan(int dtype, int64_t H, int64_t B, RnnSeqPlan* p) {
   return p->grid <= 2147483647LL;
 }
 
+template <class S, bool REV, bool MLDS>
+static void go_act(int act_kind, const RnnSeqPlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T, int64_t H,
+                   hipStream_t s) {
+  if (act_kind == ACT_KIND_TANH) go<S, REV, MLDS, ACT_KIND_TANH>(p, M, Z, St, B, T, H, s);
+  else go<S, REV, MLDS, ACT_KIND_LOGISTIC>(p, M, Z, St, B, T, H, s);
+}
+
 void launch_rnn_seq(int dtype, bool reverse, const RnnSeqPlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T,
-                    int64_t H, hipStream_t s) {
+                    int64_t H, int act_kind, hipStream_t s) {
   if (B == 0 || T == 0) return;
+  TO_CHECK(act_kind == ACT_KIND_LOGISTIC || act_kind == ACT_KIND_TANH, TO_ERR_ARG, "rnn_seq: unknown state activation");
+  const int k = act_kind;
   if (dtype == TO_F64) {
-    if (reverse) p.m_lds ? go<double, true, true>(p, M, Z, St, B, T, H, s) : go<double, true, false>(p, M, Z, St, B, T, H, s);
-    else p.m_lds ? go<double, false, true>(p, M, Z, St, B, T, H, s) : go<double, false, false>(p, M, Z, St, B, T, H, s);
+    if (reverse) p.m_lds ? go_act<double, true, true>(k, p, M, Z, St, B, T, H, s) : go_act<double, true, false>(k, p, M, Z, St, B, T, H, s);
+    else p.m_lds ? go_act<double, false, true>(k, p, M, Z, St, B, T, H, s) : go_act<double, false, false>(k, p, M, Z, St, B, T, H, s);
   } else {
-    if (reverse) p.m_lds ? go<float, true, true>(p, M, Z, St, B, T, H, s) : go<float, true, false>(p, M, Z, St, B, T, H, s);
-    else p.m_lds ? go<float, false, true>(p, M, Z, St, B, T, H, s) : go<float, false, false>(p, M, Z, St, B, T, H, s);
+    if (reverse) p.m_lds ? go_act<float, true, true>(k, p, M, Z, St, B, T, H, s) : go_act<float, true, false>(k, p, M, Z, St, B, T, H, s);
+    else p.m_lds ? go_act<float, false, true>(k, p, M, Z, St, B, T, H, s) : go_act<float, false, false>(k, p, M, Z, St, B, T, H, s);
   }
   TO_HIP(hipGetLastError());
   count_launch();

@@ -422,10 +422,44 @@ class HipT:
                                idx.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(h)))
         return DT(h)
 
-    def infer_stack(self, ws, bs, x, out_act="softmax", y=None, want_out=False, want_classes=True):
-        """`runNetwork` of a genNet stack (logistic hidden layers) over the batch of x, with `validate` / `confusion`'s
-        folds (to_fflayer_stack_infer): (out DT or None, classes int64[B] or None, confusion [n_L, n_L] indexed
-        [predicted, actual] or None -- given y only)."""
+    # hidden_act / a stateful layer's state activation: TO_ACT_LOGISTIC, TO_ACT_TANH
+    _HIDDEN = {"logistic": 0, "tanh": 3}
+
+    def stack_grad(self, ws, bs, x, y, out_act="softmax", loss="crossEntropy", hidden_act="logistic", want_losses=False):
+        """batched parameter gradients of a genNet stack (to_fflayer_stack_grad): (gW list, gb list, losses [B] or None)"""
+        gW = [self._alloc(w.shape, 0) for w in ws]
+        gB = [self._alloc(b.shape, 0) for b in bs]
+        losses = self._alloc((), x.batch) if want_losses else None
+        check(lib().to_fflayer_stack_grad(len(ws), _arr(ws), _arr(bs), self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
+                                          self._RNN_LOSS[loss], x.h, y.h, _arr(gW), _arr(gB),
+                                          losses.h if losses is not None else None))
+        return gW, gB, losses
+
+    def stack_sgd(self, ws, bs, x, y, rate, out_act="softmax", loss="crossEntropy", hidden_act="logistic",
+                  want_losses=False):
+        """the `trainNetwork` step on one batch, parameters updated in place (to_fflayer_stack_sgd)"""
+        losses = self._alloc((), x.batch) if want_losses else None
+        check(lib().to_fflayer_stack_sgd(len(ws), _arr(ws), _arr(bs), self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
+                                         self._RNN_LOSS[loss], x.h, y.h, float(rate),
+                                         losses.h if losses is not None else None))
+        return losses
+
+    def stack_online_sgd(self, ws, bs, X, Y, n, rate, idx=None, out_act="softmax", loss="crossEntropy",
+                         hidden_act="logistic"):
+        """per-sample SGD over rows idx[0..n) (None: rows 0..n-1) of X / Y in one launch, parameters updated in place
+        (to_fflayer_stack_online_sgd)"""
+        arr = None
+        if idx is not None:
+            arr = np.ascontiguousarray(idx, dtype=np.int64)
+        check(lib().to_fflayer_stack_online_sgd(len(ws), _arr(ws), _arr(bs), self._HIDDEN[hidden_act],
+                                                self._RNN_OUT[out_act], self._RNN_LOSS[loss], X.h, Y.h, int(n),
+                                                arr.ctypes.data_as(C.POINTER(C.c_int64)) if arr is not None else None,
+                                                float(rate)))
+
+    def infer_stack(self, ws, bs, x, out_act="softmax", y=None, want_out=False, want_classes=True, hidden_act="logistic"):
+        """`runNetwork` of a genNet stack (logistic or tanh hidden layers) over the batch of x, with `validate` /
+        `confusion`'s folds (to_fflayer_stack_infer): (out DT or None, classes int64[B] or None, confusion [n_L, n_L]
+        indexed [predicted, actual] or None -- given y only)."""
         act = {"softmax": 2, "logistic": 0}[out_act]
         shape, batch = x._shape()
         rows = max(batch, 1)
@@ -439,7 +473,7 @@ class HipT:
         classes = np.empty(rows, dtype=np.int64) if want_classes else None
         conf = np.zeros((nL, nL), dtype=np.int64) if y is not None else None
         i64 = C.POINTER(C.c_int64)
-        check(lib().to_fflayer_stack_infer(len(ws), _arr(ws), _arr(bs), 0, act, x.h, y.h if y is not None else None,
+        check(lib().to_fflayer_stack_infer(len(ws), _arr(ws), _arr(bs), self._HIDDEN[hidden_act], act, x.h, y.h if y is not None else None,
                                            out.h if out is not None else None,
                                            classes.ctypes.data_as(i64) if classes is not None else None,
                                            conf.ctypes.data_as(i64) if conf is not None else None))
@@ -455,15 +489,27 @@ class HipT:
         check(lib().to_alloc(self.to_dtype, r, d, batch, C.byref(h)))
         return DT(h)
 
-    @staticmethod
-    def _rnn_arrays(layers):
-        """layers: [(s, W', W, b)] in input-to-output order; s = W' = None for a stateless ffLayer"""
+    @classmethod
+    def _rnn_arrays(cls, layers):
+        """layers: [(s, W', W, b)] or [(s, W', W, b, state_act)] in input-to-output order; s = W' = None for a stateless
+        ffLayer.  state_act of a stateful layer: "logistic" (the default; also True) or "tanh"."""
         n = len(layers)
-        sact = (C.c_int * n)(*[0 if s is not None else -1 for s, _, _, _ in layers])
-        col = [(capi.c_tensor * n)(*[(t.h if t is not None else None) for t in ts]) for ts in zip(*layers)]
+        kinds = []
+        for lay in layers:
+            sa = lay[4] if len(lay) > 4 else True
+            if lay[0] is None:
+                if sa not in (True, False, None):
+                    raise ValueError("a stateless layer has no state activation")
+                kinds.append(-1)
+            else:
+                if sa in (False, None):
+                    raise ValueError("a layer with a state needs a state activation")
+                kinds.append(cls._HIDDEN["logistic" if sa is True else sa])
+        sact = (C.c_int * n)(*kinds)
+        col = [(capi.c_tensor * n)(*[(t.h if t is not None else None) for t in ts]) for ts in zip(*[lay[:4] for lay in layers])]
         return n, sact, col
 
-    def rnn_stack_run(self, layers, X, out_act="softmax", want_states=False):
+    def rnn_stack_run(self, layers, X, out_act="softmax", want_states=False, hidden_act="logistic"):
         """`runNetwork` threaded over the T steps of X [B; T, i] (to_rnn_stack_run): (out [B; T, n_L], final states --
         one per layer, None for a stateless one -- or None)"""
         n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
@@ -472,10 +518,11 @@ class HipT:
         out = self._alloc((T, layers[-1][2].shape[0]), batch)
         finals = [self._alloc((lay[2].shape[0],), batch) if (want_states and lay[0] is not None) else None for lay in layers]
         s_out = (capi.c_tensor * n)(*[(f.h if f is not None else None) for f in finals]) if want_states else None
-        check(lib().to_rnn_stack_run(n, sact, s, ws, w, b, 0, self._RNN_OUT[out_act], X.h, out.h, s_out))
+        check(lib().to_rnn_stack_run(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act], X.h, out.h, s_out))
         return out, (finals if want_states else None)
 
-    def rnn_stack_grad(self, layers, X, Y, out_act="softmax", loss="crossEntropy", want_gx=False, want_losses=False):
+    def rnn_stack_grad(self, layers, X, Y, out_act="softmax", loss="crossEntropy", want_gx=False, want_losses=False,
+                       hidden_act="logistic"):
         """BPTT of the stack summed over the sequences of X (to_rnn_stack_grad): (gs, gws, gw, gb -- lists per layer, None
         for a stateless layer's state entries --, gx [B; T, i] or None, losses [B; T] or None)"""
         n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
@@ -487,17 +534,19 @@ class HipT:
         gx = self._alloc((T, i), X.batch) if want_gx else None
         losses = self._alloc((T,), X.batch) if want_losses else None
         arr = lambda ts: (capi.c_tensor * n)(*[(t.h if t is not None else None) for t in ts])  # noqa: E731
-        check(lib().to_rnn_stack_grad(n, sact, s, ws, w, b, 0, self._RNN_OUT[out_act], self._RNN_LOSS[loss], X.h, Y.h,
+        check(lib().to_rnn_stack_grad(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
+                                      self._RNN_LOSS[loss], X.h, Y.h,
                                       arr(gS), arr(gWS), arr(gW), arr(gB), gx.h if gx is not None else None,
                                       losses.h if losses is not None else None))
         return gS, gWS, gW, gB, gx, losses
 
     def rnn_stack_sgd(self, layers, X, Y, rate_state, rate_params, out_act="softmax", loss="crossEntropy",
-                      want_losses=False):
+                      want_losses=False, hidden_act="logistic"):
         """`trainNetwork'` in place (to_rnn_stack_sgd); the per-(sequence, step) losses if asked for"""
         n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
         losses = self._alloc((X.shape[0],), X.batch) if want_losses else None
-        check(lib().to_rnn_stack_sgd(n, sact, s, ws, w, b, 0, self._RNN_OUT[out_act], self._RNN_LOSS[loss], X.h, Y.h,
+        check(lib().to_rnn_stack_sgd(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
+                                     self._RNN_LOSS[loss], X.h, Y.h,
                                      float(rate_state), float(rate_params), losses.h if losses is not None else None))
         return losses
 
@@ -516,14 +565,15 @@ class HipT:
 
     # -- induceNetwork iterated (to_fflayer_stack_induce) ----------------------------------------
     def induce_stack(self, ws, bs, x, y, rate, iters, out_act="softmax", loss="crossEntropy", want_gx=False,
-                     want_losses=False, in_place=False):
+                     want_losses=False, in_place=False, hidden_act="logistic"):
         """`induceNetwork` applied `iters` times to every row of x with the parameters fixed (to_fflayer_stack_induce):
         (out -- x itself when in_place --, gx of the last iteration or None, losses [B; iters] or None)"""
         shape, batch = x._shape()
         out = x if in_place else self._alloc(shape, batch)
         gx = self._alloc(shape, batch) if want_gx else None
         losses = self._alloc((iters,), batch) if want_losses else None
-        check(lib().to_fflayer_stack_induce(len(ws), _arr(ws), _arr(bs), 0, self._RNN_OUT[out_act], self._RNN_LOSS[loss],
+        check(lib().to_fflayer_stack_induce(len(ws), _arr(ws), _arr(bs), self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
+                                            self._RNN_LOSS[loss],
                                             x.h, y.h, float(rate), int(iters), out.h,
                                             gx.h if gx is not None else None, losses.h if losses is not None else None))
         return out, gx, losses

@@ -1,11 +1,11 @@
 // extern "C" entry points (include/tensorops_hip.h) and the host-side planning
 // that turns `class Tensor` / `class BLAS` calls into kernel launches.
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <map>
 
-#include "ops.hpp"
+#include "api_util.hpp"
+#include "stack_util.hpp"
 
 struct to_graph_s {
   hipGraph_t graph = nullptr;
@@ -19,7 +19,7 @@ struct to_graph_s {
 
 namespace to {
 
-static thread_local std::string g_err;
+thread_local std::string g_err;
 static std::vector<std::unique_ptr<LaunchRec>> g_capture_launches;  // of the capture in progress
 static std::vector<StepDesc> g_capture_desc;
 
@@ -99,8 +99,7 @@ bool gemm_small_route(const GemmProblem& p) {
   // (a few tiles under a very long K -- a weight gradient over a data set, 300 x 60000 x 784: one workgroup a tile here whatever K
   //  is, 400 us; 291 split over workgroups in gemm_kwave.hip, which carries alpha / beta C / bias / activation but no row sums)
   if (p.K >= 8192 && !p.rowsum && !p.loss_rows && !p.tail_out && gemm_kw_long_k(p)) return false;
-  const int64_t t64 = ((p.M + 63) / 64) * ((p.N + 63) / 64);
-  return gemm_small_applicable(p) || (t64 < 200 && gemm_small_can(p));
+  return gemm_small_takes(p);
 }
 
 // The fused elementwise epilogue (alpha, beta*Cin, bias, act, dact) exists in the small-GEMM kernel (both element
@@ -723,18 +722,7 @@ static void check_dtype(int dtype) { TO_CHECK(dtype == TO_F32 || dtype == TO_F64
 
 using namespace to;
 
-// HIP's current device is per OS thread and to_init selects it on the initialising thread only: a Haskell
-// capability (or any second thread) calling in would otherwise allocate and load modules on device 0.
-static void bind_device() {
-  static thread_local int bound = -1;
-  to::Runtime& r = to::rt();
-  if (r.inited && bound != r.device) {
-    (void)hipSetDevice(r.device);
-    bound = r.device;
-  }
-}
-
-// host time spent inside the library's entry points (to_api_time): what a host's own per-step cost is NOT
+// the entry clock's totals (ApiClock, api_util.hpp)
 static int64_t g_api_calls = 0;
 // TOPS_API_COUNT=1: calls and nanoseconds per entry point, printed when the process exits (diagnostic)
 static std::map<std::string, std::pair<int64_t, int64_t>>& api_counts() {
@@ -755,22 +743,6 @@ static bool api_count_on() {
   }();
   return on;
 }
-// (the time-stamp counter, not clock_gettime: two calls of the latter per entry point were 2 us of a 40 us step)
-// (x86-64: an invariant TSC, synchronised across cores, is assumed -- every x86 server part of the last decade; elsewhere the
-//  compiler's cycle counter where it has one (aarch64: cntvct), else the steady clock.  Calibrated once against steady_clock.)
-#if defined(__x86_64__) || defined(__i386__)
-static inline uint64_t api_ticks() { return __builtin_ia32_rdtsc(); }
-#elif defined(__aarch64__)
-static inline uint64_t api_ticks() {
-  uint64_t v;
-  asm volatile("mrs %0, cntvct_el0" : "=r"(v));
-  return v;
-}
-#else
-static inline uint64_t api_ticks() {
-  return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-#endif
 static double api_ns_per_tick() {
   static const double v = [] {
     const auto c0 = std::chrono::steady_clock::now();
@@ -783,46 +755,16 @@ static double api_ns_per_tick() {
   return v;
 }
 static uint64_t g_api_ticks = 0;
-struct ApiClock {
-  const char* fn;
-  uint64_t t0 = api_ticks();
-  explicit ApiClock(const char* f) : fn(f) {}
-  ~ApiClock() {
-    const uint64_t dt = api_ticks() - t0;
-    g_api_ticks += dt;
-    ++g_api_calls;
-    if (api_count_on()) {
-      auto& c = api_counts()[fn];
-      c.first++;
-      c.second += (int64_t)((double)dt * api_ns_per_tick());
-    }
+ApiClock::~ApiClock() {
+  const uint64_t dt = api_ticks() - t0;
+  g_api_ticks += dt;
+  ++g_api_calls;
+  if (api_count_on()) {
+    auto& c = api_counts()[fn];
+    c.first++;
+    c.second += (int64_t)((double)dt * api_ns_per_tick());
   }
-};
-
-#define API_BEGIN                                          \
-  std::lock_guard<std::recursive_mutex> guard_(to::lock()); \
-  ApiClock clock_(__func__);                                \
-  bind_device();                                            \
-  try {
-#define API_END                          \
-  return TO_OK;                          \
-  }                                      \
-  catch (const to::Error& e) {           \
-    to::g_err = e.what();                \
-    return e.code;                       \
-  }                                      \
-  catch (const std::exception& e) {      \
-    to::g_err = e.what();                \
-    return TO_ERR_ARG;                   \
-  }
-// like API_END but falls through on success
-#define API_END_CHECK                    \
-  }                                      \
-  catch (const to::Error& e) {           \
-    to::g_err = e.what();                \
-    return e.code;                       \
-  }
-#define NONNULL(p) TO_CHECK((p) != nullptr, TO_ERR_ARG, "null argument: " #p)
+}
 
 extern "C" {
 
@@ -2166,1124 +2108,6 @@ to_status to_copy_into_many(int n, const to_tensor* dsts, const to_tensor* srcs)
   API_END
 }
 
-// GEMM with fused epilogue on packed row-major operands: C[M,N] = A.B (+bias, act, dact)
-// returns true when `rowsum` (sum_k A[m,k]) was produced by the same launch
-struct LossHead {  // loss gradient fused into the last layer's GEMM epilogue when the kernel can
-  int kind = 0;    // GemmProblem::loss_rows
-  const void* target = nullptr;
-  void* loss_out = nullptr;
-  bool done = false;  // set when the launch produced dz instead of z
-  // optional fused tail (GemmProblem::tail_*): the previous layer's cotangent for the same rows
-  const void* tail_w = nullptr;
-  const void* tail_h = nullptr;
-  void* tail_out = nullptr;
-  int tail_n = 0;
-  int tail_kind = 0;  // GemmProblem::tail_kind
-  bool tail_done = false;
-};
-static bool fused_gemm(int dtype, const void* A, int64_t a_sm, int64_t a_sk, const void* B, int64_t b_sk,
-                       int64_t b_sn, void* C, int64_t M, int64_t N, int64_t K, const void* bias,
-                       int act, const void* dact, void* rowsum = nullptr, hipStream_t stream = nullptr,
-                       LossHead* head = nullptr, int dact_kind = 0) {
-  GemmProblem p{};
-  p.dtype = dtype;
-  p.A = A; p.B = B; p.C = C;
-  p.M = M; p.N = N; p.K = K;
-  p.a_sm = a_sm; p.a_sk = a_sk; p.b_sk = b_sk; p.b_sn = b_sn; p.c_sm = N;
-  p.batch = 1;
-  p.alpha = 1.0; p.beta = 0.0;
-  p.bias = bias; p.act = act; p.dact = dact; p.dact_kind = dact_kind;
-  hipStream_t st = stream ? stream : S();
-  // latency-bound shapes (incl. the tiny ones of a one-sample step) run on the small-GEMM kernel: it carries
-  // every fused epilogue for both element types (the tiled fp64 kernel has none)
-  const int64_t t64 = ((M + 63) / 64) * ((N + 63) / 64);
-  if (gemm_small_applicable(p) || (t64 < 200 && gemm_small_can(p))) {
-    p.rowsum = rowsum;
-    if (head && gemm_small_fuses_loss(p)) {
-      p.loss_rows = head->kind; p.target = head->target; p.loss_out = head->loss_out;
-      if (head->tail_out && gemm_small_fuses_tail(p, head->tail_n)) {
-        p.tail_w = head->tail_w; p.tail_h = head->tail_h; p.tail_out = head->tail_out; p.tail_n = head->tail_n;
-        p.tail_kind = head->tail_kind;
-        head->tail_done = true;
-      }
-      head->done = true;
-    }
-    launch_gemm_small(p, st);
-    return rowsum != nullptr;
-  }
-  // the tiled fp64 kernel has no fused epilogue: the caller (the trainer) falls back to the generic path
-  TO_CHECK(dtype == TO_F32, TO_ERR_UNSUPPORTED, "pre-fused fp64 path: a contraction is outside the small-GEMM range");
-  launch_gemm_mfma(p, st);
-  return false;
-}
-
-// The checks the ffLayer stack entry points share.  Hidden layers: logistic or tanh.  Returns the activation numbered as
-// the kernels number it (ACT_KIND_*: GemmProblem::dact_kind / tail_kind, the persistent kernels' template parameter;
-// GemmProblem::act is this + 1).
-static int stack_hidden_act_check(int hidden_act) {
-  TO_CHECK(hidden_act == TO_ACT_LOGISTIC || hidden_act == TO_ACT_TANH, TO_ERR_UNSUPPORTED,
-           "fused path: hidden activation must be logistic or tanh");
-  return hidden_act == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC;
-}
-
-// Every layer's W [n_l, n_{l-1}] and b [n_l]: unbatched, contiguous, of the data's dtype, chained from `fan_in`; gradient
-// destinations (gw / gb null: none) of the parameters' shapes.  Returns n_L.
-static int64_t stack_params_check(int n_layers, const to_tensor* w, const to_tensor* b, const to_tensor* gw,
-                                  const to_tensor* gb, int dt, int64_t fan_in) {
-  for (int l = 0; l < n_layers; ++l) {
-    NONNULL(w[l]); NONNULL(b[l]);
-    if (gw) { NONNULL(gw[l]); NONNULL(gb[l]); }
-    TO_CHECK(w[l]->dtype == dt && b[l]->dtype == dt && (!gw || (gw[l]->dtype == dt && gb[l]->dtype == dt)), TO_ERR_ARG,
-             gw ? "parameters, gradients and data must share one dtype" : "parameters and data must share one dtype");
-    TO_CHECK(w[l]->rank == 2 && w[l]->batch == 0 && w[l]->dims[1] == fan_in && w[l]->contiguous(),
-             TO_ERR_SHAPE, "layer " + std::to_string(l) + ": W has shape " + shape_str(w[l]));
-    TO_CHECK(b[l]->rank == 1 && b[l]->batch == 0 && b[l]->dims[0] == w[l]->dims[0] && b[l]->contiguous(),
-             TO_ERR_SHAPE, "layer " + std::to_string(l) + ": b has shape " + shape_str(b[l]));
-    if (gw)
-      TO_CHECK(same_shape(gw[l], w[l]) && gw[l]->contiguous() && same_shape(gb[l], b[l]) && gb[l]->contiguous(),
-               TO_ERR_SHAPE, "gradient destinations must match the parameters");
-    fan_in = w[l]->dims[0];
-  }
-  return fan_in;
-}
-
-// sgd: gw/gb are the parameters themselves and the weight-gradient launches apply
-// P <- P - rate * gradient in their epilogue (alpha = -rate, beta = 1, Cin = C = W; the bias through the
-// accumulating row sum): the step loses its separate update launch.
-static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
-                               int loss, to_tensor x, to_tensor y, const to_tensor* gw, const to_tensor* gb,
-                               to_tensor losses, bool sgd, double rate) {
-  require_init();
-  NONNULL(w); NONNULL(b); NONNULL(x); NONNULL(y); NONNULL(gw); NONNULL(gb);
-  TO_CHECK(n_layers >= 1, TO_ERR_ARG, "need at least one layer");
-  ensure(x);
-  ensure(y);
-  if (losses) { ensure(losses); before_write(losses); }
-  for (int l = 0; l < n_layers; ++l) {
-    NONNULL(w[l]); NONNULL(b[l]); NONNULL(gw[l]); NONNULL(gb[l]);
-    ensure(w[l]); ensure(b[l]); ensure(gw[l]); ensure(gb[l]);
-    before_write(gw[l]);
-    before_write(gb[l]);
-    if (sgd) { w[l]->id = fresh_id(); b[l]->id = fresh_id(); }
-  }
-  const int hk = stack_hidden_act_check(hidden_act);
-  const bool sm_ce = out_act == TO_ACT_SOFTMAX && loss == TO_LOSS_CROSS_ENTROPY;
-  const bool lg_se = out_act == TO_ACT_LOGISTIC && loss == TO_LOSS_SQUARED_ERROR;
-  TO_CHECK(sm_ce || lg_se, TO_ERR_UNSUPPORTED,
-           "fused path: (softmax, crossEntropy) or (logistic, squaredError) only");
-  TO_CHECK(x->rank == 1 && y->rank == 1 && x->batch > 0 && x->batch == y->batch, TO_ERR_SHAPE,
-           "x and y must be batched vectors with the same batch, got " + shape_str(x) + " " + shape_str(y));
-  TO_CHECK(x->contiguous() && y->contiguous(), TO_ERR_ARG, "x and y must be contiguous");
-  const int dt = x->dtype;
-  TO_CHECK(y->dtype == dt, TO_ERR_ARG, "x and y have different dtypes");
-  const int64_t B = x->batch;
-  const int64_t fan_in = stack_params_check(n_layers, w, b, gw, gb, dt, x->dims[0]);
-  TO_CHECK(y->dims[0] == fan_in, TO_ERR_SHAPE, "y does not match the output layer");
-  if (losses) TO_CHECK(losses->rank == 0 && losses->batch == B && losses->contiguous(), TO_ERR_SHAPE,
-                       "losses must be a batched scalar");
-
-  if (sgd)  // nothing may be half-updated: every weight gradient must be one small-GEMM launch
-    for (int l = 0; l < n_layers; ++l) {
-      GemmProblem q{};
-      q.dtype = dt;
-      q.M = w[l]->dims[0]; q.N = w[l]->dims[1]; q.K = B;
-      q.a_sm = 1; q.a_sk = q.M; q.b_sk = q.N; q.b_sn = 1; q.c_sm = q.N;
-      q.batch = 1;
-      const int64_t t64 = ((q.M + 63) / 64) * ((q.N + 63) / 64);
-      TO_CHECK(gemm_small_applicable(q) || (t64 < 200 && gemm_small_can(q)), TO_ERR_UNSUPPORTED,
-               "fused SGD step: a weight gradient is outside the small-GEMM range");
-    }
-  static const int fuse_tail = [] { const char* e = ab_getenv("TOPS_STEP_FUSE_TAIL"); return e ? atoi(e) : 1; }();
-  Holder tail;  // dz_{L-1} when the last layer's launch produced it
-  LossHead head;
-  head.kind = sm_ce ? 1 : 2;
-  head.target = y->ptr;
-  head.loss_out = losses ? losses->ptr : nullptr;
-  // forward: a_l = act(a_{l-1} W_l^T + b_l) for hidden layers (act: hidden_act), z_L for the last
-  std::vector<Holder> act(n_layers);  // act[l]: [B; n_l]; the last holds z_L, then is reused as dz_L
-  const void* prev = x->ptr;
-  int64_t prev_n = x->dims[0];
-  for (int l = 0; l < n_layers; ++l) {
-    const int64_t n = w[l]->dims[0];
-    act[l].t = new_tensor(1, &n, B, dt);
-    // C[B,n] = A[B,prev_n] . W^T : B operand element (k, j) = W[j*prev_n + k]
-    // (last layer: the loss head runs in the same launch when the row fits one 16-wide tile)
-    const bool last = l + 1 == n_layers;
-    if (last && n_layers >= 2 && fuse_tail) {
-      // the loss-head launch also produces dz_{L-1} = (dz_L . W_L) * act'(h) for its rows
-      tail.t = new_tensor(1, &prev_n, B, dt);
-      head.tail_w = w[l]->ptr;
-      head.tail_h = act[l - 1].t->ptr;
-      head.tail_out = tail.t->ptr;
-      head.tail_n = (int)prev_n;
-      head.tail_kind = hk;
-    }
-    fused_gemm(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, act[l].t->ptr, B, n, prev_n, b[l]->ptr,
-               last ? 0 : hk + 1, nullptr, nullptr, nullptr, last ? &head : nullptr);
-    prev = act[l].t->ptr;
-    prev_n = n;
-  }
-  // loss gradient wrt z_L, per sample row
-  const int64_t nL = w[n_layers - 1]->dims[0];
-  Holder cur;
-  if (head.done) {
-    cur.t = act[n_layers - 1].t;  // already dz_L
-    act[n_layers - 1].t = nullptr;
-  } else {
-    cur.t = new_tensor(1, &nL, B, dt);
-    launch_loss_grad_rows(dt, act[n_layers - 1].t->ptr, y->ptr, cur.t->ptr, losses ? losses->ptr : nullptr, B, nL,
-                          sm_ce ? 0 : 1, S());
-  }
-  // The weight gradient of layer l (dz_l^T . a_in, + its row sums = the bias gradient) as a GEMM problem:
-  // A element (i,k) = dz[k*n + i], B element (k,j) = a_in[k*m + j]
-  auto wgrad = [&](int l, const void* dz) {
-    GemmProblem p{};
-    const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
-    p.dtype = dt;
-    p.A = dz; p.B = l > 0 ? act[l - 1].t->ptr : x->ptr; p.C = gw[l]->ptr;
-    p.M = n; p.N = m; p.K = B;
-    p.a_sm = 1; p.a_sk = n; p.b_sk = m; p.b_sn = 1; p.c_sm = m;
-    p.batch = 1;
-    p.alpha = 1.0; p.beta = 0.0;
-    p.rowsum = gb[l]->ptr;
-    if (sgd) {
-      p.alpha = -rate; p.beta = 1.0; p.Cin = w[l]->ptr;
-      p.rowsum_acc = true; p.rowsum_alpha = -rate;
-    }
-    return p;
-  };
-  // backward, phase 1: every dz_l (the propagation reads W_l, which phase 2 may overwrite in place)
-  // dz_{l-1}[B,m] = (dz_l[B,n] . W_l[n,m]) * act'(h), h = act[l-1]  (h (1 - h), or 1 - h h for tanh)
-  std::vector<Holder> dz(n_layers);
-  dz[n_layers - 1].t = cur.take();
-  for (int l = n_layers - 1; l > 0; --l) {
-    const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
-    if (l == n_layers - 1 && head.tail_done && tail.t) {
-      dz[l - 1].t = tail.take();  // came out of the loss-head launch
-    } else {
-      dz[l - 1].t = new_tensor(1, &m, B, dt);
-      fused_gemm(dt, dz[l].t->ptr, n, 1, w[l]->ptr, m, 1, dz[l - 1].t->ptr, B, m, n, nullptr, 0, act[l - 1].t->ptr, nullptr,
-                 nullptr, nullptr, hk);
-    }
-  }
-  // phase 2: the weight gradients, independent of each other.  The two last ones go out as ONE launch when
-  // their shapes allow (one launch floor, ~4 us, less per step: 33.6 -> 28.0 us on config 3).
-  // (Running them on a side stream instead measured slower: the fork/join events cost more than the overlap
-  // buys, 0.0485 -> 0.0591 ms/step.)
-  // one sample: every weight gradient is an outer product -- all layers in one launch
-  static const int rank1 = [] { const char* e = ab_getenv("TOPS_STEP_RANK1"); return e ? atoi(e) : 1; }();
-  if (B == 1 && rank1) {
-    for (int l0 = 0; l0 < n_layers; l0 += RANK1_MAX_LAYERS) {
-      const int cnt = std::min(RANK1_MAX_LAYERS, n_layers - l0);
-      const void *dzp[RANK1_MAX_LAYERS], *ap[RANK1_MAX_LAYERS];
-      void *wp[RANK1_MAX_LAYERS], *bp[RANK1_MAX_LAYERS];
-      int64_t rows[RANK1_MAX_LAYERS], cols[RANK1_MAX_LAYERS];
-      for (int q = 0; q < cnt; ++q) {
-        const int l = l0 + q;
-        dzp[q] = dz[l].t->ptr;
-        ap[q] = l > 0 ? act[l - 1].t->ptr : x->ptr;
-        wp[q] = gw[l]->ptr;
-        bp[q] = gb[l]->ptr;
-        rows[q] = w[l]->dims[0];
-        cols[q] = w[l]->dims[1];
-      }
-      launch_rank1_many(dt, cnt, dzp, ap, wp, bp, rows, cols, sgd ? -rate : 1.0, sgd, S());
-    }
-    return;
-  }
-  int first = n_layers - 1;
-  if (n_layers >= 2 &&
-      launch_gemm_small_pair(wgrad(n_layers - 2, dz[n_layers - 2].t->ptr), wgrad(n_layers - 1, dz[n_layers - 1].t->ptr), S()))
-    first = n_layers - 3;
-  for (int l = first; l >= 0; --l) {
-    const GemmProblem p = wgrad(l, dz[l].t->ptr);
-    const int64_t t64 = ((p.M + 63) / 64) * ((p.N + 63) / 64);
-    if (gemm_small_applicable(p) || (t64 < 200 && gemm_small_can(p))) {
-      launch_gemm_small(p, S());
-      continue;
-    }
-    TO_CHECK(!sgd, TO_ERR_UNSUPPORTED, "fused SGD step: a weight gradient is outside the small-GEMM range");
-    TO_CHECK(dt == TO_F32, TO_ERR_UNSUPPORTED, "pre-fused fp64 path: a contraction is outside the small-GEMM range");
-    GemmProblem q = p;
-    q.rowsum = nullptr;
-    launch_gemm_mfma(q, S());
-    launch_sum_axis(dt, dz[l].t->ptr, gb[l]->ptr, 1, B, w[l]->dims[0], 0, w[l]->dims[0], 1, S());
-  }
-}
-
-to_status to_fflayer_stack_grad(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act,
-                                int out_act, int loss, to_tensor x, to_tensor y, const to_tensor* gw,
-                                const to_tensor* gb, to_tensor losses) {
-  API_BEGIN
-  fflayer_stack_impl(n_layers, w, b, hidden_act, out_act, loss, x, y, gw, gb, losses, false, 0.0);
-  API_END
-}
-
-to_status to_fflayer_stack_sgd(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
-                               int loss, to_tensor x, to_tensor y, double rate, to_tensor losses) {
-  API_BEGIN
-  fflayer_stack_impl(n_layers, w, b, hidden_act, out_act, loss, x, y, w, b, losses, true, rate);
-  API_END
-}
-
-// `foldl' trainNetwork` over samples (app/MNIST.hs:390-396) of an ffLayer stack as ONE persistent launch.
-static void online_sgd_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss,
-                            to_tensor X, to_tensor Y, int64_t n_idx, const int64_t* idx, double rate) {
-  require_init();
-  no_capture("to_fflayer_stack_online_sgd");
-  NONNULL(w); NONNULL(b); NONNULL(X); NONNULL(Y);
-  TO_CHECK(n_layers >= 2 && n_layers <= 6, TO_ERR_UNSUPPORTED, "online SGD kernel: 2..6 layers");
-  TO_CHECK(hidden_act == TO_ACT_LOGISTIC || hidden_act == TO_ACT_TANH, TO_ERR_UNSUPPORTED,
-           "online SGD kernel: hidden activation must be logistic or tanh");
-  const bool sm_ce = out_act == TO_ACT_SOFTMAX && loss == TO_LOSS_CROSS_ENTROPY;
-  const bool lg_se = out_act == TO_ACT_LOGISTIC && loss == TO_LOSS_SQUARED_ERROR;
-  TO_CHECK(sm_ce || lg_se, TO_ERR_UNSUPPORTED, "online SGD kernel: (softmax, crossEntropy) or (logistic, squaredError) only");
-  ensure(X);
-  ensure(Y);
-  TO_CHECK(X->rank == 1 && Y->rank == 1 && X->batch > 0 && X->batch == Y->batch && X->contiguous() && Y->contiguous(),
-           TO_ERR_SHAPE, "X and Y must be contiguous batched vectors of one batch, got " + shape_str(X) + " " + shape_str(Y));
-  const int dt = X->dtype;
-  TO_CHECK(Y->dtype == dt, TO_ERR_ARG, "X and Y have different dtypes");
-  TO_CHECK(n_idx >= 0, TO_ERR_ARG, "negative sample count");
-  int64_t dims[8];
-  dims[0] = X->dims[0];
-  void *wp[6], *bp[6];
-  for (int l = 0; l < n_layers; ++l) {
-    NONNULL(w[l]); NONNULL(b[l]);
-    ensure(w[l]);
-    ensure(b[l]);
-    TO_CHECK(w[l]->dtype == dt && b[l]->dtype == dt, TO_ERR_ARG, "parameters and data must share one dtype");
-    TO_CHECK(w[l]->rank == 2 && w[l]->batch == 0 && w[l]->dims[1] == dims[l] && w[l]->contiguous(), TO_ERR_SHAPE,
-             "layer " + std::to_string(l) + ": W has shape " + shape_str(w[l]));
-    TO_CHECK(b[l]->rank == 1 && b[l]->batch == 0 && b[l]->dims[0] == w[l]->dims[0] && b[l]->contiguous(), TO_ERR_SHAPE,
-             "layer " + std::to_string(l) + ": b has shape " + shape_str(b[l]));
-    dims[l + 1] = w[l]->dims[0];
-  }
-  TO_CHECK(Y->dims[0] == dims[n_layers], TO_ERR_SHAPE, "Y does not match the output layer");
-  int G = 0, rpw = 0;
-  size_t lds = 0;
-  TO_CHECK(online_sgd_plan(dt, n_layers, dims, &G, &rpw, &lds), TO_ERR_UNSUPPORTED,
-           "online SGD kernel: the stack does not fit (input <= 2048, head <= 64 outputs, 160 KiB of LDS per workgroup)");
-  for (int64_t k = 0; k < n_idx; ++k)
-    TO_CHECK(!idx || (idx[k] >= 0 && idx[k] < X->batch), TO_ERR_SHAPE, "sample index out of range");
-  TO_CHECK(idx || n_idx <= X->batch, TO_ERR_SHAPE, "more samples than rows");
-  for (int l = 0; l < n_layers; ++l) {  // in-place writes: recorded readers of the old values first, new identities after
-    before_write(w[l]);
-    before_write(b[l]);
-    w[l]->id = fresh_id();
-    b[l]->id = fresh_id();
-    wp[l] = w[l]->ptr;
-    bp[l] = b[l]->ptr;
-  }
-  if (n_idx == 0) return;
-  Holder order;
-  const long long* idx_dev = nullptr;
-  if (idx) {
-    const int64_t nl = (n_idx * 8 + 3) / 4;
-    order.t = new_tensor(1, &nl, 0);
-    host_to_device(order.t->ptr, idx, (size_t)n_idx * sizeof(int64_t), S());
-    idx_dev = static_cast<const long long*>(order.t->ptr);
-  }
-  online_sgd_reset_status();
-  launch_online_sgd(dt, n_layers, dims, wp, bp, X->ptr, Y->ptr, idx_dev, n_idx, rate, sm_ce ? 1 : 2,
-                    hidden_act == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC, S());
-  TO_HIP(hipStreamSynchronize(S()));  // the order buffer goes back to the pool; the watchdog's verdict is read
-  TO_CHECK(online_sgd_status() == 0, TO_ERR_HIP,
-           "online SGD kernel: a workgroup barrier timed out at sample " + std::to_string(online_sgd_status() - 1) +
-               " (the write-back is all-or-nothing: commit or abort is ONE word decided by compare-and-swap and obeyed by every workgroup; this run aborted, the parameters are unchanged)");
-}
-
-to_status to_fflayer_stack_online_sgd(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
-                                      int loss, to_tensor X, to_tensor Y, int64_t n_idx, const int64_t* idx_or_null,
-                                      double rate) {
-  API_BEGIN
-  online_sgd_impl(n_layers, w, b, hidden_act, out_act, loss, X, Y, n_idx, idx_or_null, rate);
-  API_END
-}
-
-// `runNetwork` (FeedForward.hs:123-129) of an ffLayer stack over a batch and the folds of `validate` / `confusion`
-// (app/MNIST.hs:366-389).  Hidden layers: one GEMM each, bias + activation (logistic / tanh) in its epilogue where the kernel carries one,
-// else a plain GEMM and one elementwise launch.  The head (infer_head.hip): n_L <= 32 the last layer's contraction and
-// everything after it in one launch; wider, the last GEMM into scratch (or `out` itself) and one row launch.
-static void fflayer_stack_infer_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
-                                     to_tensor x, to_tensor y, to_tensor out, int64_t* classes, int64_t* confusion) {
-  require_init();
-  no_capture("to_fflayer_stack_infer");
-  NONNULL(w); NONNULL(b); NONNULL(x);
-  TO_CHECK(n_layers >= 1, TO_ERR_ARG, "need at least one layer");
-  TO_CHECK(out || classes || confusion, TO_ERR_ARG, "infer: no output asked for (out, classes or confusion)");
-  TO_CHECK(!confusion || y, TO_ERR_ARG, "infer: the confusion matrix needs the targets y");
-  const int hk = stack_hidden_act_check(hidden_act);
-  TO_CHECK(out_act == TO_ACT_SOFTMAX || out_act == TO_ACT_LOGISTIC, TO_ERR_UNSUPPORTED,
-           "infer: the output activation must be softmax or logistic");
-  TO_CHECK(x->rank == 1 && x->dims[0] >= 1, TO_ERR_SHAPE, "infer: x must be a (batched) vector, got " + shape_str(x));
-  const int dt = x->dtype;
-  const int64_t nL = stack_params_check(n_layers, w, b, nullptr, nullptr, dt, x->dims[0]);
-  const int64_t B = x->batch > 0 ? x->batch : 1;
-  if (y) {
-    TO_CHECK(y->dtype == dt, TO_ERR_ARG, "infer: x and y have different dtypes");
-    TO_CHECK(y->rank == 1 && y->dims[0] == nL && y->batch == x->batch, TO_ERR_SHAPE,
-             "infer: y must be " + std::to_string(nL) + "-vectors of x's batch, got " + shape_str(y));
-  }
-  if (out) {
-    TO_CHECK(out->dtype == dt, TO_ERR_ARG, "infer: x and out have different dtypes");
-    TO_CHECK(out->rank == 1 && out->dims[0] == nL && out->batch == x->batch, TO_ERR_SHAPE,
-             "infer: out must be " + std::to_string(nL) + "-vectors of x's batch, got " + shape_str(out));
-    TO_CHECK(out->contiguous(), TO_ERR_ARG, "infer: out must be contiguous");
-  }
-  ensure(x);
-  if (y) ensure(y);
-  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); }
-  if (out) {
-    ensure(out);
-    before_write(out);
-    out->id = fresh_id();
-  }
-  // rows with unit element stride (a strided vector view is packed first); the rows themselves may lie anywhere
-  Holder xc(x->dims[0] > 1 && x->strides[0] != 1 ? contiguous(x) : nullptr), yc;
-  const to_tensor xr = xc.t ? xc.t : x;
-  const int64_t x_sm = x->batch > 0 ? xr->bstride : 0;
-  if (y && y->dims[0] > 1 && y->strides[0] != 1) yc.t = contiguous(y);
-  const to_tensor yr = yc.t ? yc.t : y;
-  const int64_t y_sm = y && y->batch > 0 ? yr->bstride : 0;
-  // C[B, n] = A[B, K] . W^T : B operand element (k, j) = W[j*K + k]
-  auto layer = [&](const void* A, int64_t a_sm, to_tensor W, void* C) {
-    GemmProblem p{};
-    p.dtype = dt;
-    p.A = A; p.B = W->ptr; p.C = C;
-    p.M = B; p.N = W->dims[0]; p.K = W->dims[1];
-    p.a_sm = a_sm; p.a_sk = 1; p.b_sk = 1; p.b_sn = p.K; p.c_sm = p.N;
-    p.batch = 1;
-    p.alpha = 1.0; p.beta = 0.0;
-    return p;
-  };
-  std::vector<Holder> act(n_layers);
-  const void* prev = xr->ptr;
-  int64_t prev_sm = x_sm;
-  for (int l = 0; l + 1 < n_layers; ++l) {
-    const int64_t n = w[l]->dims[0];
-    act[l].t = new_tensor(1, &n, B, dt);
-    GemmProblem p = layer(prev, prev_sm, w[l], act[l].t->ptr);
-    p.bias = b[l]->ptr;
-    p.act = hk + 1;
-    if (gemm_epilogue_ok(p)) {
-      if (gemm_small_route(p)) launch_gemm_small(p, S());
-      else run_gemm(p);
-    } else {  // (the tiled fp64 kernel: alpha / beta only)
-      p.bias = nullptr;
-      p.act = 0;
-      run_gemm(p);
-      launch_bias_act_rows(dt, act[l].t->ptr, b[l]->ptr, B, n, hk, S());
-    }
-    prev = act[l].t->ptr;
-    prev_sm = n;
-  }
-  const to_tensor WL = w[n_layers - 1], bL = b[n_layers - 1];
-  Holder cls, conf, z;
-  if (classes) cls.t = new_tensor(1, &B, 0);  // B int32 in a float-typed pool buffer
-  if (confusion) {
-    const int64_t nl = nL * nL * 2;              // n_L^2 uint64
-    conf.t = new_tensor(1, &nl, 0);
-    TO_HIP(hipMemsetAsync(conf.t->ptr, 0, (size_t)(nL * nL) * 8, S()));
-  }
-  int* cls_p = cls.t ? static_cast<int*>(cls.t->ptr) : nullptr;
-  auto* conf_p = conf.t ? static_cast<unsigned long long*>(conf.t->ptr) : nullptr;
-  void* out_p = out ? out->ptr : nullptr;
-  const void* y_p = y ? yr->ptr : nullptr;
-  const bool softmax = out_act == TO_ACT_SOFTMAX;
-  if (nL <= INFER_NARROW_MAX) {
-    launch_infer_narrow(dt, prev, prev_sm, B, WL->dims[1], WL->ptr, bL->ptr, (int)nL, softmax, out_p, y_p, y_sm, cls_p,
-                        conf_p, S());
-  } else {
-    void* zp = out_p;  // the row launch reads each element of z before it writes the same element of out
-    if (!zp) {
-      z.t = new_tensor(1, &nL, B, dt);
-      zp = z.t->ptr;
-    }
-    run_gemm(layer(prev, prev_sm, WL, zp));
-    TO_CHECK(nL <= 2147483647LL, TO_ERR_SHAPE, "infer: output layer too wide");
-    launch_infer_rows(dt, zp, B, bL->ptr, (int)nL, softmax, out_p, y_p, y_sm, cls_p, conf_p, S());
-  }
-  if (classes) {
-    std::vector<int32_t> ids((size_t)B);
-    device_to_host(ids.data(), cls_p, (size_t)B * sizeof(int32_t), S());
-    for (int64_t r = 0; r < B; ++r) classes[r] = ids[(size_t)r];
-  }
-  if (confusion) device_to_host(confusion, conf_p, (size_t)(nL * nL) * sizeof(int64_t), S());
-}
-
-to_status to_fflayer_stack_infer(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
-                                 to_tensor x, to_tensor y_or_null, to_tensor out_or_null, int64_t* classes_or_null,
-                                 int64_t* confusion_or_null) {
-  API_BEGIN
-  fflayer_stack_infer_impl(n_layers, w, b, hidden_act, out_act, x, y_or_null, out_or_null, classes_or_null,
-                           confusion_or_null);
-  API_END
-}
-
-// ---- recurrent stacks: `runNetwork` / `netGrad` / `trainNetwork'` of Recurrent.hs as one call -------------------------
-// Layer l is `fullyConnected` (Recurrent.hs:91-119; z = W x + W' s + b, new state state_act[l](z) -- logistic or tanh, each
-// layer its own --, output z through the layer's `*~ act`, hidden_act) or a stateless ffLayer (:126-138).  Internally everything is TIME-MAJOR, row r = t * B + b, so that every
-// time-independent piece is ONE contraction over all B*T rows: the input projections (bias in the epilogue), the head,
-// the weight gradients dZ^T X and dZ^T S_prev (+ the bias row sums) and the input cotangents dZ W (hidden_act' of the layer
-// below in the epilogue).  A stateful layer's states live in St [T+1][B][n] with block 0 = the initial states: S_prev and
-// S are the two offset views St[0..T) and St[1..T] of one buffer.  What is left is each stateful layer's recurrence:
-// persistent (rnn_seq.hip, one launch per layer and direction for all T steps) or per step (one GEMM with the addend,
-// plus one elementwise launch).  The caller's [B; T, .] rows are moved to and from time-major by one strided copy each.
-static int g_rnn_persistent = 1;                          // to_set_rnn_persistent: 0 per step, 1 auto, 2 wherever in range
-static int64_t g_rnn_persistent_runs = 0, g_rnn_stepwise_runs = 0;
-
-// Does the persistent kernel take a layer of width H over a batch of B sequences?  The automatic rule is the threshold
-// measured by tools/rnn_scan.py (profiles/r07_rnn_scan.txt): the kernel wins while W' sits in its
-// LDS (H = 64: 2-4x ahead of the per-step route at every B and T) and loses once every step streams W' from L2 into ONE
-// workgroup (H = 256 / 512: up to 4.4x behind), so automatic = persistent exactly when the plan holds W' in LDS.
-static bool rnn_persistent_for(int dt, int64_t H, int64_t B, RnnSeqPlan* plan) {
-  if (g_rnn_persistent == 0 || !rnn_seq_plan(dt, H, B, plan)) return false;
-  return g_rnn_persistent == 2 || plan->m_lds;
-}
-
-// C = A . B(op) with the epilogue of p (bias, act = logistic / tanh, dact = h (1 - h) / 1 - h h by dact_kind, beta * Cin); a kernel without one gets
-// the plain product and the epilogue as separate launches.  C is contiguous [M, N].
-static void rnn_gemm(GemmProblem p) {
-  if (gemm_epilogue_ok(p)) {
-    if (gemm_small_route(p)) launch_gemm_small(p, S());
-    else run_gemm(p);
-    return;
-  }
-  const int act = p.act, dact_kind = p.dact_kind;
-  const void* dact = p.dact;
-  if (p.bias) {  // C = bias rows, then C += A B
-    TO_CHECK(p.beta == 0.0, TO_ERR_STATE, "internal: bias with an addend");
-    launch_bcast_axis(p.dtype, p.bias, p.C, 1, p.M, p.N, 0, S());
-    p.beta = 1.0;
-    p.Cin = p.C;
-  }
-  TO_CHECK(!(act && dact), TO_ERR_STATE, "internal: act and dact in one epilogue");
-  p.bias = nullptr; p.act = 0; p.dact = nullptr; p.dact_kind = 0;
-  run_gemm(p);
-  if (act || dact) {
-    EwArgs a{};
-    a.dtype = p.dtype;
-    a.kind = act ? (act == 2 ? EW_TANH : EW_LOGISTIC) : (dact_kind ? EW_MUL_1MH2 : EW_MUL_H1MH);
-    a.n = act ? 1 : 2;
-    a.x[0] = p.C;
-    a.x[1] = dact;
-    a.period[0] = a.period[1] = p.M * p.N;
-    a.out = p.C;
-    a.total = p.M * p.N;
-    launch_ewise(a, S());
-  }
-}
-
-// C[M, N] = A[M, K] (rows a_sm apart) . Bop where Bop(k, n) = Bm[k * b_sk + n * b_sn]
-static GemmProblem rnn_problem(int dt, const void* A, int64_t a_sm, int64_t a_sk, const void* Bm, int64_t b_sk,
-                               int64_t b_sn, void* C, int64_t M, int64_t N, int64_t K) {
-  GemmProblem p{};
-  p.dtype = dt;
-  p.A = A; p.B = Bm; p.C = C;
-  p.M = M; p.N = N; p.K = K;
-  p.a_sm = a_sm; p.a_sk = a_sk; p.b_sk = b_sk; p.b_sn = b_sn; p.c_sm = N;
-  p.batch = 1;
-  p.alpha = 1.0; p.beta = 0.0;
-  return p;
-}
-
-static void ew2(int dt, int kind, void* out, const void* x0, const void* x1, int64_t n) {
-  EwArgs a{};
-  a.dtype = dt;
-  a.kind = kind;
-  a.n = x1 ? 2 : 1;
-  a.x[0] = x0;
-  a.x[1] = x1;
-  a.period[0] = a.period[1] = n;
-  a.coef[0] = a.coef[1] = 1.0;
-  a.out = out;
-  a.total = n;
-  launch_ewise(a, S());
-}
-
-static void rnn_stack_impl(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
-                           const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
-                           to_tensor out, const to_tensor* s_out, const to_tensor* gs, const to_tensor* gws,
-                           const to_tensor* gw, const to_tensor* gb, to_tensor gx, to_tensor losses, int mode,
-                           double rate_state, double rate_params) {
-  // mode 0: run, 1: grad, 2: sgd
-  const char* fn = mode == 0 ? "to_rnn_stack_run" : mode == 1 ? "to_rnn_stack_grad" : "to_rnn_stack_sgd";
-  const std::string F = std::string(fn) + ": ";
-  require_init();
-  no_capture(fn);
-  NONNULL(state_act); NONNULL(s); NONNULL(ws); NONNULL(w); NONNULL(b); NONNULL(X);
-  TO_CHECK(n_layers >= 1, TO_ERR_ARG, F + "need at least one layer");
-  for (int l = 0; l < n_layers; ++l)
-    TO_CHECK(state_act[l] == TO_ACT_LOGISTIC || state_act[l] == TO_ACT_TANH || state_act[l] == TO_RNN_STATELESS,
-             TO_ERR_UNSUPPORTED,
-             F + "layer " + std::to_string(l) + ": the state activation must be logistic or tanh (or TO_RNN_STATELESS)");
-  const int hk = stack_hidden_act_check(hidden_act);
-  auto state_kind = [&](int l) { return state_act[l] == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC; };
-  const bool sm_ce = out_act == TO_ACT_SOFTMAX && loss == TO_LOSS_CROSS_ENTROPY;
-  const bool lg_se = out_act == TO_ACT_LOGISTIC && loss == TO_LOSS_SQUARED_ERROR;
-  if (mode == 0)
-    TO_CHECK(out_act == TO_ACT_SOFTMAX || out_act == TO_ACT_LOGISTIC, TO_ERR_UNSUPPORTED,
-             F + "the output activation must be softmax or logistic");
-  else
-    TO_CHECK(sm_ce || lg_se, TO_ERR_UNSUPPORTED, F + "(softmax, crossEntropy) or (logistic, squaredError) only");
-  const int dt = X->dtype;
-  TO_CHECK(X->rank == 2 && X->dims[0] >= 1 && X->dims[1] >= 1, TO_ERR_SHAPE,
-           F + "X must be [B; T, i] (or [T, i]), got " + shape_str(X));
-  const int64_t T = X->dims[0], B = X->batch > 0 ? X->batch : 1;
-  const to_tensor* gw_chk = mode == 1 ? gw : nullptr;
-  if (mode == 1) { NONNULL(gs); NONNULL(gws); NONNULL(gw); NONNULL(gb); }
-  const int64_t nL = stack_params_check(n_layers, w, b, gw_chk, mode == 1 ? gb : nullptr, dt, X->dims[1]);
-  auto seq_like = [&](to_tensor t, int64_t n, const char* what) {  // [B; T, n] of X's batch and dtype, contiguous
-    TO_CHECK(t->dtype == dt, TO_ERR_ARG, F + what + " and X have different dtypes");
-    TO_CHECK(t->rank == 2 && t->dims[0] == T && t->dims[1] == n && t->batch == X->batch, TO_ERR_SHAPE,
-             F + what + " must be [B; " + std::to_string(T) + ", " + std::to_string(n) + "] of X's batch, got " + shape_str(t));
-  };
-  for (int l = 0; l < n_layers; ++l) {
-    const int64_t n = w[l]->dims[0];
-    const std::string L = F + "layer " + std::to_string(l) + ": ";
-    if (state_act[l] == TO_RNN_STATELESS) {
-      TO_CHECK(!s[l] && !ws[l], TO_ERR_ARG, L + "a stateless layer has no state and no W'");
-      if (mode == 1) TO_CHECK(!gs[l] && !gws[l], TO_ERR_ARG, L + "a stateless layer has no state gradients");
-      if (mode == 0 && s_out) TO_CHECK(!s_out[l], TO_ERR_ARG, L + "a stateless layer has no final state");
-      continue;
-    }
-    NONNULL(s[l]); NONNULL(ws[l]);
-    TO_CHECK(s[l]->dtype == dt && ws[l]->dtype == dt, TO_ERR_ARG, L + "states, parameters and data must share one dtype");
-    TO_CHECK(ws[l]->rank == 2 && ws[l]->batch == 0 && ws[l]->dims[0] == n && ws[l]->dims[1] == n && ws[l]->contiguous(),
-             TO_ERR_SHAPE, L + "W' has shape " + shape_str(ws[l]));
-    TO_CHECK(s[l]->rank == 1 && s[l]->dims[0] == n, TO_ERR_SHAPE, L + "s has shape " + shape_str(s[l]));
-    if (mode == 0)
-      TO_CHECK(s[l]->batch == 0 || s[l]->batch == X->batch, TO_ERR_SHAPE,
-               L + "s must be unbatched or of X's batch, got " + shape_str(s[l]));
-    else
-      TO_CHECK(s[l]->batch == 0 && s[l]->contiguous(), TO_ERR_SHAPE,
-               L + "the initial state of grad / sgd must be unbatched and contiguous, got " + shape_str(s[l]));
-    if (mode == 1) {
-      NONNULL(gs[l]); NONNULL(gws[l]);
-      TO_CHECK(gs[l]->dtype == dt && gws[l]->dtype == dt, TO_ERR_ARG, L + "gradients and data must share one dtype");
-      TO_CHECK(same_shape(gs[l], s[l]) && gs[l]->batch == 0 && gs[l]->contiguous() && same_shape(gws[l], ws[l]) &&
-                   gws[l]->contiguous(), TO_ERR_SHAPE, L + "gradient destinations must match the state and W'");
-    }
-    if (mode == 0 && s_out && s_out[l]) {
-      TO_CHECK(s_out[l]->dtype == dt, TO_ERR_ARG, L + "s_out and X have different dtypes");
-      TO_CHECK(s_out[l]->rank == 1 && s_out[l]->dims[0] == n && s_out[l]->batch == X->batch && s_out[l]->contiguous(),
-               TO_ERR_SHAPE, L + "s_out must be a contiguous [B; n] of X's batch, got " + shape_str(s_out[l]));
-    }
-  }
-  if (mode == 0) {
-    NONNULL(out);
-    seq_like(out, nL, "out");
-    TO_CHECK(out->contiguous(), TO_ERR_ARG, F + "out must be contiguous");
-  } else {
-    NONNULL(Y);
-    seq_like(Y, nL, "Y");
-    if (gx) { seq_like(gx, X->dims[1], "gx"); TO_CHECK(gx->contiguous(), TO_ERR_ARG, F + "gx must be contiguous"); }
-    if (losses) {
-      TO_CHECK(losses->dtype == dt, TO_ERR_ARG, F + "losses and X have different dtypes");
-      TO_CHECK(losses->rank == 1 && losses->dims[0] == T && losses->batch == X->batch && losses->contiguous(),
-               TO_ERR_SHAPE, F + "losses must be a contiguous [B; T] of X's batch, got " + shape_str(losses));
-    }
-  }
-  TO_CHECK(T * B <= 2147483647LL, TO_ERR_SHAPE, F + "more than 2^31-1 rows");
-
-  // ---- operands produced; destinations claimed -------------------------------------------------------------------
-  ensure(X);
-  if (Y) ensure(Y);
-  for (int l = 0; l < n_layers; ++l) {
-    ensure(w[l]); ensure(b[l]);
-    if (s[l]) { ensure(s[l]); ensure(ws[l]); }
-  }
-  auto claim = [](to_tensor t) { ensure(t); before_write(t); t->id = fresh_id(); };
-  if (out) claim(out);
-  if (s_out) for (int l = 0; l < n_layers; ++l) if (s_out[l]) claim(s_out[l]);
-  if (gx) claim(gx);
-  if (losses) claim(losses);
-  if (mode == 1)
-    for (int l = 0; l < n_layers; ++l) {
-      claim(gw[l]); claim(gb[l]);
-      if (gs[l]) { claim(gs[l]); claim(gws[l]); }
-    }
-
-  const int64_t rows = T * B;
-  const int64_t es = dt == TO_F64 ? 8 : 4;
-  auto at = [es](const void* p, int64_t elems) { return static_cast<void*>(static_cast<char*>(const_cast<void*>(p)) + elems * es); };
-  // [B; T, n] (strides of t) -> time-major [T][B][n]
-  auto to_time_major = [&](to_tensor t, Holder& h) -> const void* {
-    if (B == 1 && t->contiguous()) return t->ptr;
-    const int64_t n = t->dims[1];
-    const int64_t d3[3] = {T, B, n}, s3[3] = {t->strides[0], t->batch > 0 ? t->bstride : 0, t->strides[1]};
-    const int64_t dims2[2] = {T * B, n};
-    h.t = new_tensor(2, dims2, 0, dt);
-    launch_copy_strided(dt, t->ptr, h.t->ptr, 3, d3, s3, S());
-    return h.t->ptr;
-  };
-  // time-major [T][B][n] -> the caller's contiguous [B; T, n]
-  auto from_time_major = [&](const void* src, to_tensor dst, int64_t n) {
-    if (src == dst->ptr) return;
-    const int64_t d3[3] = {B, T, n}, s3[3] = {n, B * n, 1};
-    launch_copy_strided(dt, src, dst->ptr, 3, d3, s3, S());
-  };
-  // scratch of `rows` x n, or the caller's own buffer when it is time-major already (B == 1)
-  auto scratch_or = [&](to_tensor dst, int64_t n, Holder& h) -> void* {
-    if (dst && B == 1) return dst->ptr;
-    const int64_t d2[2] = {rows, n};
-    h.t = new_tensor(2, d2, 0, dt);
-    return h.t->ptr;
-  };
-  Holder xh, yh;
-  const void* Xt = to_time_major(X, xh);
-  const void* Yt = mode ? to_time_major(Y, yh) : nullptr;
-
-  // ---- forward -------------------------------------------------------------------------------------------------------
-  std::vector<Holder> Z(n_layers), St(n_layers), WT(n_layers), Ah(n_layers);
-  std::vector<const void*> outp(n_layers, nullptr);   // what the layer above reads: hidden_act(z_l), all rows
-  std::vector<RnnSeqPlan> plan(n_layers);
-  std::vector<char> persist(n_layers, 0);
-  bool any_state = false, all_persistent = true;
-  const void* prev = Xt;
-  int64_t prev_n = X->dims[1];
-  const void* no_bias_for_head = nullptr;  // run, stateless last layer: the head launch adds b_L
-  for (int l = 0; l < n_layers; ++l) {
-    const int64_t n = w[l]->dims[0];
-    const bool last = l + 1 == n_layers, stateful = state_act[l] != TO_RNN_STATELESS;
-    const int64_t d2[2] = {rows, n};
-    Z[l].t = new_tensor(2, d2, 0, dt);
-    // the input projection (stateless hidden layer: its activation) over all rows
-    GemmProblem p = rnn_problem(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, Z[l].t->ptr, rows, n, prev_n);
-    p.bias = b[l]->ptr;
-    if (!stateful && !last) p.act = hk + 1;
-    if (last && !stateful && mode == 0) { p.bias = nullptr; no_bias_for_head = b[l]->ptr; }
-    rnn_gemm(p);
-    if (stateful) {
-      any_state = true;
-      const int64_t d3[2] = {(T + 1) * B, n};
-      St[l].t = new_tensor(2, d3, 0, dt);
-      void* st = St[l].t->ptr;
-      if (s[l]->batch == 0) {
-        launch_bcast_axis(dt, s[l]->ptr, st, 1, B, n, 0, S());
-      } else {
-        const int64_t dd[2] = {B, n}, ss[2] = {s[l]->bstride, s[l]->strides[0]};
-        launch_copy_strided(dt, s[l]->ptr, st, 2, dd, ss, S());
-      }
-      persist[l] = rnn_persistent_for(dt, n, B, &plan[l]);
-      all_persistent = all_persistent && persist[l];
-      void* z = Z[l].t->ptr;
-      if (persist[l]) {
-        const int64_t dd[2] = {n, n}, ss[2] = {1, n};  // W'^T: M[k][j] = W'[j][k]
-        WT[l].t = new_tensor(2, dd, 0, dt);
-        launch_copy_strided(dt, ws[l]->ptr, WT[l].t->ptr, 2, dd, ss, S());
-        launch_rnn_seq(dt, false, plan[l], WT[l].t->ptr, z, st, B, T, n, state_kind(l), S());
-      } else {
-        for (int64_t t = 0; t < T; ++t) {  // z_t = P_t + s_{t-1} W'^T (in place), s_t = state_act(z_t)
-          GemmProblem q = rnn_problem(dt, at(st, t * B * n), n, 1, ws[l]->ptr, 1, n, at(z, t * B * n), B, n, n);
-          q.beta = 1.0;
-          q.Cin = q.C;
-          rnn_gemm(q);
-          ew2(dt, state_kind(l) == ACT_KIND_TANH ? EW_TANH : EW_LOGISTIC, at(st, (t + 1) * B * n), at(z, t * B * n), nullptr,
-              B * n);
-        }
-      }
-    }
-    // what the layer above reads: a hidden stateful layer's output hidden_act(z) IS its state when the two activations
-    // are the same function; otherwise it is one more elementwise pass over all rows of z
-    if (stateful && !last && state_kind(l) == hk) {
-      prev = at(St[l].t->ptr, B * n);
-    } else if (stateful && !last) {
-      Ah[l].t = new_tensor(2, d2, 0, dt);
-      ew2(dt, hk == ACT_KIND_TANH ? EW_TANH : EW_LOGISTIC, Ah[l].t->ptr, Z[l].t->ptr, nullptr, rows * n);
-      prev = Ah[l].t->ptr;
-    } else {
-      prev = Z[l].t->ptr;
-    }
-    outp[l] = prev;
-    prev_n = n;
-  }
-  if (any_state) (all_persistent ? g_rnn_persistent_runs : g_rnn_stepwise_runs)++;
-  const int L = n_layers - 1;
-  if (mode == 0) {
-    if (s_out)
-      for (int l = 0; l < n_layers; ++l)
-        if (s_out[l])
-          TO_HIP(hipMemcpyAsync(s_out[l]->ptr, at(St[l].t->ptr, T * B * w[l]->dims[0]), (size_t)(B * w[l]->dims[0] * es),
-                                hipMemcpyDeviceToDevice, S()));
-    Holder oh, zb;
-    const void* bias = no_bias_for_head;
-    if (!bias) {
-      zb.t = new_tensor(1, &nL, 0, dt);
-      launch_fill(dt, zb.t->ptr, nL, 0.0, S());
-      bias = zb.t->ptr;
-    }
-    TO_CHECK(nL <= 2147483647LL, TO_ERR_SHAPE, F + "output layer too wide");
-    void* ot = scratch_or(out, nL, oh);
-    launch_infer_rows(dt, Z[L].t->ptr, rows, bias, (int)nL, out_act == TO_ACT_SOFTMAX, ot, nullptr, 0, nullptr, nullptr,
-                      S());
-    from_time_major(ot, out, nL);
-    TO_HIP(hipStreamSynchronize(S()));
-    return;
-  }
-
-  // ---- backward ------------------------------------------------------------------------------------------------------
-  // gradient destinations: the caller's (grad) or scratch (sgd: applied at the end, so that a failure updates nothing)
-  std::vector<Holder> tg(4 * n_layers);
-  std::vector<void*> g_s(n_layers, nullptr), g_ws(n_layers, nullptr), g_w(n_layers), g_b(n_layers);
-  for (int l = 0; l < n_layers; ++l) {
-    auto dest = [&](const to_tensor* given, to_tensor like, Holder& h) -> void* {
-      if (mode == 1) return given[l]->ptr;
-      h.t = new_tensor(like->rank, like->dims, 0, dt);
-      return h.t->ptr;
-    };
-    g_w[l] = dest(gw, w[l], tg[4 * l]);
-    g_b[l] = dest(gb, b[l], tg[4 * l + 1]);
-    if (state_act[l] != TO_RNN_STATELESS) {
-      g_s[l] = dest(gs, s[l], tg[4 * l + 2]);
-      g_ws[l] = dest(gws, ws[l], tg[4 * l + 3]);
-    }
-  }
-  Holder dzL, lh;
-  {
-    const int64_t d2[2] = {rows, nL};
-    dzL.t = new_tensor(2, d2, 0, dt);
-  }
-  void* lt = nullptr;
-  if (losses) {
-    if (B == 1) lt = losses->ptr;
-    else { const int64_t nr = rows; lh.t = new_tensor(1, &nr, 0, dt); lt = lh.t->ptr; }
-  }
-  launch_loss_grad_rows(dt, Z[L].t->ptr, Yt, dzL.t->ptr, lt, rows, nL, sm_ce ? 0 : 1, S());
-  if (losses && lt != losses->ptr) {  // [T][B] -> [B][T]
-    const int64_t dd[2] = {B, T}, ss[2] = {1, B};
-    launch_copy_strided(dt, lt, losses->ptr, 2, dd, ss, S());
-  }
-  Holder dz_cur(dzL.take()), gxh;
-  for (int l = L; l >= 0; --l) {
-    const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
-    const bool stateful = state_act[l] != TO_RNN_STATELESS;
-    void* dz = dz_cur.t->ptr;
-    if (stateful) {  // dz_t = G_t + (dz_{t+1} W') (.) state_act'(s_t), in place over G
-      void* st = St[l].t->ptr;
-      if (persist[l]) {
-        launch_rnn_seq(dt, true, plan[l], ws[l]->ptr, dz, st, B, T, n, state_kind(l), S());
-      } else {  // per step: D = (dz_{t+1} W') (.) state_act'(s_t), then dz_t += D
-        const int64_t d2[2] = {B, n};
-        Holder dtmp(new_tensor(2, d2, 0, dt));
-        for (int64_t t = T - 2; t >= 0; --t) {
-          GemmProblem q = rnn_problem(dt, at(dz, (t + 1) * B * n), n, 1, ws[l]->ptr, n, 1, dtmp.t->ptr, B, n, n);
-          q.dact = at(st, (t + 1) * B * n);
-          q.dact_kind = state_kind(l);
-          rnn_gemm(q);
-          ew2(dt, EW_AFFINE, at(dz, t * B * n), at(dz, t * B * n), dtmp.t->ptr, B * n);
-        }
-      }
-      // gW' = dZ^T S_prev ; gs = (sum_b dz_0[b]) W'
-      run_gemm(rnn_problem(dt, dz, 1, n, st, n, 1, g_ws[l], n, n, rows));
-      Holder dsum(new_tensor(1, &n, 0, dt));
-      launch_sum_axis(dt, dz, dsum.t->ptr, 1, B, n, 0, n, 1, S());
-      run_gemm(rnn_problem(dt, dsum.t->ptr, n, 1, ws[l]->ptr, n, 1, g_s[l], 1, n, n));
-    }
-    // gW = dZ^T A_in (+ gb = the row sums of dZ)
-    const void* a_in = l > 0 ? outp[l - 1] : Xt;
-    GemmProblem p = rnn_problem(dt, dz, 1, n, a_in, m, 1, g_w[l], n, m, rows);
-    p.rowsum = g_b[l];
-    if (gemm_small_route(p)) {
-      launch_gemm_small(p, S());
-    } else {
-      p.rowsum = nullptr;
-      run_gemm(p);
-      launch_sum_axis(dt, dz, g_b[l], 1, rows, n, 0, n, 1, S());
-    }
-    // the cotangent of the layer's input: dZ W (. hidden_act' of the layer below, whose output is a_in)
-    if (l > 0 || gx) {
-      Holder next;
-      void* dst = l > 0 ? nullptr : scratch_or(gx, m, gxh);
-      if (l > 0) {
-        const int64_t d2[2] = {rows, m};
-        next.t = new_tensor(2, d2, 0, dt);
-        dst = next.t->ptr;
-      }
-      GemmProblem q = rnn_problem(dt, dz, n, 1, w[l]->ptr, m, 1, dst, rows, m, n);
-      if (l > 0) { q.dact = a_in; q.dact_kind = hk; }
-      rnn_gemm(q);
-      if (l == 0) from_time_major(dst, gx, m);
-      else { Holder drop(dz_cur.take()); dz_cur.t = next.take(); }
-    }
-  }
-  if (mode == 2) {  // trainNetwork': s -= rate_state gs, every parameter -= rate_params g
-    for (int l = 0; l < n_layers; ++l) {
-      before_write(w[l]); before_write(b[l]);
-      w[l]->id = fresh_id(); b[l]->id = fresh_id();
-      launch_sgd(dt, w[l]->ptr, g_w[l], rate_params, w[l]->total(), S());
-      launch_sgd(dt, b[l]->ptr, g_b[l], rate_params, b[l]->total(), S());
-      if (state_act[l] != TO_RNN_STATELESS) {
-        before_write(s[l]); before_write(ws[l]);
-        s[l]->id = fresh_id(); ws[l]->id = fresh_id();
-        launch_sgd(dt, s[l]->ptr, g_s[l], rate_state, s[l]->total(), S());
-        launch_sgd(dt, ws[l]->ptr, g_ws[l], rate_params, ws[l]->total(), S());
-      }
-    }
-  }
-  TO_HIP(hipStreamSynchronize(S()));
-}
-
-to_status to_rnn_stack_run(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
-                           const to_tensor* b, int hidden_act, int out_act, to_tensor X, to_tensor out,
-                           const to_tensor* s_out_or_null) {
-  API_BEGIN
-  rnn_stack_impl(n_layers, state_act, s, ws, w, b, hidden_act, out_act, -1, X, nullptr, out, s_out_or_null, nullptr,
-                 nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.0, 0.0);
-  API_END
-}
-
-to_status to_rnn_stack_grad(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
-                            const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
-                            const to_tensor* gs, const to_tensor* gws, const to_tensor* gw, const to_tensor* gb,
-                            to_tensor gx_or_null, to_tensor losses_or_null) {
-  API_BEGIN
-  rnn_stack_impl(n_layers, state_act, s, ws, w, b, hidden_act, out_act, loss, X, Y, nullptr, nullptr, gs, gws, gw, gb,
-                 gx_or_null, losses_or_null, 1, 0.0, 0.0);
-  API_END
-}
-
-to_status to_rnn_stack_sgd(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
-                           const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
-                           double rate_state, double rate_params, to_tensor losses_or_null) {
-  API_BEGIN
-  rnn_stack_impl(n_layers, state_act, s, ws, w, b, hidden_act, out_act, loss, X, Y, nullptr, nullptr, nullptr, nullptr,
-                 nullptr, nullptr, nullptr, losses_or_null, 2, rate_state, rate_params);
-  API_END
-}
-
-to_status to_set_rnn_persistent(int on, int* previous_or_null) {
-  API_BEGIN
-  TO_CHECK(on >= 0 && on <= 2, TO_ERR_ARG, "to_set_rnn_persistent: 0 (per step), 1 (automatic) or 2 (wherever in range)");
-  if (previous_or_null) *previous_or_null = g_rnn_persistent;
-  g_rnn_persistent = on;
-  API_END
-}
-
-to_status to_rnn_stats(int64_t* persistent_runs, int64_t* stepwise_runs) {
-  API_BEGIN
-  if (persistent_runs) *persistent_runs = g_rnn_persistent_runs;
-  if (stepwise_runs) *stepwise_runs = g_rnn_stepwise_runs;
-  API_END
-}
-
-// ---- `induceNetwork` iterated (FeedForward.hs:150-164; app/MNIST.hs:357-365: 5000 dependent steps on the input) --------
-// Route A, per iteration: the forward of to_fflayer_stack_infer, launch_loss_grad_rows, the cotangents back through the
-// layers and the last contraction with the step in its epilogue (x <- 1 x + (-rate) dz_1 W_1: alpha = -rate, beta = 1,
-// Cin = C = x; when gx is wanted the last iteration runs the plain product as well, into gx).  Takes every valid stack; its launch count grows with iters.  Route B, persistent (induce_seq.hip): all
-// iterations of all rows in ONE launch, where its plan fits (and, for a plan of several workgroups a row, where the
-// placement probe holds).  Both iterate on a private copy of x; the caller's tensors are written once, at the end.
-static int g_induce_persistent = 1;                       // to_set_induce_persistent: 0 per iteration, 1 auto, 2 wherever in range
-static int64_t g_induce_persistent_runs = 0, g_induce_iter_runs = 0;
-
-// The automatic rule.  NOT MEASURED YET: tools/induce_scan.py has not been run on a device for this change (see
-// profiles/r08_induce_scan.txt and DESIGN.md section 3.3), so the default takes the persistent route only where its
-// advantage follows from counting and needs no measurement to hold: a plan of ONE workgroup a row (no exchange, no
-// placement precondition, nobody to wait for) with at most 256 rows, where every row has a workgroup of its own and an
-// iteration is a handful of passes over LDS against six or more dependent launches on route A.  Plans of several
-// workgroups a row (the reference's 784-300-100-10 in fp32) and longer batches stay on route A by default until the scan
-// has been run and says otherwise; to_set_induce_persistent(2) forces them.
-static bool induce_auto_persistent(const InduceSeqPlan& plan, int64_t B) {
-  return plan.G == 1 && B <= 256;
-}
-
-static void induce_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss,
-                        to_tensor x, to_tensor y, double rate, int64_t iters, to_tensor out, to_tensor gx, to_tensor losses) {
-  const std::string F = "to_fflayer_stack_induce: ";
-  require_init();
-  no_capture("to_fflayer_stack_induce");
-  NONNULL(w); NONNULL(b); NONNULL(x); NONNULL(y); NONNULL(out);
-  TO_CHECK(n_layers >= 1, TO_ERR_ARG, F + "need at least one layer");
-  TO_CHECK(iters >= 0, TO_ERR_ARG, F + "negative iteration count");
-  TO_CHECK(!gx || iters >= 1, TO_ERR_ARG, F + "gx is the gradient of the last iteration: it needs iters >= 1");
-  const int hk = stack_hidden_act_check(hidden_act);
-  const bool sm_ce = out_act == TO_ACT_SOFTMAX && loss == TO_LOSS_CROSS_ENTROPY;
-  const bool lg_se = out_act == TO_ACT_LOGISTIC && loss == TO_LOSS_SQUARED_ERROR;
-  TO_CHECK(sm_ce || lg_se, TO_ERR_UNSUPPORTED, F + "(softmax, crossEntropy) or (logistic, squaredError) only");
-  TO_CHECK(x->rank == 1 && x->dims[0] >= 1, TO_ERR_SHAPE, F + "x must be a (batched) vector, got " + shape_str(x));
-  const int dt = x->dtype;
-  const int64_t i0 = x->dims[0];
-  const int64_t nL = stack_params_check(n_layers, w, b, nullptr, nullptr, dt, i0);
-  const int64_t B = x->batch > 0 ? x->batch : 1;
-  TO_CHECK(y->dtype == dt, TO_ERR_ARG, F + "x and y have different dtypes");
-  TO_CHECK(y->rank == 1 && y->dims[0] == nL && (y->batch == 0 || y->batch == x->batch), TO_ERR_SHAPE,
-           F + "y must be " + std::to_string(nL) + "-vectors of x's batch (or one unbatched target), got " + shape_str(y));
-  auto like_x = [&](to_tensor t, const char* what) {
-    TO_CHECK(t->dtype == dt, TO_ERR_ARG, F + "x and " + what + " have different dtypes");
-    TO_CHECK(t->rank == 1 && t->dims[0] == i0 && t->batch == x->batch, TO_ERR_SHAPE,
-             F + what + " must have x's shape and batch, got " + shape_str(t));
-    TO_CHECK(t->contiguous(), TO_ERR_ARG, F + what + " must be contiguous");
-  };
-  like_x(out, "out");
-  if (gx) like_x(gx, "gx");
-  if (losses) {
-    TO_CHECK(losses->dtype == dt, TO_ERR_ARG, F + "x and losses have different dtypes");
-    TO_CHECK(losses->rank == 1 && losses->dims[0] == iters && losses->batch == x->batch, TO_ERR_SHAPE,
-             F + "losses must be [B; " + std::to_string(iters) + "] of x's batch, got " + shape_str(losses));
-    TO_CHECK(losses->contiguous(), TO_ERR_ARG, F + "losses must be contiguous");
-  }
-  TO_CHECK(B <= 2147483647LL && B * i0 <= (1LL << 40), TO_ERR_SHAPE, F + "too many rows");
-
-  // ---- operands produced; destinations claimed -----------------------------------------------------------------------
-  ensure(x);
-  ensure(y);
-  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); }
-  auto claim = [](to_tensor t) { ensure(t); before_write(t); t->id = fresh_id(); };
-  const int64_t es = dt == TO_F64 ? 8 : 4;
-  auto at = [es](void* p, int64_t elems) { return static_cast<void*>(static_cast<char*>(p) + elems * es); };
-  if (iters == 0) {  // x to out bit for bit; nothing else is touched, neither route counted
-    if (out != x) {
-      claim(out);
-      if (out->ptr != x->ptr) {
-        const int64_t dd[2] = {B, i0}, ss[2] = {x->batch > 0 ? x->bstride : 0, x->strides[0]};
-        launch_copy_strided(dt, x->ptr, out->ptr, 2, dd, ss, S());
-      }
-    }
-    TO_HIP(hipStreamSynchronize(S()));
-    return;
-  }
-  claim(out);
-  if (gx) claim(gx);
-  if (losses) claim(losses);
-
-  // the private copy of x the iterations run on, contiguous [B][i0]
-  const int64_t dx[2] = {B, i0};
-  Holder cur(new_tensor(2, dx, 0, dt));
-  {
-    const int64_t ss[2] = {x->batch > 0 ? x->bstride : 0, x->strides[0]};
-    launch_copy_strided(dt, x->ptr, cur.t->ptr, 2, dx, ss, S());
-  }
-  Holder gxs, lt;
-  if (gx) gxs.t = new_tensor(2, dx, 0, dt);
-  const int64_t dl[2] = {B, iters};
-  if (losses) lt.t = new_tensor(2, dl, 0, dt);
-  // targets with unit element stride; rows y_sm apart (0: one target for every row)
-  Holder yc(y->dims[0] > 1 && y->strides[0] != 1 ? contiguous(y) : nullptr);
-  const to_tensor yr = yc.t ? yc.t : y;
-  const int64_t y_sm = y->batch > 0 ? yr->bstride : 0;
-
-  int64_t dims[INDUCE_MAX_LAYERS + 1] = {0};
-  InduceSeqPlan plan;
-  bool persistent = false;
-  if (g_induce_persistent != 0 && n_layers <= INDUCE_MAX_LAYERS) {
-    dims[0] = i0;
-    for (int l = 0; l < n_layers; ++l) dims[l + 1] = w[l]->dims[0];
-    persistent = induce_seq_plan(dt, n_layers, dims, B, iters, &plan) &&
-                 (g_induce_persistent == 2 || induce_auto_persistent(plan, B)) &&
-                 (plan.G == 1 || online_sgd_placement_ok(S()));   // (the exchange's precondition: one XCD's L2)
-  }
-
-  if (persistent) {
-    const void *wp[INDUCE_MAX_LAYERS], *bp[INDUCE_MAX_LAYERS];
-    for (int l = 0; l < n_layers; ++l) { wp[l] = w[l]->ptr; bp[l] = b[l]->ptr; }
-    launch_induce_seq(dt, plan, n_layers, dims, wp, bp, cur.t->ptr, yr->ptr, y_sm, gxs.t ? gxs.t->ptr : nullptr,
-                      lt.t ? lt.t->ptr : nullptr, B, iters, rate, sm_ce ? 1 : 2, hk, S());
-    TO_HIP(hipStreamSynchronize(S()));   // the watchdog's verdict is read before anything of the caller's is written
-    int64_t bad_row = 0;
-    const int64_t bad = induce_seq_status(&bad_row);
-    TO_CHECK(bad == 0, TO_ERR_HIP,
-             F + "the persistent kernel gave up waiting for a workgroup at iteration " + std::to_string(bad - 1) + " of row " +
-                 std::to_string(bad_row) + " (out, gx and losses are untouched)");
-    g_induce_persistent_runs++;
-  } else {
-    // route A.  y as [B][nL] rows (launch_loss_grad_rows reads one target per row)
-    Holder yt;
-    const void* yp = yr->ptr;
-    if (B > 1 && (y->batch == 0 || y_sm != nL)) {
-      const int64_t dy[2] = {B, nL};
-      yt.t = new_tensor(2, dy, 0, dt);
-      if (y->batch == 0) {
-        launch_bcast_axis(dt, yr->ptr, yt.t->ptr, 1, B, nL, 0, S());
-      } else {
-        const int64_t ss[2] = {y_sm, 1};
-        launch_copy_strided(dt, yr->ptr, yt.t->ptr, 2, dy, ss, S());
-      }
-      yp = yt.t->ptr;
-    }
-    std::vector<Holder> act(n_layers), dz(n_layers);   // act[l]: [B][n_l], the last one z_L; dz[l]: the cotangent of z_l
-    for (int l = 0; l < n_layers; ++l) {
-      const int64_t d2[2] = {B, w[l]->dims[0]};
-      act[l].t = new_tensor(2, d2, 0, dt);
-      dz[l].t = new_tensor(2, d2, 0, dt);
-    }
-    Holder lcol;   // losses as [iters][B]: column k of the caller's [B][iters] is one contiguous run here
-    if (losses) {
-      const int64_t d2[2] = {iters, B};
-      lcol.t = new_tensor(2, d2, 0, dt);
-    }
-    void* xp = cur.t->ptr;
-    for (int64_t k = 0; k < iters; ++k) {
-      const void* prev = xp;
-      int64_t prev_n = i0;
-      for (int l = 0; l < n_layers; ++l) {   // a_l = hidden_act(a_{l-1} W_l^T + b_l); the last layer: z_L
-        const int64_t n = w[l]->dims[0];
-        GemmProblem p = rnn_problem(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, act[l].t->ptr, B, n, prev_n);
-        p.bias = b[l]->ptr;
-        if (l + 1 < n_layers) p.act = hk + 1;
-        rnn_gemm(p);
-        prev = act[l].t->ptr;
-        prev_n = n;
-      }
-      launch_loss_grad_rows(dt, act[n_layers - 1].t->ptr, yp, dz[n_layers - 1].t->ptr, lcol.t ? at(lcol.t->ptr, k * B) : nullptr,
-                            B, nL, sm_ce ? 0 : 1, S());
-      for (int l = n_layers - 1; l > 0; --l) {   // dz_{l-1} = (dz_l W_l) (.) hidden_act'(a_{l-1})
-        const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
-        GemmProblem q = rnn_problem(dt, dz[l].t->ptr, n, 1, w[l]->ptr, m, 1, dz[l - 1].t->ptr, B, m, n);
-        q.dact = act[l - 1].t->ptr;
-        q.dact_kind = hk;
-        rnn_gemm(q);
-      }
-      const int64_t n1 = w[0]->dims[0];
-      GemmProblem q = rnn_problem(dt, dz[0].t->ptr, n1, 1, w[0]->ptr, i0, 1, xp, B, i0, n1);
-      if (gx && k + 1 == iters) {
-        // the plain product is wanted too: one more contraction, once a call.  The step itself is taken by the SAME launch
-        // as in every other iteration (below), so that out's bits do not depend on whether gx was asked for -- an axpy
-        // behind the plain product would round alpha * acc + x differently from the epilogue
-        GemmProblem qg = q;
-        qg.C = gxs.t->ptr;
-        rnn_gemm(qg);
-      }
-      q.alpha = -rate;   // x <- 1 x + (-rate) dz_1 W_1 in the contraction's epilogue
-      q.beta = 1.0;
-      q.Cin = xp;
-      rnn_gemm(q);
-    }
-    if (losses) {   // [iters][B] -> [B][iters]
-      const int64_t ss[2] = {1, B};
-      launch_copy_strided(dt, lcol.t->ptr, lt.t->ptr, 2, dl, ss, S());
-    }
-    g_induce_iter_runs++;
-  }
-  TO_HIP(hipMemcpyAsync(out->ptr, cur.t->ptr, (size_t)(B * i0 * es), hipMemcpyDeviceToDevice, S()));
-  if (gx) TO_HIP(hipMemcpyAsync(gx->ptr, gxs.t->ptr, (size_t)(B * i0 * es), hipMemcpyDeviceToDevice, S()));
-  if (losses) TO_HIP(hipMemcpyAsync(losses->ptr, lt.t->ptr, (size_t)(B * iters * es), hipMemcpyDeviceToDevice, S()));
-  TO_HIP(hipStreamSynchronize(S()));
-}
-
-to_status to_fflayer_stack_induce(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
-                                  int loss, to_tensor x, to_tensor y, double rate, int64_t iters, to_tensor out,
-                                  to_tensor gx_or_null, to_tensor losses_or_null) {
-  API_BEGIN
-  induce_impl(n_layers, w, b, hidden_act, out_act, loss, x, y, rate, iters, out, gx_or_null, losses_or_null);
-  API_END
-}
-
-to_status to_set_induce_persistent(int on, int* previous_or_null) {
-  API_BEGIN
-  TO_CHECK(on >= 0 && on <= 2, TO_ERR_ARG,
-           "to_set_induce_persistent: 0 (per iteration), 1 (automatic) or 2 (wherever in range)");
-  if (previous_or_null) *previous_or_null = g_induce_persistent;
-  g_induce_persistent = on;
-  API_END
-}
-
-to_status to_induce_stats(int64_t* persistent_runs, int64_t* per_iteration_runs) {
-  API_BEGIN
-  if (persistent_runs) *persistent_runs = g_induce_persistent_runs;
-  if (per_iteration_runs) *per_iteration_runs = g_induce_iter_runs;
-  API_END
-}
 
 // Is the captured step the trainNetwork step of an ffLayer stack on ONE sample?  Reads the launches the planner made of it:
 //   forward   l = 1..L-1 : a_l = logistic(W_l a_{l-1} + b_l)              (GEMV, bias + activation in the epilogue)
@@ -3411,22 +2235,8 @@ to_status to_graph_online_sgd(to_graph g, to_tensor x_buf, to_tensor y_buf, to_t
     TO_CHECK(!idx_or_null || (idx_or_null[k] >= 0 && idx_or_null[k] < X->batch), TO_ERR_SHAPE, "sample index out of range");
   TO_CHECK(idx_or_null || n_idx <= X->batch, TO_ERR_SHAPE, "more samples than rows");
   lazy_flush_all();  // like a replay: the parameter buffers are about to change, recorded readers come first
-  if (n_idx > 0) {
-    Holder order;
-    const long long* idx_dev = nullptr;
-    if (idx_or_null) {
-      const int64_t nl = (n_idx * 8 + 3) / 4;
-      order.t = new_tensor(1, &nl, 0);
-      host_to_device(order.t->ptr, idx_or_null, (size_t)n_idx * sizeof(int64_t), S());
-      idx_dev = static_cast<const long long*>(order.t->ptr);
-    }
-    online_sgd_reset_status();
-    launch_online_sgd(f.dtype, f.L, f.dims, f.W, f.b, X->ptr, Y->ptr, idx_dev, n_idx, f.rate, f.head, ACT_KIND_LOGISTIC, S());
-    TO_HIP(hipStreamSynchronize(S()));
-    TO_CHECK(online_sgd_status() == 0, TO_ERR_HIP,
-             "online SGD kernel: a workgroup barrier timed out at sample " + std::to_string(online_sgd_status() - 1) +
-                 " (the write-back is all-or-nothing: commit or abort is ONE word decided by compare-and-swap and obeyed by every workgroup; this run aborted, the parameters are unchanged)");
-  }
+  if (n_idx > 0)
+    run_online_sgd(f.dtype, f.L, f.dims, f.W, f.b, X, Y, idx_or_null, n_idx, f.rate, f.head, ACT_KIND_LOGISTIC);
   *handled = 1;
   g_online_runs++;
   g_online_samples += n_idx;

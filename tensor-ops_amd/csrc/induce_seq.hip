@@ -4,7 +4,7 @@
 //   x_{k+1} = x_k - rate * d/dx loss(net(x_k), y)
 //
 // is a chain of tiny dependent matrix-vector products in which only the i0 numbers of x change.  The per-iteration route
-// (api.cpp, route A) pays about eight launches an iteration; here the parameters sit in LDS for the whole launch:
+// (stack_ff.cpp, route A) pays about eight launches an iteration; here the parameters sit in LDS for the whole launch:
 //
 //   * layer 1 is split by COLUMNS over G <= 32 workgroups of one XCD: workgroup g owns the columns J_g of W_1 (all o1 rows)
 //     and the matching slice x[J_g].  The slice never leaves its workgroup: x[J_g] -= rate * W_1[:, J_g]^T dz_1 is local;
@@ -28,7 +28,7 @@
 // fp64 784-32-10 at G = 2; fp64 784-300-100-10 does NOT fit (W_2 alone is 240 KB): route A.
 // Every sum runs in an order fixed by the plan (dtype and widths only), so a row's bits depend neither on the batch nor on
 // the row's place in it, and iters = a followed by iters = b equals iters = a + b.
-// The automatic rule (which shapes take this route by default) is in api.cpp beside the measurements it was derived from
+// The automatic rule (which shapes take this route by default) is in stack_ff.cpp beside the measurements it was derived from
 // (tools/induce_scan.py, profiles/r08_induce_scan.txt).
 #include "common.hpp"
 

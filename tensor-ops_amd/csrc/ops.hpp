@@ -1,4 +1,4 @@
-// Host-side op implementations shared by the eager entry points (api.cpp) and the deferred
+// Host-side op implementations shared by the eager entry points (api.cpp, stack_ff.cpp, stack_rnn.cpp) and the deferred
 // executor (lazy.cpp).  Everything here takes MATERIALISED handles (ptr != nullptr).
 #pragma once
 #include <map>

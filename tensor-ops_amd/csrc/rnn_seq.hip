@@ -1,6 +1,6 @@
 // The recurrence of a `fullyConnected` layer (Recurrent.hs:91-119) over a whole sequence, for to_rnn_stack_*.  Everything
 // of BPTT that does not depend on time (input projections, heads, weight gradients, input cotangents) is one GEMM over all
-// B*T rows in api.cpp; what is left is a chain of T dependent [rows, H] x [H, H] products:
+// B*T rows in stack_rnn.cpp; what is left is a chain of T dependent [rows, H] x [H, H] products:
 //   forward  z_t  = P_t + s_{t-1} W'^T,  s_t = act(z_t)                   (P_t: the input projection, z_t in place over it)
 //   reverse  dz_t = G_t + (dz_{t+1} W') (.) act'(s_t),  dz_T = 0          (G_t: the output-path cotangent, in place)
 // act: the layer's state activation, a template parameter of the kernel (ACT_KIND_LOGISTIC: s (1 - s); ACT_KIND_TANH:
@@ -10,9 +10,9 @@
 // whole sequences (rows) and all H columns, so a step's new vector never leaves the workgroup: it is exchanged through
 // LDS (double-buffered, one barrier per step) -- no inter-workgroup hand-over, no spin, no residency requirement, any grid
 // size.  M sits in LDS when it fits beside the two state buffers (up to H = 201 in fp32, 142 in fp64) and is read through
-// L1 / L2 otherwise -- which loses to the per-step route (profiles/r07_rnn_scan.txt): api.cpp routes only the LDS form
+// L1 / L2 otherwise -- which loses to the per-step route (profiles/r07_rnn_scan.txt): stack_rnn.cpp routes only the LDS form
 // automatically.  The next step's P_t / G_t values are loaded before the barrier.  Every sum has a fixed order.
-// Layouts (api.cpp, time-major): Z [T][B][H], St [T+1][B][H] with row block 0 = the initial states.
+// Layouts (stack_rnn.cpp, time-major): Z [T][B][H], St [T+1][B][H] with row block 0 = the initial states.
 #include <algorithm>
 
 #include "common.hpp"

@@ -1,0 +1,555 @@
+// The one-call entry points for ffLayer stacks: to_fflayer_stack_grad / _sgd / _online_sgd / _infer / _induce.
+#include "api_util.hpp"
+#include "stack_util.hpp"
+
+using namespace to;
+
+extern "C" {
+
+// A contraction of the step (row_gemm) with its fused epilogue (bias, act, dact).  A loss head (loss_rows, target,
+// loss_out) and, behind it, a tail (tail_*) on p are wishes: what the kernel taking p cannot fuse is dropped.  Returns the
+// problem as launched: loss_rows still set means C holds dz instead of z, tail_out still set that the tail was produced.
+static GemmProblem fused_gemm(GemmProblem p) {
+  // latency-bound shapes (incl. the tiny ones of a one-sample step) run on the small-GEMM kernel: it carries
+  // every fused epilogue for both element types (the tiled fp64 kernel has none)
+  const bool small = gemm_small_takes(p);
+  if (!small || !gemm_small_fuses_loss(p)) { p.loss_rows = 0; p.target = nullptr; p.loss_out = nullptr; }
+  if (!p.loss_rows || !p.tail_out || !gemm_small_fuses_tail(p, p.tail_n)) {
+    p.tail_w = p.tail_h = nullptr; p.tail_out = nullptr; p.tail_n = 0; p.tail_kind = 0;
+  }
+  // the tiled fp64 kernel has no fused epilogue: the caller (the trainer) falls back to the generic path
+  TO_CHECK(small || p.dtype == TO_F32, TO_ERR_UNSUPPORTED, "pre-fused fp64 path: a contraction is outside the small-GEMM range");
+  if (small) launch_gemm_small(p, S());
+  else launch_gemm_mfma(p, S());
+  return p;
+}
+
+// sgd: gw/gb are the parameters themselves and the weight-gradient launches apply
+// P <- P - rate * gradient in their epilogue (alpha = -rate, beta = 1, Cin = C = W; the bias through the
+// accumulating row sum): the step loses its separate update launch.
+static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                               int loss, to_tensor x, to_tensor y, const to_tensor* gw, const to_tensor* gb,
+                               to_tensor losses, bool sgd, double rate) {
+  require_init();
+  NONNULL(w); NONNULL(b); NONNULL(x); NONNULL(y); NONNULL(gw); NONNULL(gb);
+  TO_CHECK(n_layers >= 1, TO_ERR_ARG, "need at least one layer");
+  for (int l = 0; l < n_layers; ++l) { NONNULL(w[l]); NONNULL(b[l]); NONNULL(gw[l]); NONNULL(gb[l]); }
+  const int hk = stack_hidden_act_check(hidden_act);
+  const int head_kind = stack_loss_head(out_act, loss, "fused path: ");
+  TO_CHECK(x->rank == 1 && y->rank == 1 && x->batch > 0 && x->batch == y->batch, TO_ERR_SHAPE,
+           "x and y must be batched vectors with the same batch, got " + shape_str(x) + " " + shape_str(y));
+  TO_CHECK(x->contiguous() && y->contiguous(), TO_ERR_ARG, "x and y must be contiguous");
+  const int dt = x->dtype;
+  TO_CHECK(y->dtype == dt, TO_ERR_ARG, "x and y have different dtypes");
+  const int64_t B = x->batch;
+  const int64_t fan_in = stack_params_check(n_layers, w, b, gw, gb, dt, x->dims[0]);
+  TO_CHECK(y->dims[0] == fan_in, TO_ERR_SHAPE, "y does not match the output layer");
+  if (losses) TO_CHECK(losses->rank == 0 && losses->batch == B && losses->contiguous(), TO_ERR_SHAPE,
+                       "losses must be a batched scalar");
+  // The weight gradient of layer l (dz_l^T . a_in, + its row sums = the bias gradient) as a GEMM problem:
+  // A element (i,k) = dz[k*n + i], B element (k,j) = a_in[k*m + j]
+  auto wgrad = [&](int l, const void* dz, const void* a_in) {
+    const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
+    GemmProblem p = row_gemm(dt, dz, 1, n, a_in, m, 1, gw[l]->ptr, n, m, B);
+    p.rowsum = gb[l]->ptr;
+    if (sgd) {
+      p.alpha = -rate; p.beta = 1.0; p.Cin = w[l]->ptr;
+      p.rowsum_acc = true; p.rowsum_alpha = -rate;
+    }
+    return p;
+  };
+  if (sgd)  // nothing may be half-updated: every weight gradient must be one small-GEMM launch
+    for (int l = 0; l < n_layers; ++l)
+      TO_CHECK(gemm_small_takes(wgrad(l, nullptr, nullptr)), TO_ERR_UNSUPPORTED,
+               "fused SGD step: a weight gradient is outside the small-GEMM range");
+
+  // ---- operands produced; destinations claimed -----------------------------------------------------------------------
+  ensure(x);
+  ensure(y);
+  if (losses) { ensure(losses); before_write(losses); }
+  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); ensure(gw[l]); ensure(gb[l]); }
+  for (int l = 0; l < n_layers; ++l) {  // (identities: sgd's parameters get a new one, grad's destinations keep theirs)
+    before_write(gw[l]);
+    before_write(gb[l]);
+    if (sgd) { w[l]->id = fresh_id(); b[l]->id = fresh_id(); }
+  }
+  static const int fuse_tail = [] { const char* e = ab_getenv("TOPS_STEP_FUSE_TAIL"); return e ? atoi(e) : 1; }();
+  Holder tail;  // dz_{L-1} when the last layer's launch produced it
+  GemmProblem fwd{};  // the last layer's launch
+  // forward: a_l = act(a_{l-1} W_l^T + b_l) for hidden layers (act: hidden_act), z_L for the last
+  std::vector<Holder> act(n_layers);  // act[l]: [B; n_l]; the last holds z_L, then is reused as dz_L
+  const void* prev = x->ptr;
+  int64_t prev_n = x->dims[0];
+  for (int l = 0; l < n_layers; ++l) {
+    const int64_t n = w[l]->dims[0];
+    act[l].t = new_tensor(1, &n, B, dt);
+    // C[B,n] = A[B,prev_n] . W^T : B operand element (k, j) = W[j*prev_n + k]
+    // (last layer: the loss head runs in the same launch when the row fits one 16-wide tile)
+    const bool last = l + 1 == n_layers;
+    GemmProblem p = row_gemm(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, act[l].t->ptr, B, n, prev_n);
+    p.bias = b[l]->ptr;
+    p.act = last ? 0 : hk + 1;
+    if (last) { p.loss_rows = head_kind; p.target = y->ptr; p.loss_out = losses ? losses->ptr : nullptr; }
+    if (last && n_layers >= 2 && fuse_tail) {
+      // the loss-head launch also produces dz_{L-1} = (dz_L . W_L) * act'(h) for its rows
+      tail.t = new_tensor(1, &prev_n, B, dt);
+      p.tail_w = w[l]->ptr; p.tail_h = act[l - 1].t->ptr; p.tail_out = tail.t->ptr; p.tail_n = (int)prev_n; p.tail_kind = hk;
+    }
+    fwd = fused_gemm(p);
+    prev = act[l].t->ptr;
+    prev_n = n;
+  }
+  // loss gradient wrt z_L, per sample row
+  const int64_t nL = w[n_layers - 1]->dims[0];
+  Holder cur;
+  if (fwd.loss_rows) {
+    cur.t = act[n_layers - 1].t;  // already dz_L
+    act[n_layers - 1].t = nullptr;
+  } else {
+    cur.t = new_tensor(1, &nL, B, dt);
+    launch_loss_grad_rows(dt, act[n_layers - 1].t->ptr, y->ptr, cur.t->ptr, losses ? losses->ptr : nullptr, B, nL,
+                          loss_grad_rows_kind(head_kind), S());
+  }
+  auto a_in = [&](int l) -> const void* { return l > 0 ? act[l - 1].t->ptr : x->ptr; };
+  // backward, phase 1: every dz_l (the propagation reads W_l, which phase 2 may overwrite in place)
+  // dz_{l-1}[B,m] = (dz_l[B,n] . W_l[n,m]) * act'(h), h = act[l-1]  (h (1 - h), or 1 - h h for tanh)
+  std::vector<Holder> dz(n_layers);
+  dz[n_layers - 1].t = cur.take();
+  for (int l = n_layers - 1; l > 0; --l) {
+    const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
+    if (l == n_layers - 1 && fwd.tail_out) {
+      dz[l - 1].t = tail.take();  // came out of the loss-head launch
+    } else {
+      dz[l - 1].t = new_tensor(1, &m, B, dt);
+      GemmProblem q = row_gemm(dt, dz[l].t->ptr, n, 1, w[l]->ptr, m, 1, dz[l - 1].t->ptr, B, m, n);
+      q.dact = act[l - 1].t->ptr;
+      q.dact_kind = hk;
+      fused_gemm(q);
+    }
+  }
+  // phase 2: the weight gradients, independent of each other.  The two last ones go out as ONE launch when
+  // their shapes allow (one launch floor, ~4 us, less per step: 33.6 -> 28.0 us on config 3).
+  // (Running them on a side stream instead measured slower: the fork/join events cost more than the overlap
+  // buys, 0.0485 -> 0.0591 ms/step.)
+  // one sample: every weight gradient is an outer product -- all layers in one launch
+  static const int rank1 = [] { const char* e = ab_getenv("TOPS_STEP_RANK1"); return e ? atoi(e) : 1; }();
+  if (B == 1 && rank1) {
+    for (int l0 = 0; l0 < n_layers; l0 += RANK1_MAX_LAYERS) {
+      const int cnt = std::min(RANK1_MAX_LAYERS, n_layers - l0);
+      const void *dzp[RANK1_MAX_LAYERS], *ap[RANK1_MAX_LAYERS];
+      void *wp[RANK1_MAX_LAYERS], *bp[RANK1_MAX_LAYERS];
+      int64_t rows[RANK1_MAX_LAYERS], cols[RANK1_MAX_LAYERS];
+      for (int q = 0; q < cnt; ++q) {
+        const int l = l0 + q;
+        dzp[q] = dz[l].t->ptr;
+        ap[q] = a_in(l);
+        wp[q] = gw[l]->ptr;
+        bp[q] = gb[l]->ptr;
+        rows[q] = w[l]->dims[0];
+        cols[q] = w[l]->dims[1];
+      }
+      launch_rank1_many(dt, cnt, dzp, ap, wp, bp, rows, cols, sgd ? -rate : 1.0, sgd, S());
+    }
+    return;
+  }
+  int first = n_layers - 1;
+  if (n_layers >= 2 &&
+      launch_gemm_small_pair(wgrad(n_layers - 2, dz[n_layers - 2].t->ptr, a_in(n_layers - 2)),
+                             wgrad(n_layers - 1, dz[n_layers - 1].t->ptr, a_in(n_layers - 1)), S()))
+    first = n_layers - 3;
+  for (int l = first; l >= 0; --l) {
+    const GemmProblem p = wgrad(l, dz[l].t->ptr, a_in(l));
+    if (gemm_small_takes(p)) {
+      launch_gemm_small(p, S());
+      continue;
+    }
+    TO_CHECK(dt == TO_F32, TO_ERR_UNSUPPORTED, "pre-fused fp64 path: a contraction is outside the small-GEMM range");
+    GemmProblem q = p;
+    q.rowsum = nullptr;
+    launch_gemm_mfma(q, S());
+    launch_sum_axis(dt, dz[l].t->ptr, gb[l]->ptr, 1, B, w[l]->dims[0], 0, w[l]->dims[0], 1, S());
+  }
+}
+
+to_status to_fflayer_stack_grad(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act,
+                                int out_act, int loss, to_tensor x, to_tensor y, const to_tensor* gw,
+                                const to_tensor* gb, to_tensor losses) {
+  API_BEGIN
+  fflayer_stack_impl(n_layers, w, b, hidden_act, out_act, loss, x, y, gw, gb, losses, false, 0.0);
+  API_END
+}
+
+to_status to_fflayer_stack_sgd(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                               int loss, to_tensor x, to_tensor y, double rate, to_tensor losses) {
+  API_BEGIN
+  fflayer_stack_impl(n_layers, w, b, hidden_act, out_act, loss, x, y, w, b, losses, true, rate);
+  API_END
+}
+
+// `foldl' trainNetwork` over samples (app/MNIST.hs:390-396) of an ffLayer stack as ONE persistent launch.
+static void online_sgd_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss,
+                            to_tensor X, to_tensor Y, int64_t n_idx, const int64_t* idx, double rate) {
+  require_init();
+  no_capture("to_fflayer_stack_online_sgd");
+  NONNULL(w); NONNULL(b); NONNULL(X); NONNULL(Y);
+  TO_CHECK(n_layers >= 2 && n_layers <= 6, TO_ERR_UNSUPPORTED, "online SGD kernel: 2..6 layers");
+  const int hk = stack_hidden_act_check(hidden_act, "online SGD kernel: ");
+  const int head = stack_loss_head(out_act, loss, "online SGD kernel: ");
+  TO_CHECK(X->rank == 1 && Y->rank == 1 && X->batch > 0 && X->batch == Y->batch && X->contiguous() && Y->contiguous(),
+           TO_ERR_SHAPE, "X and Y must be contiguous batched vectors of one batch, got " + shape_str(X) + " " + shape_str(Y));
+  const int dt = X->dtype;
+  TO_CHECK(Y->dtype == dt, TO_ERR_ARG, "X and Y have different dtypes");
+  TO_CHECK(n_idx >= 0, TO_ERR_ARG, "negative sample count");
+  TO_CHECK(Y->dims[0] == stack_params_check(n_layers, w, b, nullptr, nullptr, dt, X->dims[0]), TO_ERR_SHAPE,
+           "Y does not match the output layer");
+  int64_t dims[8];
+  dims[0] = X->dims[0];
+  for (int l = 0; l < n_layers; ++l) dims[l + 1] = w[l]->dims[0];
+  int G = 0, rpw = 0;
+  size_t lds = 0;
+  TO_CHECK(online_sgd_plan(dt, n_layers, dims, &G, &rpw, &lds), TO_ERR_UNSUPPORTED,
+           "online SGD kernel: the stack does not fit (input <= 2048, head <= 64 outputs, 160 KiB of LDS per workgroup)");
+  for (int64_t k = 0; k < n_idx; ++k)
+    TO_CHECK(!idx || (idx[k] >= 0 && idx[k] < X->batch), TO_ERR_SHAPE, "sample index out of range");
+  TO_CHECK(idx || n_idx <= X->batch, TO_ERR_SHAPE, "more samples than rows");
+  ensure(X);
+  ensure(Y);
+  void *wp[6], *bp[6];
+  for (int l = 0; l < n_layers; ++l) {  // in-place writes: recorded readers of the old values first, new identities after
+    claim(w[l]);
+    claim(b[l]);
+    wp[l] = w[l]->ptr;
+    bp[l] = b[l]->ptr;
+  }
+  if (n_idx > 0) run_online_sgd(dt, n_layers, dims, wp, bp, X, Y, idx, n_idx, rate, head, hk);
+}
+
+to_status to_fflayer_stack_online_sgd(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                      int loss, to_tensor X, to_tensor Y, int64_t n_idx, const int64_t* idx_or_null,
+                                      double rate) {
+  API_BEGIN
+  online_sgd_impl(n_layers, w, b, hidden_act, out_act, loss, X, Y, n_idx, idx_or_null, rate);
+  API_END
+}
+
+// `runNetwork` (FeedForward.hs:123-129) of an ffLayer stack over a batch and the folds of `validate` / `confusion`
+// (app/MNIST.hs:366-389).  Hidden layers: one GEMM each, bias + activation (logistic / tanh) in its epilogue where the kernel carries one,
+// else a plain GEMM and one elementwise launch.  The head (infer_head.hip): n_L <= 32 the last layer's contraction and
+// everything after it in one launch; wider, the last GEMM into scratch (or `out` itself) and one row launch.
+static void fflayer_stack_infer_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                     to_tensor x, to_tensor y, to_tensor out, int64_t* classes, int64_t* confusion) {
+  require_init();
+  no_capture("to_fflayer_stack_infer");
+  NONNULL(w); NONNULL(b); NONNULL(x);
+  TO_CHECK(n_layers >= 1, TO_ERR_ARG, "need at least one layer");
+  TO_CHECK(out || classes || confusion, TO_ERR_ARG, "infer: no output asked for (out, classes or confusion)");
+  TO_CHECK(!confusion || y, TO_ERR_ARG, "infer: the confusion matrix needs the targets y");
+  const int hk = stack_hidden_act_check(hidden_act);
+  TO_CHECK(out_act == TO_ACT_SOFTMAX || out_act == TO_ACT_LOGISTIC, TO_ERR_UNSUPPORTED,
+           "infer: the output activation must be softmax or logistic");
+  TO_CHECK(x->rank == 1 && x->dims[0] >= 1, TO_ERR_SHAPE, "infer: x must be a (batched) vector, got " + shape_str(x));
+  const int dt = x->dtype;
+  const int64_t nL = stack_params_check(n_layers, w, b, nullptr, nullptr, dt, x->dims[0]);
+  const int64_t B = x->batch > 0 ? x->batch : 1;
+  if (y) {
+    TO_CHECK(y->dtype == dt, TO_ERR_ARG, "infer: x and y have different dtypes");
+    TO_CHECK(y->rank == 1 && y->dims[0] == nL && y->batch == x->batch, TO_ERR_SHAPE,
+             "infer: y must be " + std::to_string(nL) + "-vectors of x's batch, got " + shape_str(y));
+  }
+  if (out) {
+    TO_CHECK(out->dtype == dt, TO_ERR_ARG, "infer: x and out have different dtypes");
+    TO_CHECK(out->rank == 1 && out->dims[0] == nL && out->batch == x->batch, TO_ERR_SHAPE,
+             "infer: out must be " + std::to_string(nL) + "-vectors of x's batch, got " + shape_str(out));
+    TO_CHECK(out->contiguous(), TO_ERR_ARG, "infer: out must be contiguous");
+  }
+  ensure(x);
+  if (y) ensure(y);
+  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); }
+  if (out) claim(out);
+  // rows with unit element stride (a strided vector view is packed first); the rows themselves may lie anywhere
+  Holder xc, yc;
+  const to_tensor xr = unit_stride_rows(x, xc), yr = unit_stride_rows(y, yc);
+  const int64_t x_sm = x->batch > 0 ? xr->bstride : 0;
+  const int64_t y_sm = y && y->batch > 0 ? yr->bstride : 0;
+  // C[B, n] = A[B, K] . W^T : B operand element (k, j) = W[j*K + k]
+  auto layer = [&](const void* A, int64_t a_sm, to_tensor W, void* C) {
+    return row_gemm(dt, A, a_sm, 1, W->ptr, 1, W->dims[1], C, B, W->dims[0], W->dims[1]);
+  };
+  std::vector<Holder> act(n_layers);
+  const void* prev = xr->ptr;
+  int64_t prev_sm = x_sm;
+  for (int l = 0; l + 1 < n_layers; ++l) {
+    const int64_t n = w[l]->dims[0];
+    act[l].t = new_tensor(1, &n, B, dt);
+    GemmProblem p = layer(prev, prev_sm, w[l], act[l].t->ptr);
+    p.bias = b[l]->ptr;
+    p.act = hk + 1;
+    if (gemm_epilogue_ok(p)) {
+      if (gemm_small_route(p)) launch_gemm_small(p, S());
+      else run_gemm(p);
+    } else {  // (the tiled fp64 kernel: alpha / beta only)
+      p.bias = nullptr;
+      p.act = 0;
+      run_gemm(p);
+      launch_bias_act_rows(dt, act[l].t->ptr, b[l]->ptr, B, n, hk, S());
+    }
+    prev = act[l].t->ptr;
+    prev_sm = n;
+  }
+  const to_tensor WL = w[n_layers - 1], bL = b[n_layers - 1];
+  Holder cls, conf, z;
+  if (classes) cls.t = new_tensor(1, &B, 0);  // B int32 in a float-typed pool buffer
+  if (confusion) {
+    const int64_t nl = nL * nL * 2;              // n_L^2 uint64
+    conf.t = new_tensor(1, &nl, 0);
+    TO_HIP(hipMemsetAsync(conf.t->ptr, 0, (size_t)(nL * nL) * 8, S()));
+  }
+  int* cls_p = cls.t ? static_cast<int*>(cls.t->ptr) : nullptr;
+  auto* conf_p = conf.t ? static_cast<unsigned long long*>(conf.t->ptr) : nullptr;
+  void* out_p = out ? out->ptr : nullptr;
+  const void* y_p = y ? yr->ptr : nullptr;
+  const bool softmax = out_act == TO_ACT_SOFTMAX;
+  if (nL <= INFER_NARROW_MAX) {
+    launch_infer_narrow(dt, prev, prev_sm, B, WL->dims[1], WL->ptr, bL->ptr, (int)nL, softmax, out_p, y_p, y_sm, cls_p,
+                        conf_p, S());
+  } else {
+    void* zp = out_p;  // the row launch reads each element of z before it writes the same element of out
+    if (!zp) {
+      z.t = new_tensor(1, &nL, B, dt);
+      zp = z.t->ptr;
+    }
+    run_gemm(layer(prev, prev_sm, WL, zp));
+    TO_CHECK(nL <= 2147483647LL, TO_ERR_SHAPE, "infer: output layer too wide");
+    launch_infer_rows(dt, zp, B, bL->ptr, (int)nL, softmax, out_p, y_p, y_sm, cls_p, conf_p, S());
+  }
+  if (classes) {
+    std::vector<int32_t> ids((size_t)B);
+    device_to_host(ids.data(), cls_p, (size_t)B * sizeof(int32_t), S());
+    for (int64_t r = 0; r < B; ++r) classes[r] = ids[(size_t)r];
+  }
+  if (confusion) device_to_host(confusion, conf_p, (size_t)(nL * nL) * sizeof(int64_t), S());
+}
+
+to_status to_fflayer_stack_infer(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                 to_tensor x, to_tensor y_or_null, to_tensor out_or_null, int64_t* classes_or_null,
+                                 int64_t* confusion_or_null) {
+  API_BEGIN
+  fflayer_stack_infer_impl(n_layers, w, b, hidden_act, out_act, x, y_or_null, out_or_null, classes_or_null,
+                           confusion_or_null);
+  API_END
+}
+
+// ---- `induceNetwork` iterated (FeedForward.hs:150-164; app/MNIST.hs:357-365: 5000 dependent steps on the input) --------
+// Route A, per iteration: the forward of to_fflayer_stack_infer, launch_loss_grad_rows, the cotangents back through the
+// layers and the last contraction with the step in its epilogue (x <- 1 x + (-rate) dz_1 W_1: alpha = -rate, beta = 1,
+// Cin = C = x; when gx is wanted the last iteration runs the plain product as well, into gx).  Takes every valid stack; its launch count grows with iters.  Route B, persistent (induce_seq.hip): all
+// iterations of all rows in ONE launch, where its plan fits (and, for a plan of several workgroups a row, where the
+// placement probe holds).  Both iterate on a private copy of x; the caller's tensors are written once, at the end.
+static int g_induce_persistent = 1;                       // to_set_induce_persistent: 0 per iteration, 1 auto, 2 wherever in range
+static int64_t g_induce_persistent_runs = 0, g_induce_iter_runs = 0;
+
+// The automatic rule.  NOT MEASURED YET: tools/induce_scan.py has not been run on a device for this change (see
+// profiles/r08_induce_scan.txt and DESIGN.md section 3.3), so the default takes the persistent route only where its
+// advantage follows from counting and needs no measurement to hold: a plan of ONE workgroup a row (no exchange, no
+// placement precondition, nobody to wait for) with at most 256 rows, where every row has a workgroup of its own and an
+// iteration is a handful of passes over LDS against six or more dependent launches on route A.  Plans of several
+// workgroups a row (the reference's 784-300-100-10 in fp32) and longer batches stay on route A by default until the scan
+// has been run and says otherwise; to_set_induce_persistent(2) forces them.
+static bool induce_auto_persistent(const InduceSeqPlan& plan, int64_t B) {
+  return plan.G == 1 && B <= 256;
+}
+
+static void induce_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss,
+                        to_tensor x, to_tensor y, double rate, int64_t iters, to_tensor out, to_tensor gx, to_tensor losses) {
+  const std::string F = "to_fflayer_stack_induce: ";
+  require_init();
+  no_capture("to_fflayer_stack_induce");
+  NONNULL(w); NONNULL(b); NONNULL(x); NONNULL(y); NONNULL(out);
+  TO_CHECK(n_layers >= 1, TO_ERR_ARG, F + "need at least one layer");
+  TO_CHECK(iters >= 0, TO_ERR_ARG, F + "negative iteration count");
+  TO_CHECK(!gx || iters >= 1, TO_ERR_ARG, F + "gx is the gradient of the last iteration: it needs iters >= 1");
+  const int hk = stack_hidden_act_check(hidden_act);
+  const int head = stack_loss_head(out_act, loss, F);
+  TO_CHECK(x->rank == 1 && x->dims[0] >= 1, TO_ERR_SHAPE, F + "x must be a (batched) vector, got " + shape_str(x));
+  const int dt = x->dtype;
+  const int64_t i0 = x->dims[0];
+  const int64_t nL = stack_params_check(n_layers, w, b, nullptr, nullptr, dt, i0);
+  const int64_t B = x->batch > 0 ? x->batch : 1;
+  TO_CHECK(y->dtype == dt, TO_ERR_ARG, F + "x and y have different dtypes");
+  TO_CHECK(y->rank == 1 && y->dims[0] == nL && (y->batch == 0 || y->batch == x->batch), TO_ERR_SHAPE,
+           F + "y must be " + std::to_string(nL) + "-vectors of x's batch (or one unbatched target), got " + shape_str(y));
+  auto like_x = [&](to_tensor t, const char* what) {
+    TO_CHECK(t->dtype == dt, TO_ERR_ARG, F + "x and " + what + " have different dtypes");
+    TO_CHECK(t->rank == 1 && t->dims[0] == i0 && t->batch == x->batch, TO_ERR_SHAPE,
+             F + what + " must have x's shape and batch, got " + shape_str(t));
+    TO_CHECK(t->contiguous(), TO_ERR_ARG, F + what + " must be contiguous");
+  };
+  like_x(out, "out");
+  if (gx) like_x(gx, "gx");
+  if (losses) {
+    TO_CHECK(losses->dtype == dt, TO_ERR_ARG, F + "x and losses have different dtypes");
+    TO_CHECK(losses->rank == 1 && losses->dims[0] == iters && losses->batch == x->batch, TO_ERR_SHAPE,
+             F + "losses must be [B; " + std::to_string(iters) + "] of x's batch, got " + shape_str(losses));
+    TO_CHECK(losses->contiguous(), TO_ERR_ARG, F + "losses must be contiguous");
+  }
+  TO_CHECK(B <= 2147483647LL && B * i0 <= (1LL << 40), TO_ERR_SHAPE, F + "too many rows");
+
+  // ---- operands produced; destinations claimed -----------------------------------------------------------------------
+  ensure(x);
+  ensure(y);
+  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); }
+  const int64_t es = dt == TO_F64 ? 8 : 4;
+  if (iters == 0) {  // x to out bit for bit; nothing else is touched, neither route counted
+    if (out != x) {
+      claim(out);
+      if (out->ptr != x->ptr) {
+        const int64_t dd[2] = {B, i0}, ss[2] = {x->batch > 0 ? x->bstride : 0, x->strides[0]};
+        launch_copy_strided(dt, x->ptr, out->ptr, 2, dd, ss, S());
+      }
+    }
+    TO_HIP(hipStreamSynchronize(S()));
+    return;
+  }
+  claim(out);
+  if (gx) claim(gx);
+  if (losses) claim(losses);
+
+  // the private copy of x the iterations run on, contiguous [B][i0]
+  const int64_t dx[2] = {B, i0};
+  Holder cur(new_tensor(2, dx, 0, dt));
+  {
+    const int64_t ss[2] = {x->batch > 0 ? x->bstride : 0, x->strides[0]};
+    launch_copy_strided(dt, x->ptr, cur.t->ptr, 2, dx, ss, S());
+  }
+  Holder gxs, lt;
+  if (gx) gxs.t = new_tensor(2, dx, 0, dt);
+  const int64_t dl[2] = {B, iters};
+  if (losses) lt.t = new_tensor(2, dl, 0, dt);
+  // targets with unit element stride; rows y_sm apart (0: one target for every row)
+  Holder yc;
+  const to_tensor yr = unit_stride_rows(y, yc);
+  const int64_t y_sm = y->batch > 0 ? yr->bstride : 0;
+
+  int64_t dims[INDUCE_MAX_LAYERS + 1] = {0};
+  InduceSeqPlan plan;
+  bool persistent = false;
+  if (g_induce_persistent != 0 && n_layers <= INDUCE_MAX_LAYERS) {
+    dims[0] = i0;
+    for (int l = 0; l < n_layers; ++l) dims[l + 1] = w[l]->dims[0];
+    persistent = induce_seq_plan(dt, n_layers, dims, B, iters, &plan) &&
+                 (g_induce_persistent == 2 || induce_auto_persistent(plan, B)) &&
+                 (plan.G == 1 || online_sgd_placement_ok(S()));   // (the exchange's precondition: one XCD's L2)
+  }
+
+  if (persistent) {
+    const void *wp[INDUCE_MAX_LAYERS], *bp[INDUCE_MAX_LAYERS];
+    for (int l = 0; l < n_layers; ++l) { wp[l] = w[l]->ptr; bp[l] = b[l]->ptr; }
+    launch_induce_seq(dt, plan, n_layers, dims, wp, bp, cur.t->ptr, yr->ptr, y_sm, gxs.t ? gxs.t->ptr : nullptr,
+                      lt.t ? lt.t->ptr : nullptr, B, iters, rate, head, hk, S());
+    TO_HIP(hipStreamSynchronize(S()));   // the watchdog's verdict is read before anything of the caller's is written
+    int64_t bad_row = 0;
+    const int64_t bad = induce_seq_status(&bad_row);
+    TO_CHECK(bad == 0, TO_ERR_HIP,
+             F + "the persistent kernel gave up waiting for a workgroup at iteration " + std::to_string(bad - 1) + " of row " +
+                 std::to_string(bad_row) + " (out, gx and losses are untouched)");
+    g_induce_persistent_runs++;
+  } else {
+    // route A.  y as [B][nL] rows (launch_loss_grad_rows reads one target per row)
+    Holder yt;
+    const void* yp = yr->ptr;
+    if (B > 1 && (y->batch == 0 || y_sm != nL)) {
+      const int64_t dy[2] = {B, nL};
+      yt.t = new_tensor(2, dy, 0, dt);
+      if (y->batch == 0) {
+        launch_bcast_axis(dt, yr->ptr, yt.t->ptr, 1, B, nL, 0, S());
+      } else {
+        const int64_t ss[2] = {y_sm, 1};
+        launch_copy_strided(dt, yr->ptr, yt.t->ptr, 2, dy, ss, S());
+      }
+      yp = yt.t->ptr;
+    }
+    std::vector<Holder> act(n_layers), dz(n_layers);   // act[l]: [B][n_l], the last one z_L; dz[l]: the cotangent of z_l
+    for (int l = 0; l < n_layers; ++l) {
+      const int64_t d2[2] = {B, w[l]->dims[0]};
+      act[l].t = new_tensor(2, d2, 0, dt);
+      dz[l].t = new_tensor(2, d2, 0, dt);
+    }
+    Holder lcol;   // losses as [iters][B]: column k of the caller's [B][iters] is one contiguous run here
+    if (losses) {
+      const int64_t d2[2] = {iters, B};
+      lcol.t = new_tensor(2, d2, 0, dt);
+    }
+    void* xp = cur.t->ptr;
+    for (int64_t k = 0; k < iters; ++k) {
+      const void* prev = xp;
+      int64_t prev_n = i0;
+      for (int l = 0; l < n_layers; ++l) {   // a_l = hidden_act(a_{l-1} W_l^T + b_l); the last layer: z_L
+        const int64_t n = w[l]->dims[0];
+        GemmProblem p = row_gemm(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, act[l].t->ptr, B, n, prev_n);
+        p.bias = b[l]->ptr;
+        if (l + 1 < n_layers) p.act = hk + 1;
+        gemm_with_epilogue(p);
+        prev = act[l].t->ptr;
+        prev_n = n;
+      }
+      launch_loss_grad_rows(dt, act[n_layers - 1].t->ptr, yp, dz[n_layers - 1].t->ptr, lcol.t ? at(lcol.t->ptr, k * B, es) : nullptr,
+                            B, nL, loss_grad_rows_kind(head), S());
+      for (int l = n_layers - 1; l > 0; --l) {   // dz_{l-1} = (dz_l W_l) (.) hidden_act'(a_{l-1})
+        const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
+        GemmProblem q = row_gemm(dt, dz[l].t->ptr, n, 1, w[l]->ptr, m, 1, dz[l - 1].t->ptr, B, m, n);
+        q.dact = act[l - 1].t->ptr;
+        q.dact_kind = hk;
+        gemm_with_epilogue(q);
+      }
+      const int64_t n1 = w[0]->dims[0];
+      GemmProblem q = row_gemm(dt, dz[0].t->ptr, n1, 1, w[0]->ptr, i0, 1, xp, B, i0, n1);
+      if (gx && k + 1 == iters) {
+        // the plain product is wanted too: one more contraction, once a call.  The step itself is taken by the SAME launch
+        // as in every other iteration (below), so that out's bits do not depend on whether gx was asked for -- an axpy
+        // behind the plain product would round alpha * acc + x differently from the epilogue
+        GemmProblem qg = q;
+        qg.C = gxs.t->ptr;
+        gemm_with_epilogue(qg);
+      }
+      q.alpha = -rate;   // x <- 1 x + (-rate) dz_1 W_1 in the contraction's epilogue
+      q.beta = 1.0;
+      q.Cin = xp;
+      gemm_with_epilogue(q);
+    }
+    if (losses) {   // [iters][B] -> [B][iters]
+      const int64_t ss[2] = {1, B};
+      launch_copy_strided(dt, lcol.t->ptr, lt.t->ptr, 2, dl, ss, S());
+    }
+    g_induce_iter_runs++;
+  }
+  TO_HIP(hipMemcpyAsync(out->ptr, cur.t->ptr, (size_t)(B * i0 * es), hipMemcpyDeviceToDevice, S()));
+  if (gx) TO_HIP(hipMemcpyAsync(gx->ptr, gxs.t->ptr, (size_t)(B * i0 * es), hipMemcpyDeviceToDevice, S()));
+  if (losses) TO_HIP(hipMemcpyAsync(losses->ptr, lt.t->ptr, (size_t)(B * iters * es), hipMemcpyDeviceToDevice, S()));
+  TO_HIP(hipStreamSynchronize(S()));
+}
+
+to_status to_fflayer_stack_induce(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                  int loss, to_tensor x, to_tensor y, double rate, int64_t iters, to_tensor out,
+                                  to_tensor gx_or_null, to_tensor losses_or_null) {
+  API_BEGIN
+  induce_impl(n_layers, w, b, hidden_act, out_act, loss, x, y, rate, iters, out, gx_or_null, losses_or_null);
+  API_END
+}
+
+to_status to_set_induce_persistent(int on, int* previous_or_null) {
+  API_BEGIN
+  TO_CHECK(on >= 0 && on <= 2, TO_ERR_ARG,
+           "to_set_induce_persistent: 0 (per iteration), 1 (automatic) or 2 (wherever in range)");
+  if (previous_or_null) *previous_or_null = g_induce_persistent;
+  g_induce_persistent = on;
+  API_END
+}
+
+to_status to_induce_stats(int64_t* persistent_runs, int64_t* per_iteration_runs) {
+  API_BEGIN
+  if (persistent_runs) *persistent_runs = g_induce_persistent_runs;
+  if (per_iteration_runs) *per_iteration_runs = g_induce_iter_runs;
+  API_END
+}
+
+}  // extern "C"

@@ -338,6 +338,39 @@ to_status to_fflayer_stack_grad(int n_layers, const to_tensor* w, const to_tenso
 to_status to_fflayer_stack_sgd(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
                                int loss, to_tensor x, to_tensor y, double rate, to_tensor losses_or_null);
 
+/* Minibatch SGD over a resident data set -- the loop every caller of to_fflayer_stack_sgd writes around it, and `trainEncoder`
+ * (AutoEncoder.hs:87-110) over minibatches -- in ONE call.  For k = 0 .. ceil(n_idx / minibatch) - 1, in order: rows
+ * idx[k*minibatch .. min((k+1)*minibatch, n_idx)) of X / Y (idx null: rows k*minibatch .. in place) are one batch, and one
+ * to_fflayer_stack_sgd step runs on it: p -= rate * (gradient SUMMED over the batch), parameters updated in place.  The last
+ * batch may be short.  A step's launches are to_fflayer_stack_sgd's for that batch, bit for bit.
+ *   X               [N; i0], contiguous;
+ *   Y_or_null       [N; n_L] of X's batch and dtype, contiguous; null: the target of row r is X's row r itself
+ *                   (reconstruction; needs n_L == i0, TO_ERR_SHAPE otherwise; nothing is gathered twice for it);
+ *   idx_or_null     n_idx entries in [0, N), repeats allowed, also inside one minibatch; the library has its copy when the
+ *                   call returns.  Null: n_idx <= N;
+ *   losses_or_null  contiguous batched scalar of batch n_idx: losses[j] is the loss of row idx[j] under the parameters its
+ *                   step started from, written by the step's loss head itself.
+ * hidden_act, (out_act, loss), dtypes and every other rule are to_fflayer_stack_sgd's (an unsupported pair:
+ * TO_ERR_UNSUPPORTED).  n_idx < 1 or minibatch < 1: TO_ERR_ARG; an index out of range: TO_ERR_SHAPE.  Every refusal is
+ * decided before the first launch -- "a contraction is outside the small-GEMM range" included, for both batch sizes that
+ * occur, the full minibatch and the short tail -- so a refused call leaves parameters and losses untouched.  Pending operands
+ * are produced first; refused during graph capture (TO_ERR_STATE); keeps no handle; does not block beyond what taking the
+ * copy of idx needs (up to 64 KiB of indices ride the pinned ring, stream-ordered; more go through the synchronous staged
+ * transfer).
+ * Routes.  idx given: the rows of a CHUNK of consecutive steps are gathered into a pool buffer by one launch
+ * (csrc/minibatch_stage.hip: X and Y in the same launch, 16-byte pieces per tensor where its rows allow, elements otherwise)
+ * and the chunk's steps run on contiguous slabs of it, each starting on a 16-byte boundary; one stream, so the next chunk
+ * reuses the buffer without an event.  A chunk is as many steps as fit the stage bound, one at least.  idx null: no staging,
+ * the steps run on views of X / Y.
+ * to_set_minibatch_stage_bytes: the stage bound, process-wide; 0 restores the default; returns the previous value.  The
+ * default, 32 MiB, is a guess that has NOT been measured (tools/minibatch_scan.py reports one-step chunks next to it;
+ * DESIGN.md section 3.3). */
+to_status to_fflayer_stack_minibatch_sgd(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                         int loss, to_tensor X, to_tensor Y_or_null, int64_t n_idx,
+                                         const int64_t* idx_or_null, int64_t minibatch, double rate,
+                                         to_tensor losses_or_null);
+to_status to_set_minibatch_stage_bytes(int64_t bytes, int64_t* previous_or_null);
+
 /* Per-sample online SGD -- `foldl' (\nt (i,o) -> trainNetwork loss rate i o nt)` (app/MNIST.hs:390-396,
  * app/Dots.hs:74-80) -- of the same stacks over rows idx[0..n_idx) (null: rows 0..n_idx-1) of the resident batched X / Y,
  * parameters updated in place, as ONE persistent launch: the workgroups keep the parameters in LDS between samples,

@@ -427,6 +427,12 @@ void launch_stack_rows(int n, const void* const* rows, const int64_t* row_sb_dwo
                        int64_t row_dwords, int64_t out_sb_dwords, hipStream_t s);
 void launch_gather_rows(const void* x, void* out, const long long* idx, int64_t n_rows, int64_t row_bytes,
                         hipStream_t s);
+// minibatch_stage.hip: rows idx[r], r < n_rows, of X (and of Y, unless null) into per-step slabs -- row r lands in slab r / M
+// at row r % M -- in one launch; es: the element size; 16-byte pieces per tensor where its rows, slabs and bases allow
+constexpr int64_t MINIBATCH_STAGE_DEFAULT = 32ll << 20;   // to_set_minibatch_stage_bytes(0); a guess, not measured
+void launch_minibatch_stage(const long long* idx, int64_t n_rows, int64_t M, const void* X, void* x_dst, int64_t x_row_bytes,
+                            int64_t x_slab_bytes, const void* Y, void* y_dst, int64_t y_row_bytes, int64_t y_slab_bytes,
+                            int es, hipStream_t s);
 void launch_one_hot(int dtype, void* out, const long long* idx, int64_t B, int64_t n, double hot, double cold,
                     hipStream_t s);
 constexpr int RANK1_MAX_LAYERS = 8;

@@ -6,49 +6,45 @@ using namespace to;
 
 extern "C" {
 
-// A contraction of the step (row_gemm) with its fused epilogue (bias, act, dact).  A loss head (loss_rows, target,
-// loss_out) and, behind it, a tail (tail_*) on p are wishes: what the kernel taking p cannot fuse is dropped.  Returns the
-// problem as launched: loss_rows still set means C holds dz instead of z, tail_out still set that the tail was produced.
-static GemmProblem fused_gemm(GemmProblem p) {
+// A contraction of the step (row_gemm) with its fused epilogue (bias, act, dact).  A loss head (loss_rows) and, behind it, a
+// tail (tail_n) on p are wishes: what the kernel taking p cannot fuse is dropped.  Returns the problem as it will be
+// launched: loss_rows still set means C holds dz instead of z, tail_n still set that the tail is produced.  Decided by the
+// shape alone, and launches nothing: to_fflayer_stack_minibatch_sgd asks it for every problem of its steps beforehand.
+static GemmProblem fused_route(GemmProblem p) {
   // latency-bound shapes (incl. the tiny ones of a one-sample step) run on the small-GEMM kernel: it carries
   // every fused epilogue for both element types (the tiled fp64 kernel has none)
   const bool small = gemm_small_takes(p);
   if (!small || !gemm_small_fuses_loss(p)) { p.loss_rows = 0; p.target = nullptr; p.loss_out = nullptr; }
-  if (!p.loss_rows || !p.tail_out || !gemm_small_fuses_tail(p, p.tail_n)) {
+  if (!p.loss_rows || !p.tail_n || !gemm_small_fuses_tail(p, p.tail_n)) {
     p.tail_w = p.tail_h = nullptr; p.tail_out = nullptr; p.tail_n = 0; p.tail_kind = 0;
   }
   // the tiled fp64 kernel has no fused epilogue: the caller (the trainer) falls back to the generic path
   TO_CHECK(small || p.dtype == TO_F32, TO_ERR_UNSUPPORTED, "pre-fused fp64 path: a contraction is outside the small-GEMM range");
-  if (small) launch_gemm_small(p, S());
+  return p;
+}
+
+static GemmProblem fused_gemm(GemmProblem p) {
+  p = fused_route(p);
+  if (gemm_small_takes(p)) launch_gemm_small(p, S());
   else launch_gemm_mfma(p, S());
   return p;
 }
 
+// One step of a stack -- the gradients of to_fflayer_stack_grad, or (sgd) the `trainNetwork` update -- with everything about
+// it that does not depend on the batch: what fflayer_stack_impl and to_fflayer_stack_minibatch_sgd share.
 // sgd: gw/gb are the parameters themselves and the weight-gradient launches apply
 // P <- P - rate * gradient in their epilogue (alpha = -rate, beta = 1, Cin = C = W; the bias through the
 // accumulating row sum): the step loses its separate update launch.
-static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
-                               int loss, to_tensor x, to_tensor y, const to_tensor* gw, const to_tensor* gb,
-                               to_tensor losses, bool sgd, double rate) {
-  require_init();
-  NONNULL(w); NONNULL(b); NONNULL(x); NONNULL(y); NONNULL(gw); NONNULL(gb);
-  TO_CHECK(n_layers >= 1, TO_ERR_ARG, "need at least one layer");
-  for (int l = 0; l < n_layers; ++l) { NONNULL(w[l]); NONNULL(b[l]); NONNULL(gw[l]); NONNULL(gb[l]); }
-  const int hk = stack_hidden_act_check(hidden_act);
-  const int head_kind = stack_loss_head(out_act, loss, "fused path: ");
-  TO_CHECK(x->rank == 1 && y->rank == 1 && x->batch > 0 && x->batch == y->batch, TO_ERR_SHAPE,
-           "x and y must be batched vectors with the same batch, got " + shape_str(x) + " " + shape_str(y));
-  TO_CHECK(x->contiguous() && y->contiguous(), TO_ERR_ARG, "x and y must be contiguous");
-  const int dt = x->dtype;
-  TO_CHECK(y->dtype == dt, TO_ERR_ARG, "x and y have different dtypes");
-  const int64_t B = x->batch;
-  const int64_t fan_in = stack_params_check(n_layers, w, b, gw, gb, dt, x->dims[0]);
-  TO_CHECK(y->dims[0] == fan_in, TO_ERR_SHAPE, "y does not match the output layer");
-  if (losses) TO_CHECK(losses->rank == 0 && losses->batch == B && losses->contiguous(), TO_ERR_SHAPE,
-                       "losses must be a batched scalar");
+struct StackStep {
+  int n_layers;
+  const to_tensor *w, *b, *gw, *gb;
+  int hk, head_kind, dt;
+  bool sgd;
+  double rate;
+
   // The weight gradient of layer l (dz_l^T . a_in, + its row sums = the bias gradient) as a GEMM problem:
   // A element (i,k) = dz[k*n + i], B element (k,j) = a_in[k*m + j]
-  auto wgrad = [&](int l, const void* dz, const void* a_in) {
+  GemmProblem wgrad(int l, const void* dz, const void* a_in, int64_t B) const {
     const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
     GemmProblem p = row_gemm(dt, dz, 1, n, a_in, m, 1, gw[l]->ptr, n, m, B);
     p.rowsum = gb[l]->ptr;
@@ -57,47 +53,71 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
       p.rowsum_acc = true; p.rowsum_alpha = -rate;
     }
     return p;
-  };
-  if (sgd)  // nothing may be half-updated: every weight gradient must be one small-GEMM launch
-    for (int l = 0; l < n_layers; ++l)
-      TO_CHECK(gemm_small_takes(wgrad(l, nullptr, nullptr)), TO_ERR_UNSUPPORTED,
-               "fused SGD step: a weight gradient is outside the small-GEMM range");
-
-  // ---- operands produced; destinations claimed -----------------------------------------------------------------------
-  ensure(x);
-  ensure(y);
-  if (losses) { ensure(losses); before_write(losses); }
-  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); ensure(gw[l]); ensure(gb[l]); }
-  for (int l = 0; l < n_layers; ++l) {  // (identities: sgd's parameters get a new one, grad's destinations keep theirs)
-    before_write(gw[l]);
-    before_write(gb[l]);
-    if (sgd) { w[l]->id = fresh_id(); b[l]->id = fresh_id(); }
   }
-  static const int fuse_tail = [] { const char* e = ab_getenv("TOPS_STEP_FUSE_TAIL"); return e ? atoi(e) : 1; }();
+  // forward, layer l: C[B,n] = A[B,prev_n] . W^T : B operand element (k, j) = W[j*prev_n + k]; bias and the hidden
+  // activation in the epilogue; the last layer wishes for the loss head and (two layers or more) for the tail
+  // dz_{L-1} = (dz_L . W_L) * act'(h) of its rows in the same launch
+  GemmProblem forward(int l, const void* prev, void* C, int64_t B, const void* y, void* losses, const void* h,
+                      void* tail_out) const {
+    static const int fuse_tail = [] { const char* e = ab_getenv("TOPS_STEP_FUSE_TAIL"); return e ? atoi(e) : 1; }();
+    const int64_t n = w[l]->dims[0], prev_n = w[l]->dims[1];
+    const bool last = l + 1 == n_layers;
+    GemmProblem p = row_gemm(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, C, B, n, prev_n);
+    p.bias = b[l]->ptr;
+    p.act = last ? 0 : hk + 1;
+    if (last) { p.loss_rows = head_kind; p.target = y; p.loss_out = losses; }
+    if (last && n_layers >= 2 && fuse_tail) {
+      p.tail_w = w[l]->ptr; p.tail_h = h; p.tail_out = tail_out; p.tail_n = (int)prev_n; p.tail_kind = hk;
+    }
+    return p;
+  }
+  bool wants_tail() const { return forward(n_layers - 1, nullptr, nullptr, 1, nullptr, nullptr, nullptr, nullptr).tail_n != 0; }
+  // dz_{l-1}[B,m] = (dz_l[B,n] . W_l[n,m]) * act'(h), h = act[l-1]  (h (1 - h), or 1 - h h for tanh)
+  GemmProblem backward(int l, const void* dz, const void* h, void* out, int64_t B) const {
+    const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
+    GemmProblem q = row_gemm(dt, dz, n, 1, w[l]->ptr, m, 1, out, B, m, n);
+    q.dact = h;
+    q.dact_kind = hk;
+    return q;
+  }
+
+  // nothing may be half-updated: every weight gradient of an sgd step must be one small-GEMM launch
+  void check_wgrads(int64_t B) const {
+    if (!sgd) return;
+    for (int l = 0; l < n_layers; ++l)
+      TO_CHECK(gemm_small_takes(wgrad(l, nullptr, nullptr, B)), TO_ERR_UNSUPPORTED,
+               "fused SGD step: a weight gradient is outside the small-GEMM range");
+  }
+  // Every refusal the launches of an sgd step on B rows can end in, with nothing launched: the same problems in the same
+  // order, their routes decided by fused_route as launch() decides them.
+  void check_sgd(int64_t B) const {
+    check_wgrads(B);
+    GemmProblem fwd{};
+    for (int l = 0; l < n_layers; ++l) fwd = fused_route(forward(l, nullptr, nullptr, B, nullptr, nullptr, nullptr, nullptr));
+    for (int l = n_layers - 1; l > 0; --l)
+      if (!(l == n_layers - 1 && fwd.tail_n)) fused_route(backward(l, nullptr, nullptr, nullptr, B));
+  }
+  void launch(const void* x, const void* y, void* losses, int64_t B) const;
+};
+
+// The launches of one step on the contiguous rows x [B; i0], y [B; n_L] (losses: B scalars, or null).  Operands exist and
+// destinations are claimed.
+void StackStep::launch(const void* x, const void* y, void* losses, int64_t B) const {
   Holder tail;  // dz_{L-1} when the last layer's launch produced it
   GemmProblem fwd{};  // the last layer's launch
   // forward: a_l = act(a_{l-1} W_l^T + b_l) for hidden layers (act: hidden_act), z_L for the last
   std::vector<Holder> act(n_layers);  // act[l]: [B; n_l]; the last holds z_L, then is reused as dz_L
-  const void* prev = x->ptr;
-  int64_t prev_n = x->dims[0];
+  const void* prev = x;
   for (int l = 0; l < n_layers; ++l) {
-    const int64_t n = w[l]->dims[0];
+    const int64_t n = w[l]->dims[0], prev_n = w[l]->dims[1];
     act[l].t = new_tensor(1, &n, B, dt);
-    // C[B,n] = A[B,prev_n] . W^T : B operand element (k, j) = W[j*prev_n + k]
-    // (last layer: the loss head runs in the same launch when the row fits one 16-wide tile)
+    // (last layer: the loss head runs in the same launch when the row fits one 16-wide tile; it also produces
+    //  dz_{L-1} for its rows where the tail fuses)
     const bool last = l + 1 == n_layers;
-    GemmProblem p = row_gemm(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, act[l].t->ptr, B, n, prev_n);
-    p.bias = b[l]->ptr;
-    p.act = last ? 0 : hk + 1;
-    if (last) { p.loss_rows = head_kind; p.target = y->ptr; p.loss_out = losses ? losses->ptr : nullptr; }
-    if (last && n_layers >= 2 && fuse_tail) {
-      // the loss-head launch also produces dz_{L-1} = (dz_L . W_L) * act'(h) for its rows
-      tail.t = new_tensor(1, &prev_n, B, dt);
-      p.tail_w = w[l]->ptr; p.tail_h = act[l - 1].t->ptr; p.tail_out = tail.t->ptr; p.tail_n = (int)prev_n; p.tail_kind = hk;
-    }
-    fwd = fused_gemm(p);
+    if (last && wants_tail()) tail.t = new_tensor(1, &prev_n, B, dt);
+    fwd = fused_gemm(forward(l, prev, act[l].t->ptr, B, y, losses, l > 0 ? act[l - 1].t->ptr : nullptr,
+                             tail.t ? tail.t->ptr : nullptr));
     prev = act[l].t->ptr;
-    prev_n = n;
   }
   // loss gradient wrt z_L, per sample row
   const int64_t nL = w[n_layers - 1]->dims[0];
@@ -107,24 +127,19 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
     act[n_layers - 1].t = nullptr;
   } else {
     cur.t = new_tensor(1, &nL, B, dt);
-    launch_loss_grad_rows(dt, act[n_layers - 1].t->ptr, y->ptr, cur.t->ptr, losses ? losses->ptr : nullptr, B, nL,
-                          loss_grad_rows_kind(head_kind), S());
+    launch_loss_grad_rows(dt, act[n_layers - 1].t->ptr, y, cur.t->ptr, losses, B, nL, loss_grad_rows_kind(head_kind), S());
   }
-  auto a_in = [&](int l) -> const void* { return l > 0 ? act[l - 1].t->ptr : x->ptr; };
+  auto a_in = [&](int l) -> const void* { return l > 0 ? act[l - 1].t->ptr : x; };
   // backward, phase 1: every dz_l (the propagation reads W_l, which phase 2 may overwrite in place)
-  // dz_{l-1}[B,m] = (dz_l[B,n] . W_l[n,m]) * act'(h), h = act[l-1]  (h (1 - h), or 1 - h h for tanh)
   std::vector<Holder> dz(n_layers);
   dz[n_layers - 1].t = cur.take();
   for (int l = n_layers - 1; l > 0; --l) {
-    const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
     if (l == n_layers - 1 && fwd.tail_out) {
       dz[l - 1].t = tail.take();  // came out of the loss-head launch
     } else {
+      const int64_t m = w[l]->dims[1];
       dz[l - 1].t = new_tensor(1, &m, B, dt);
-      GemmProblem q = row_gemm(dt, dz[l].t->ptr, n, 1, w[l]->ptr, m, 1, dz[l - 1].t->ptr, B, m, n);
-      q.dact = act[l - 1].t->ptr;
-      q.dact_kind = hk;
-      fused_gemm(q);
+      fused_gemm(backward(l, dz[l].t->ptr, act[l - 1].t->ptr, dz[l - 1].t->ptr, B));
     }
   }
   // phase 2: the weight gradients, independent of each other.  The two last ones go out as ONE launch when
@@ -154,11 +169,11 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
   }
   int first = n_layers - 1;
   if (n_layers >= 2 &&
-      launch_gemm_small_pair(wgrad(n_layers - 2, dz[n_layers - 2].t->ptr, a_in(n_layers - 2)),
-                             wgrad(n_layers - 1, dz[n_layers - 1].t->ptr, a_in(n_layers - 1)), S()))
+      launch_gemm_small_pair(wgrad(n_layers - 2, dz[n_layers - 2].t->ptr, a_in(n_layers - 2), B),
+                             wgrad(n_layers - 1, dz[n_layers - 1].t->ptr, a_in(n_layers - 1), B), S()))
     first = n_layers - 3;
   for (int l = first; l >= 0; --l) {
-    const GemmProblem p = wgrad(l, dz[l].t->ptr, a_in(l));
+    const GemmProblem p = wgrad(l, dz[l].t->ptr, a_in(l), B);
     if (gemm_small_takes(p)) {
       launch_gemm_small(p, S());
       continue;
@@ -169,6 +184,41 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
     launch_gemm_mfma(q, S());
     launch_sum_axis(dt, dz[l].t->ptr, gb[l]->ptr, 1, B, w[l]->dims[0], 0, w[l]->dims[0], 1, S());
   }
+}
+
+static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                               int loss, to_tensor x, to_tensor y, const to_tensor* gw, const to_tensor* gb,
+                               to_tensor losses, bool sgd, double rate) {
+  require_init();
+  NONNULL(w); NONNULL(b); NONNULL(x); NONNULL(y); NONNULL(gw); NONNULL(gb);
+  TO_CHECK(n_layers >= 1, TO_ERR_ARG, "need at least one layer");
+  for (int l = 0; l < n_layers; ++l) { NONNULL(w[l]); NONNULL(b[l]); NONNULL(gw[l]); NONNULL(gb[l]); }
+  const int hk = stack_hidden_act_check(hidden_act);
+  const int head_kind = stack_loss_head(out_act, loss, "fused path: ");
+  TO_CHECK(x->rank == 1 && y->rank == 1 && x->batch > 0 && x->batch == y->batch, TO_ERR_SHAPE,
+           "x and y must be batched vectors with the same batch, got " + shape_str(x) + " " + shape_str(y));
+  TO_CHECK(x->contiguous() && y->contiguous(), TO_ERR_ARG, "x and y must be contiguous");
+  const int dt = x->dtype;
+  TO_CHECK(y->dtype == dt, TO_ERR_ARG, "x and y have different dtypes");
+  const int64_t B = x->batch;
+  const int64_t fan_in = stack_params_check(n_layers, w, b, gw, gb, dt, x->dims[0]);
+  TO_CHECK(y->dims[0] == fan_in, TO_ERR_SHAPE, "y does not match the output layer");
+  if (losses) TO_CHECK(losses->rank == 0 && losses->batch == B && losses->contiguous(), TO_ERR_SHAPE,
+                       "losses must be a batched scalar");
+  const StackStep step{n_layers, w, b, gw, gb, hk, head_kind, dt, sgd, rate};
+  step.check_wgrads(B);
+
+  // ---- operands produced; destinations claimed -----------------------------------------------------------------------
+  ensure(x);
+  ensure(y);
+  if (losses) { ensure(losses); before_write(losses); }
+  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); ensure(gw[l]); ensure(gb[l]); }
+  for (int l = 0; l < n_layers; ++l) {  // (identities: sgd's parameters get a new one, grad's destinations keep theirs)
+    before_write(gw[l]);
+    before_write(gb[l]);
+    if (sgd) { w[l]->id = fresh_id(); b[l]->id = fresh_id(); }
+  }
+  step.launch(x->ptr, y->ptr, losses ? losses->ptr : nullptr, B);
 }
 
 to_status to_fflayer_stack_grad(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act,
@@ -183,6 +233,127 @@ to_status to_fflayer_stack_sgd(int n_layers, const to_tensor* w, const to_tensor
                                int loss, to_tensor x, to_tensor y, double rate, to_tensor losses) {
   API_BEGIN
   fflayer_stack_impl(n_layers, w, b, hidden_act, out_act, loss, x, y, w, b, losses, true, rate);
+  API_END
+}
+
+// ---- minibatch SGD over a resident data set: the steps of to_fflayer_stack_sgd, one per minibatch, in one call ------------
+// idx given: the rows of a chunk of consecutive steps are gathered into a pool buffer by ONE launch (minibatch_stage.hip)
+// and the steps run on its slabs; idx null: the steps run on views of X / Y themselves.  Every step's slab starts on a
+// 16-byte boundary, like the fresh tensor a host loop's to_batch_gather hands its step: the alignment the kernels' routes
+// look at.
+static int64_t g_minibatch_stage_bytes = MINIBATCH_STAGE_DEFAULT;
+
+static void minibatch_sgd_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss,
+                               to_tensor X, to_tensor Y, int64_t n_idx, const int64_t* idx, int64_t M, double rate,
+                               to_tensor losses) {
+  const std::string F = "to_fflayer_stack_minibatch_sgd: ";
+  require_init();
+  no_capture("to_fflayer_stack_minibatch_sgd");
+  NONNULL(w); NONNULL(b); NONNULL(X);
+  TO_CHECK(n_layers >= 1, TO_ERR_ARG, F + "need at least one layer");
+  TO_CHECK(n_idx >= 1 && M >= 1, TO_ERR_ARG, F + "needs at least one sample and a minibatch of at least one row");
+  for (int l = 0; l < n_layers; ++l) { NONNULL(w[l]); NONNULL(b[l]); }
+  const int hk = stack_hidden_act_check(hidden_act);
+  const int head_kind = stack_loss_head(out_act, loss, F);
+  TO_CHECK(X->rank == 1 && X->batch > 0, TO_ERR_SHAPE, F + "X must be batched vectors, got " + shape_str(X));
+  TO_CHECK(X->contiguous(), TO_ERR_ARG, F + "X must be contiguous");
+  const int dt = X->dtype;
+  const int64_t N = X->batch, i0 = X->dims[0];
+  const int64_t nL = stack_params_check(n_layers, w, b, nullptr, nullptr, dt, i0);
+  if (Y) {
+    TO_CHECK(Y->dtype == dt, TO_ERR_ARG, F + "X and Y have different dtypes");
+    TO_CHECK(Y->rank == 1 && Y->dims[0] == nL && Y->batch == N, TO_ERR_SHAPE,
+             F + "Y must be " + std::to_string(nL) + "-vectors of X's batch, got " + shape_str(Y));
+    TO_CHECK(Y->contiguous(), TO_ERR_ARG, F + "Y must be contiguous");
+  } else {
+    TO_CHECK(nL == i0, TO_ERR_SHAPE, F + "without Y the target of a row is the row itself: the output layer must have X's width");
+  }
+  if (losses) {
+    TO_CHECK(losses->dtype == dt, TO_ERR_ARG, F + "X and losses have different dtypes");
+    TO_CHECK(losses->rank == 0 && losses->batch == n_idx && losses->contiguous(), TO_ERR_SHAPE,
+             F + "losses must be a contiguous batched scalar of batch n_idx");
+  }
+  if (idx) {
+    for (int64_t k = 0; k < n_idx; ++k)
+      TO_CHECK(idx[k] >= 0 && idx[k] < N, TO_ERR_SHAPE, F + "sample index out of range");
+  } else {
+    TO_CHECK(n_idx <= N, TO_ERR_SHAPE, F + "more samples than rows");
+  }
+  if (M > n_idx) M = n_idx;
+  const int64_t n_steps = (n_idx + M - 1) / M, tail_rows = n_idx - (n_steps - 1) * M;
+  // nothing half-trained: every refusal of a step, for both batches that occur, before the first launch
+  const StackStep step{n_layers, w, b, w, b, hk, head_kind, dt, true, rate};
+  step.check_sgd(M);
+  if (tail_rows != M) step.check_sgd(tail_rows);
+
+  // ---- operands produced; destinations claimed -----------------------------------------------------------------------
+  ensure(X);
+  if (Y) ensure(Y);
+  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); }
+  if (losses) claim(losses);
+  for (int l = 0; l < n_layers; ++l) {  // in-place writes: recorded readers of the old values first, new identities after
+    claim(w[l]);
+    claim(b[l]);
+  }
+  const int64_t es = dt == TO_F64 ? 8 : 4;
+  auto loss_at = [&](int64_t k) -> void* { return losses ? at(losses->ptr, k * M, es) : nullptr; };
+  auto rows_of = [&](int64_t k) { return k + 1 == n_steps ? tail_rows : M; };
+  if (!idx) {
+    for (int64_t k = 0; k < n_steps; ++k) {
+      const void* x = at(X->ptr, k * M * i0, es);
+      step.launch(x, Y ? at(Y->ptr, k * M * nL, es) : x, loss_at(k), rows_of(k));
+    }
+    return;
+  }
+  // the device's copy of idx: through the pinned ring up to a slot of it (nothing in this call uploads another table, so the
+  // slot holds for all of its launches), beyond that the staged transfer into a pool buffer
+  Holder order;
+  const long long* didx;
+  if ((size_t)n_idx * sizeof(int64_t) <= 65536) {
+    didx = static_cast<const long long*>(table_upload(idx, (size_t)n_idx * sizeof(int64_t), S()));
+  } else {
+    const int64_t nl = (n_idx * 8 + 3) / 4;
+    order.t = new_tensor(1, &nl, 0);
+    host_to_device(order.t->ptr, idx, (size_t)n_idx * sizeof(int64_t), S());
+    didx = static_cast<const long long*>(order.t->ptr);
+  }
+  // a chunk: consecutive steps whose slabs fit the bound, one step at least
+  auto slab = [](int64_t bytes) { return (bytes + 15) / 16 * 16; };
+  const int64_t x_slab = slab(M * i0 * es), y_slab = Y ? slab(M * nL * es) : 0;
+  int64_t chunk = g_minibatch_stage_bytes / (x_slab + y_slab);
+  chunk = std::max<int64_t>(1, std::min(chunk, n_steps));
+  const int64_t stage_floats = chunk * (x_slab + y_slab) / 4;
+  TO_CHECK(stage_floats <= 2147483647LL, TO_ERR_SHAPE, F + "a minibatch does not fit one stage buffer");
+  Holder stage(new_tensor(1, &stage_floats, 0));
+  char* const xs = static_cast<char*>(stage.t->ptr);
+  char* const ys = xs + chunk * x_slab;
+  for (int64_t k0 = 0; k0 < n_steps; k0 += chunk) {
+    const int64_t steps = std::min(chunk, n_steps - k0), rows = std::min(steps * M, n_idx - k0 * M);
+    launch_minibatch_stage(didx + k0 * M, rows, M, X->ptr, xs, i0 * es, x_slab, Y ? Y->ptr : nullptr, Y ? ys : nullptr,
+                           nL * es, y_slab, (int)es, S());
+    for (int64_t j = 0; j < steps; ++j) {
+      const void* x = xs + j * x_slab;
+      step.launch(x, Y ? ys + j * y_slab : x, loss_at(k0 + j), rows_of(k0 + j));
+    }
+  }
+  // (one stream: the stage buffer and the index table go back to the pool behind the launches that read them)
+}
+
+to_status to_fflayer_stack_minibatch_sgd(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                         int loss, to_tensor X, to_tensor Y_or_null, int64_t n_idx,
+                                         const int64_t* idx_or_null, int64_t minibatch, double rate,
+                                         to_tensor losses_or_null) {
+  API_BEGIN
+  minibatch_sgd_impl(n_layers, w, b, hidden_act, out_act, loss, X, Y_or_null, n_idx, idx_or_null, minibatch, rate,
+                     losses_or_null);
+  API_END
+}
+
+to_status to_set_minibatch_stage_bytes(int64_t bytes, int64_t* previous_or_null) {
+  API_BEGIN
+  TO_CHECK(bytes >= 0, TO_ERR_ARG, "to_set_minibatch_stage_bytes: a byte count, or 0 for the default");
+  if (previous_or_null) *previous_or_null = g_minibatch_stage_bytes;
+  g_minibatch_stage_bytes = bytes ? bytes : MINIBATCH_STAGE_DEFAULT;
   API_END
 }
 

@@ -444,6 +444,33 @@ class HipT:
                                          losses.h if losses is not None else None))
         return losses
 
+    def stack_minibatch_sgd(self, ws, bs, X, Y, rate, minibatch, idx=None, n=None, out_act="softmax", loss="crossEntropy",
+                            hidden_act="logistic", want_losses=False):
+        """minibatch SGD over rows idx (None: rows 0..n-1, n None: every row) of the resident X / Y, one `trainNetwork` step a
+        minibatch, parameters updated in place, in one call (to_fflayer_stack_minibatch_sgd).  Y None: the target of a row
+        is the row itself (`trainEncoder`).  The losses [n_idx] of the rows in idx's order if asked for."""
+        arr = None
+        if idx is not None:
+            arr = np.ascontiguousarray(idx, dtype=np.int64)
+            n = len(arr) if n is None else n
+        elif n is None:
+            n = X.batch
+        losses = self._alloc((), int(n)) if want_losses and n >= 1 else None
+        check(lib().to_fflayer_stack_minibatch_sgd(len(ws), _arr(ws), _arr(bs), self._HIDDEN[hidden_act],
+                                                   self._RNN_OUT[out_act], self._RNN_LOSS[loss], X.h,
+                                                   Y.h if Y is not None else None, int(n),
+                                                   arr.ctypes.data_as(C.POINTER(C.c_int64)) if arr is not None else None,
+                                                   int(minibatch), float(rate), losses.h if losses is not None else None))
+        return losses
+
+    @staticmethod
+    def minibatch_stage_bytes(nbytes):
+        """to_set_minibatch_stage_bytes: the bound on the staging buffer of stack_minibatch_sgd (0: the default); returns the
+        previous bound"""
+        prev = C.c_int64()
+        check(lib().to_set_minibatch_stage_bytes(int(nbytes), C.byref(prev)))
+        return prev.value
+
     def stack_online_sgd(self, ws, bs, X, Y, n, rate, idx=None, out_act="softmax", loss="crossEntropy",
                          hidden_act="logistic"):
         """per-sample SGD over rows idx[0..n) (None: rows 0..n-1) of X / Y in one launch, parameters updated in place

@@ -13,7 +13,8 @@
 // the library's counter-based device generator (mwc-random streams are not reproducible anyway);
 // validation runs as batched inference + device argMax instead of one runNetwork per image;
 // `--epochs` bounds the reference's endless epoch loop; `--minibatch M` (not in the reference)
-// switches the update to the batched gradTOp of M samples; `--f64` selects ElemT = Double.
+// switches the update to the batched gradTOp of M samples, and `--onecall` with it trains each "Batch" with ONE
+// to_fflayer_stack_minibatch_sgd over the epoch's permutation (no gathered copy of the queue); `--f64` selects ElemT = Double.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -191,7 +192,7 @@ int main(int argc, char** argv) {
   std::vector<int64_t> layers{300, 100};  // :94-98
   int64_t batch = 1000;                // :99-103
   std::string data_dir = "data/mnist";  // :104-108
-  bool noconfusion = false, white = false, check_only = false, f64 = false;
+  bool noconfusion = false, white = false, check_only = false, f64 = false, onecall = false;
   int induce = -1, epochs = 1, induce_iters = 5000;
   int64_t minibatch = 0, syn_train = 0, syn_test = 0, max_batches = 0;
   uint64_t seed = 0x7e500001ull;
@@ -226,6 +227,7 @@ int main(int argc, char** argv) {
     else if (a == "--max-batches") max_batches = std::atoll(next());
     else if (a == "--induce-iters") induce_iters = std::atoi(next());
     else if (a == "--minibatch") minibatch = std::atoll(next());
+    else if (a == "--onecall") onecall = true;
     else if (a == "--seed") seed = std::strtoull(next(), nullptr, 0);
     else if (a == "--f64") f64 = true;
     else if (a == "--check-data") check_only = true;
@@ -237,12 +239,13 @@ int main(int argc, char** argv) {
       std::fprintf(stderr,
                    "tensor-ops-mnist - train neural nets on MNIST data set (HIP backend)\n"
                    "usage: %s [-r STEP] [-l LIST] [-b AMOUNT] [-d PATH] [-c] [-w] [-i DIGIT]\n"
-                   "          [--epochs N] [--max-batches N] [--minibatch M] [--f64] [--seed N]\n"
+                   "          [--epochs N] [--max-batches N] [--minibatch M [--onecall]] [--f64] [--seed N]\n"
                    "          [--synthetic NTRAIN,NTEST] [--check-data] [--induce-iters N]\n", argv[0]);
       return 2;
     }
   }
   if (batch < 1) { std::fprintf(stderr, "--batch must be positive\n"); return 2; }
+  if (onecall && minibatch < 1) { std::fprintf(stderr, "--onecall needs --minibatch M\n"); return 2; }
   try {
     Idx raw_tr, raw_te;
     if (syn_train > 0) {
@@ -297,7 +300,8 @@ int main(int argc, char** argv) {
     std::printf("]\n");
     if (white) std::printf("white noise class enabled\n");
     if (induce >= 0) std::printf("inducing: %d\n", induce);
-    if (minibatch > 0) std::printf("update: batched gradTOp over %lld samples\n", (long long)minibatch);
+    if (onecall) std::printf("update: one-call minibatch SGD over %lld samples\n", (long long)minibatch);
+    else if (minibatch > 0) std::printf("update: batched gradTOp over %lld samples\n", (long long)minibatch);
 
     const int flags = TRAINER_MEMO | TRAINER_FUSED;
     uint64_t rs = seed + 77;
@@ -309,19 +313,35 @@ int main(int argc, char** argv) {
       std::vector<int64_t> perm((size_t)tr2.n());
       for (size_t i = 0; i < perm.size(); ++i) perm[i] = (int64_t)i;
       for (size_t i = perm.size(); i > 1; --i) std::swap(perm[i - 1], perm[(size_t)(splitmix64(rs) % i)]);
-      T qx = gather(tr2.x, perm);
+      // (--onecall trains through the permutation on the data set where it lies: the queue is never gathered)
+      T qx = onecall ? T() : gather(tr2.x, perm);
       std::vector<int64_t> ql(perm.size());
       for (size_t i = 0; i < perm.size(); ++i) ql[i] = tr2.labels[(size_t)perm[i]];
-      T qy = HipT::oneHot(n_out, 1.0, 0.0, ql, true);  // TT.oneHot 1 0   (:216)
+      T qy = HipT::oneHot(n_out, 1.0, 0.0, onecall ? tr2.labels : ql, true);  // TT.oneHot 1 0   (:216)
       std::printf("Training on %lld samples in batches of %lld ...\n", (long long)tr2.n(), (long long)batch);
 
       int64_t b = 1;
       for (int64_t start = 0; start < tr2.n(); start += batch, ++b) {
         const int64_t cnt = std::min(batch, tr2.n() - start);
         std::printf("Batch %lld ...\n", (long long)b);
-        T bx = rows(qx, start, cnt), by = rows(qy, start, cnt);
+        T bx, by;
+        if (onecall) {  // (the batch's rows for the training score below; the steps read tr2.x through perm)
+          bx = gather(tr2.x, std::vector<int64_t>(perm.begin() + start, perm.begin() + start + cnt));
+        } else {
+          bx = rows(qx, start, cnt);
+          by = rows(qy, start, cnt);
+        }
         const auto t0 = std::chrono::steady_clock::now();
-        if (minibatch <= 0) {
+        if (onecall) {
+          std::vector<to_tensor> pw, pb;  // genNet's parameters: W_1, b_1, W_2, b_2, ...
+          for (size_t i = 0; i + 1 < net.params.size(); i += 2) {
+            pw.push_back(net.params[i].h());
+            pb.push_back(net.params[i + 1].h());
+          }
+          check(to_fflayer_stack_minibatch_sgd((int)pw.size(), pw.data(), pb.data(), TO_ACT_LOGISTIC, TO_ACT_SOFTMAX,
+                                               TO_LOSS_CROSS_ENTROPY, tr2.x.h(), qy.h(), cnt, perm.data() + start, minibatch,
+                                               rate, nullptr));
+        } else if (minibatch <= 0) {
           net = trainAll(net, LOSS_CROSS_ENTROPY, rate, bx, by, cnt, nullptr, flags);  // trainAll (:390-393)
         } else {
           for (int64_t s = 0; s < cnt; s += minibatch) {

@@ -371,6 +371,57 @@ to_status to_fflayer_stack_minibatch_sgd(int n_layers, const to_tensor* w, const
                                          to_tensor losses_or_null);
 to_status to_set_minibatch_stage_bytes(int64_t bytes, int64_t* previous_or_null);
 
+/* ---- encoder / decoder pairs of ffLayer stacks: AutoEncoder.hs in one call ----------------------------------------------- */
+/* `Encoder t i o` (AutoEncoder.hs:37-40) as two `genNet` stacks given as ONE per-layer array: w[l] / b[l], l = 0 .. L-1, L =
+ * n_enc + n_dec, in input-to-output order as in to_fflayer_stack_*; layers 0 .. n_enc-1 are the encoder ([i0] -> the code
+ * [c]), n_enc .. L-1 the decoder ([c] -> [i0]: w[L-1] must have i0 rows, TO_ERR_SHAPE otherwise).  n_enc < 1 or n_dec < 1:
+ * TO_ERR_ARG.  Layer l applies
+ *   hidden_act   TO_ACT_LOGISTIC or TO_ACT_TANH, every layer but the two below;
+ *   code_act     layer n_enc-1, the encoder's output: TO_ACT_LOGISTIC, TO_ACT_TANH or TO_ACT_IDENTITY (a bare `ffLayer`: no
+ *                activation in the forward pass, no act' factor in the backward pass);
+ *   out_act      layer L-1, with the loss one of (TO_ACT_SOFTMAX, TO_LOSS_CROSS_ENTROPY), (TO_ACT_LOGISTIC,
+ *                TO_LOSS_SQUARED_ERROR), (TO_ACT_TANH, TO_LOSS_SQUARED_ERROR), (TO_ACT_IDENTITY, TO_LOSS_SQUARED_ERROR).
+ * Anything else: TO_ERR_UNSUPPORTED with nothing written.  The target of a row is the row itself; with a = out_act(z):
+ * squaredError = sum (a - x)^2, dz = 2 (a - x) act'(a), act' = a (1 - a) / 1 - a^2 / 1; softmax with crossEntropy as in
+ * to_fflayer_stack_grad (dz = p sum(x) - x).  The to_fflayer_stack_* and to_rnn_stack_* entries refuse TO_ACT_IDENTITY and
+ * keep refusing TO_ACT_TANH as an output activation.
+ *
+ * run: `encode` (:42-48), `encodeDecode` (:58-63) and `testEncoder` (:65-81) over the hidden batch of x ([B; i0], or
+ * unbatched: one row).  Each output optional, at least one asked for (else TO_ERR_ARG), caller-allocated, contiguous, of x's
+ * dtype and batch: code [B; c], recon [B; i0], losses [B].  With only code asked for the decoder is not run; an output's
+ * bits do not depend on which others are asked for.  fp32 or fp64, any B, any widths: never TO_ERR_UNSUPPORTED for a valid
+ * stack and pair.  Hidden layers go as to_fflayer_stack_infer's; the head -- bias, activation, loss of a row -- is one row
+ * launch behind the last GEMM (csrc/recon_head.hip).  Parameters and x are only read: an output that overlaps x, another
+ * output or a parameter is TO_ERR_ARG (decode: out against code and the decoder's parameters).  Refused during graph capture
+ * (TO_ERR_STATE).
+ * decode: `decode` (:50-56): layers n_enc .. L-1 on code [B; c] into out [B; i0]; the encoder's entries of w / b are not
+ * looked at.
+ * grad: `encGrad` (:112-142) summed over the batch of x ([B; i0], contiguous) into gw[l] / gb[l]; losses[r] = testEncoder of
+ * row r.  sgd: `trainEncoder` (:87-110) on one batch, parameters updated in place.  minibatch_sgd:
+ * to_fflayer_stack_minibatch_sgd with Y = NULL for these stacks: the same idx, tail-minibatch, losses and staging rules
+ * (to_set_minibatch_stage_bytes included).  The three carry exactly the refusals of to_fflayer_stack_grad / _sgd /
+ * _minibatch_sgd for the same shapes -- an fp64 contraction outside the small-GEMM range, an sgd weight gradient outside it
+ * -- every one decided before the first launch: a refused call leaves parameters, gradients and losses untouched.  When
+ * code_act == hidden_act and the pair is one of to_fflayer_stack_grad's two they issue the launches of to_fflayer_stack_grad
+ * / _sgd / _minibatch_sgd on (w, b, x, y = x) and produce the same bits; a stack whose code activation is the other of
+ * logistic / tanh takes the same number of launches; the pairs with tanh / identity run the row launch of
+ * csrc/recon_head.hip behind the last GEMM where the old pairs have their loss head. */
+enum { TO_ACT_IDENTITY = 4 };
+to_status to_autoencoder_stack_run(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int code_act,
+                                   int out_act, int loss, to_tensor x, to_tensor code_or_null, to_tensor recon_or_null,
+                                   to_tensor losses_or_null);
+to_status to_autoencoder_stack_decode(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                      to_tensor code, to_tensor out);
+to_status to_autoencoder_stack_grad(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int code_act,
+                                    int out_act, int loss, to_tensor x, const to_tensor* gw, const to_tensor* gb,
+                                    to_tensor losses_or_null);
+to_status to_autoencoder_stack_sgd(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int code_act,
+                                   int out_act, int loss, to_tensor x, double rate, to_tensor losses_or_null);
+to_status to_autoencoder_stack_minibatch_sgd(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act,
+                                             int code_act, int out_act, int loss, to_tensor X, int64_t n_idx,
+                                             const int64_t* idx_or_null, int64_t minibatch, double rate,
+                                             to_tensor losses_or_null);
+
 /* Per-sample online SGD -- `foldl' (\nt (i,o) -> trainNetwork loss rate i o nt)` (app/MNIST.hs:390-396,
  * app/Dots.hs:74-80) -- of the same stacks over rows idx[0..n_idx) (null: rows 0..n_idx-1) of the resident batched X / Y,
  * parameters updated in place, as ONE persistent launch: the workgroups keep the parameters in LDS between samples,

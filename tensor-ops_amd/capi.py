@@ -117,6 +117,16 @@ SIGNATURES = {
     "to_fflayer_stack_minibatch_sgd": [C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int,
                                        c_tensor, c_tensor, C.c_int64, i64p, C.c_int64, C.c_double, c_tensor],
     "to_set_minibatch_stage_bytes": [C.c_int64, i64p],
+    "to_autoencoder_stack_run": [C.c_int, C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int,
+                                 C.c_int, c_tensor, c_tensor, c_tensor, c_tensor],
+    "to_autoencoder_stack_decode": [C.c_int, C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, c_tensor,
+                                    c_tensor],
+    "to_autoencoder_stack_grad": [C.c_int, C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int,
+                                  C.c_int, c_tensor, C.POINTER(c_tensor), C.POINTER(c_tensor), c_tensor],
+    "to_autoencoder_stack_sgd": [C.c_int, C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int,
+                                 C.c_int, c_tensor, C.c_double, c_tensor],
+    "to_autoencoder_stack_minibatch_sgd": [C.c_int, C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int,
+                                           C.c_int, C.c_int, c_tensor, C.c_int64, i64p, C.c_int64, C.c_double, c_tensor],
     "to_fflayer_stack_online_sgd": [C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int,
                                     c_tensor, c_tensor, C.c_int64, i64p, C.c_double],
     "to_fflayer_stack_infer": [C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, c_tensor, c_tensor,

@@ -288,7 +288,7 @@ bool gemm_small_fuses_tail(const GemmProblem& p, int64_t tail_n);
 void launch_gemm_f64(const GemmProblem& p, hipStream_t s);
 bool gemm_t32_applicable(const GemmProblem& p);  // gemm_t32.hip: ~one round of 32x32 tiles, four waves each, DMA-fed (the training step's two big contractions)
 void launch_gemm_t32(const GemmProblem& p, hipStream_t s);
-bool launch_gemm_t32_pair(const GemmProblem& p1, const GemmProblem& p2, hipStream_t s);   // two weight-gradient contractions, one launch
+bool launch_gemm_t32_pair(const GemmProblem& p1, const GemmProblem& p2, hipStream_t s, bool dry = false);   // two weight-gradient contractions, one launch (dry: see launch_gemm_small_pair)
 bool launch_gemm_t32_head(const GemmProblem& fwd, const GemmProblem& head, hipStream_t s); // forward layer + the loss-head launch reading its output, one launch
 void gemm_t32_init();   // its row-block counters (to_init)
 int gemm_t32_take_failure();   // nonzero once after a joined launch gave up waiting (its outputs are invalid; the form is off from then on)
@@ -309,7 +309,8 @@ void launch_gemm_mfma(const GemmProblem& p, hipStream_t s);
 void launch_gemm_small(const GemmProblem& p, hipStream_t s);
 bool gemm_small_applicable(const GemmProblem& p);
 bool gemm_small_can(const GemmProblem& p);
-bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStream_t s);
+// (dry: the answer alone, decided by the shapes -- nothing is launched; what StackStep asks before a step's first launch)
+bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStream_t s, bool dry = false);
 // forward layer + the loss-head launch reading its output, joined by an intra-XCD seam (gemm_small.hip)
 bool launch_gemm_small_seam(const GemmProblem& fwd, const GemmProblem& head, hipStream_t s);
 void gemm_small_seam_init();
@@ -340,6 +341,9 @@ bool gemm_f64_w4_full_rounds(const GemmProblem& p);
 // epilogues compute (tanhf / tanh, 1 - h h): every route of an entry computes the same function.  A further activation
 // whose derivative can be written on its output goes here.
 constexpr int ACT_KIND_LOGISTIC = 0, ACT_KIND_TANH = 1;
+// No activation (an autoencoder's linear code layer): GemmProblem::act = this + 1 = 0, and no dact / tail behind it.  The host
+// side's per-layer number only; no kernel takes it as dact_kind / tail_kind.
+constexpr int ACT_KIND_IDENTITY = -1;
 __device__ __forceinline__ float tanh_act(float z) { return tanhf(z); }
 __device__ __forceinline__ double tanh_act(double z) { return tanh(z); }
 __device__ __forceinline__ float tanh_dact(float h) { return 1.0f - h * h; }
@@ -462,8 +466,15 @@ void launch_infer_narrow(int dtype, const void* A, int64_t a_sm, int64_t B, int6
                          unsigned long long* conf, hipStream_t s);
 void launch_infer_rows(int dtype, const void* z, int64_t B, const void* bias, int n, bool softmax, void* out,
                        const void* y, int64_t y_sm, int* classes, unsigned long long* conf, hipStream_t s);
-// x[r][j] = act(x[r][j] + bias[j]) in place, act_kind ACT_KIND_* (a hidden layer whose GEMM carried no epilogue)
+// x[r][j] = act(x[r][j] + bias[j]) in place, act_kind ACT_KIND_* (ACT_KIND_IDENTITY: the bias alone; a hidden layer whose
+// GEMM carried no epilogue)
 void launch_bias_act_rows(int dtype, void* x, const void* bias, int64_t B, int64_t n, int act_kind, hipStream_t s);
+// recon_head.hip: the reconstruction head of to_autoencoder_stack_*, one wave per row.  pair: 1 (softmax, crossEntropy), 2
+// (logistic, squaredError) -- stack_loss_head's numbers --, 3 (tanh, squaredError), 4 (identity, squaredError).  z [B, n]
+// contiguous (+ bias [n], optional); target rows t_sm elements apart (null: decode, only `out` means anything); optional
+// outputs dz [B, n] (may be z), out = act(z + bias) [B, n] (may be z; not dz), loss [B].
+void launch_recon_head(int dtype, int pair, const void* z, const void* bias, const void* target, int64_t t_sm, void* dz,
+                       void* out, void* loss, int64_t B, int64_t n, hipStream_t s);
 // rnn_seq.hip: the recurrence of a stateful layer over all T steps in one launch (to_rnn_stack_*).  M [H][H]: W'^T
 // (forward: Z = P -> z in place, St blocks 1..T = act(z), act_kind ACT_KIND_*) or W' (reverse: Z = G -> dz in place, reading
 // St blocks 1..T).  Z [T][B][H], St [T+1][B][H] (block 0: the initial states).  H <= RNN_SEQ_MAX_H, any B and T.

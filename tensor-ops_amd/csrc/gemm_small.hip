@@ -1376,10 +1376,10 @@ constexpr bool SMALL_PAIR_STAG = false;
 // Two weight-gradient GEMMs (dZ^T . A: A m-contiguous view of dZ, B n-contiguous) in one launch when the
 // heuristics pick the (16-wave one-shot 32x32, 8-wave 16x16) pair of configurations -- the shapes of a
 // wide hidden layer next to a narrow output layer.  Returns false when the pair is not of that form.
-bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStream_t s) {
+bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStream_t s, bool dry) {
   static const int enable = [] { const char* e = ab_getenv("TOPS_SMALL_PAIR"); return e ? atoi(e) : 1; }();
   if (!enable || p1.dtype != p2.dtype || p1.batch != 1 || p2.batch != 1) return false;
-  if (launch_gemm_t32_pair(p1, p2, s)) return true;   // four DMA-fed waves per 32x32 tile (gemm_t32.hip)
+  if (launch_gemm_t32_pair(p1, p2, s, dry)) return true;   // four DMA-fed waves per 32x32 tile (gemm_t32.hip)
   if (!gemm_small_can(p1) || !gemm_small_can(p2)) return false;
   if (p1.dtype == TO_F64) {
     SmallArgsT<double> g1, g2;
@@ -1387,6 +1387,7 @@ bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStr
     if (!(c1.f64_t32 && c1.nw == 8 && c1.os == 1 && c1.amode == 1 && c1.bmode == 0)) return false;
     if (!(!c2.f64_t32 && c2.ts == 16 && c2.nw == 8 && c2.os == 8 && c2.amode == 1 && c2.bmode == 0)) return false;
     if (g1.loss_rows || g2.loss_rows) return false;
+    if (dry) return true;
     const int n1 = (int)((p1.M + 31) / 32) * g1.tiles_n, n2 = (int)((p2.M + 15) / 16) * g2.tiles_n;
     launch_k((gemm_small_pair_f64_kernel<1, 0, 1, 0>), dim3(n1 + n2), dim3(512), 0, s, g1, g2, n1);
     TO_HIP(hipGetLastError());
@@ -1406,6 +1407,7 @@ bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStr
       c2.ts == 16 && c2.nw == 1 && c2.os == 0 && c2.amode == 1 && c2.bmode == 0 && !c2.f64_t32 && !g1.loss_rows && !g2.loss_rows) {
     const long t1 = (long)g1.tiles_m * g1.tiles_n, t2 = (long)g2.tiles_m * g2.tiles_n;
     if (t1 + t2 > 65535) return false;
+    if (dry) return true;
     launch_k((gemm_small_pair_kernel<float, 1, 0, 1, 16, 0, 1, 0, 1, 16, 0>), dim3((unsigned)(t1 + t2)), dim3(64), 0, s, g1, g2, (int)t1);
     TO_HIP(hipGetLastError());
     count_launch();
@@ -1414,6 +1416,7 @@ bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStr
   if (!(c1.ts == 32 && c1.nw == 16 && c1.os == 8 && c1.amode == 1 && c1.bmode == 0)) return false;
   if (!(c2.ts == 16 && c2.nw == 8 && c2.os == 8 && c2.amode == 1 && c2.bmode == 0)) return false;
   if (g1.loss_rows || g2.loss_rows) return false;
+  if (dry) return true;
   const int n1 = (int)((p1.M + 31) / 32) * g1.tiles_n, n2 = (int)((p2.M + 15) / 16) * g2.tiles_n;
   dim3 grid(n1 + n2), block(1024);
   // (both one-shot: the two-stage pipeline of the 16x16 body does not fit the 128 registers of a 1024-thread

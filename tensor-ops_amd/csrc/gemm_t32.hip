@@ -738,7 +738,7 @@ bool gemm_t32_applicable(const GemmProblem& p) {
 }
 
 // Both problems of a weight-gradient pair on this design: together about one round of tiles, the same K.
-bool launch_gemm_t32_pair(const GemmProblem& p1, const GemmProblem& p2, hipStream_t s);
+bool launch_gemm_t32_pair(const GemmProblem& p1, const GemmProblem& p2, hipStream_t s, bool dry);
 
 // workgroups of a launch: eight times the largest rectangle of the XCD grid
 static long t32_grid(const T32Args& g) {
@@ -888,7 +888,7 @@ bool launch_gemm_t32_head(const GemmProblem& pf, const GemmProblem& ph, hipStrea
   return true;
 }
 
-bool launch_gemm_t32_pair(const GemmProblem& p1, const GemmProblem& p2, hipStream_t s) {
+bool launch_gemm_t32_pair(const GemmProblem& p1, const GemmProblem& p2, hipStream_t s, bool dry) {
   // OFF in product builds (measured, config 3, rocprofv3 over 411 launches: 13.4-14.3 us against 10.2 us for gemm_small's
   // pair launch; profiles/README.md round 5).  Both operands of dZ^T . X are row-contiguous, which is the one case where
   // gemm_small's one-shot register loads already fetch whole 128-byte lines, and it has ALL 256 KB of a tile in flight at
@@ -904,6 +904,7 @@ bool launch_gemm_t32_pair(const GemmProblem& p1, const GemmProblem& p2, hipStrea
   if (!t32_fill(p2, g2, akc2, bkc2, true, &rag2) || akc2 || bkc2) return false;
   const long n1 = (long)g1.tiles_m * g1.tiles_n, n2 = (long)g2.tiles_m * g2.tiles_n;
   if (n1 < 96 || n1 + n2 > 512 || p1.K < 256 || p1.K > 8192 || p2.K < 256 || p2.K > 8192 || n2 > n1) return false;
+  if (dry) return true;
   static bool attr = false;
   if (!attr) {
     t32_attr(reinterpret_cast<const void*>(gemm_t32_pair_kernel<false>));

@@ -241,6 +241,7 @@ template <class S, int ACT>
 __global__ __launch_bounds__(256) void bias_act_kernel(S* __restrict__ x, const S* __restrict__ bias, long total, long n) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     if constexpr (ACT == ACT_KIND_TANH) x[i] = tanh_act(x[i] + bias[i % n]);
+    else if constexpr (ACT == ACT_KIND_IDENTITY) x[i] = x[i] + bias[i % n];
     else x[i] = S(1) / (S(1) + exp_i(-(x[i] + bias[i % n])));
   }
 }
@@ -296,10 +297,14 @@ void launch_infer_rows(int dtype, const void* z, int64_t B, const void* bias, in
 void launch_bias_act_rows(int dtype, void* x, const void* bias, int64_t B, int64_t n, int act_kind, hipStream_t s) {
   const int64_t total = B * n;
   if (total == 0) return;
-  TO_CHECK(act_kind == ACT_KIND_LOGISTIC || act_kind == ACT_KIND_TANH, TO_ERR_ARG, "bias_act_rows: unknown activation");
+  TO_CHECK(act_kind == ACT_KIND_LOGISTIC || act_kind == ACT_KIND_TANH || act_kind == ACT_KIND_IDENTITY, TO_ERR_ARG,
+           "bias_act_rows: unknown activation");
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 16);
   if (act_kind == ACT_KIND_TANH)
     TO_DISPATCH(dtype, launch_k(bias_act_kernel<S, ACT_KIND_TANH>, dim3(grid), dim3(256), 0, s, (S*)x, (const S*)bias,
+                                (long)total, (long)n));
+  else if (act_kind == ACT_KIND_IDENTITY)
+    TO_DISPATCH(dtype, launch_k(bias_act_kernel<S, ACT_KIND_IDENTITY>, dim3(grid), dim3(256), 0, s, (S*)x, (const S*)bias,
                                 (long)total, (long)n));
   else
     TO_DISPATCH(dtype, launch_k(bias_act_kernel<S, ACT_KIND_LOGISTIC>, dim3(grid), dim3(256), 0, s, (S*)x, (const S*)bias,

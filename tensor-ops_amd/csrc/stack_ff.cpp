@@ -1,4 +1,7 @@
-// The one-call entry points for ffLayer stacks: to_fflayer_stack_grad / _sgd / _online_sgd / _infer / _induce.
+// The one-call entry points for ffLayer stacks: to_fflayer_stack_grad / _sgd / _minibatch_sgd / _online_sgd / _infer / _induce,
+// and for encoder / decoder pairs of them: to_autoencoder_stack_run / _decode / _grad / _sgd / _minibatch_sgd.
+#include <deque>
+
 #include "api_util.hpp"
 #include "stack_util.hpp"
 
@@ -35,10 +38,15 @@ static GemmProblem fused_gemm(GemmProblem p) {
 // sgd: gw/gb are the parameters themselves and the weight-gradient launches apply
 // P <- P - rate * gradient in their epilogue (alpha = -rate, beta = 1, Cin = C = W; the bias through the
 // accumulating row sum): the step loses its separate update launch.
+// act[l], l < n_layers - 1: the activation behind layer l (ACT_KIND_*; ACT_KIND_IDENTITY: none -- act = 0 in the forward, no
+// dact in the backward and no fused tail behind it).  head_kind: stack_loss_head's pairs 1 / 2, which the small-GEMM kernel
+// fuses (loss_rows) and launch_loss_grad_rows knows, or the pairs 3 / 4 of ae_loss_head, which never set loss_rows: their
+// head is launch_recon_head behind the last GEMM.
 struct StackStep {
   int n_layers;
   const to_tensor *w, *b, *gw, *gb;
-  int hk, head_kind, dt;
+  const int* act;
+  int head_kind, dt;
   bool sgd;
   double rate;
 
@@ -64,10 +72,10 @@ struct StackStep {
     const bool last = l + 1 == n_layers;
     GemmProblem p = row_gemm(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, C, B, n, prev_n);
     p.bias = b[l]->ptr;
-    p.act = last ? 0 : hk + 1;
-    if (last) { p.loss_rows = head_kind; p.target = y; p.loss_out = losses; }
-    if (last && n_layers >= 2 && fuse_tail) {
-      p.tail_w = w[l]->ptr; p.tail_h = h; p.tail_out = tail_out; p.tail_n = (int)prev_n; p.tail_kind = hk;
+    p.act = last ? 0 : act[l] + 1;
+    if (last && head_kind <= 2) { p.loss_rows = head_kind; p.target = y; p.loss_out = losses; }
+    if (last && head_kind <= 2 && n_layers >= 2 && fuse_tail && act[l - 1] != ACT_KIND_IDENTITY) {
+      p.tail_w = w[l]->ptr; p.tail_h = h; p.tail_out = tail_out; p.tail_n = (int)prev_n; p.tail_kind = act[l - 1];
     }
     return p;
   }
@@ -76,8 +84,7 @@ struct StackStep {
   GemmProblem backward(int l, const void* dz, const void* h, void* out, int64_t B) const {
     const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
     GemmProblem q = row_gemm(dt, dz, n, 1, w[l]->ptr, m, 1, out, B, m, n);
-    q.dact = h;
-    q.dact_kind = hk;
+    if (act[l - 1] != ACT_KIND_IDENTITY) { q.dact = h; q.dact_kind = act[l - 1]; }
     return q;
   }
 
@@ -97,6 +104,12 @@ struct StackStep {
     for (int l = n_layers - 1; l > 0; --l)
       if (!(l == n_layers - 1 && fwd.tail_n)) fused_route(backward(l, nullptr, nullptr, nullptr, B));
   }
+  // ... and of a step of either kind: the weight gradients' walk as well, dry
+  void check_step(int64_t B) const {
+    check_sgd(B);
+    wgrads(nullptr, nullptr, B, true);
+  }
+  void wgrads(const void* const* dz, const void* const* a_in, int64_t B, bool dry) const;
   void launch(const void* x, const void* y, void* losses, int64_t B) const;
 };
 
@@ -106,30 +119,34 @@ void StackStep::launch(const void* x, const void* y, void* losses, int64_t B) co
   Holder tail;  // dz_{L-1} when the last layer's launch produced it
   GemmProblem fwd{};  // the last layer's launch
   // forward: a_l = act(a_{l-1} W_l^T + b_l) for hidden layers (act: hidden_act), z_L for the last
-  std::vector<Holder> act(n_layers);  // act[l]: [B; n_l]; the last holds z_L, then is reused as dz_L
+  std::vector<Holder> a(n_layers);  // a[l]: [B; n_l]; the last holds z_L, then is reused as dz_L
   const void* prev = x;
   for (int l = 0; l < n_layers; ++l) {
     const int64_t n = w[l]->dims[0], prev_n = w[l]->dims[1];
-    act[l].t = new_tensor(1, &n, B, dt);
+    a[l].t = new_tensor(1, &n, B, dt);
     // (last layer: the loss head runs in the same launch when the row fits one 16-wide tile; it also produces
     //  dz_{L-1} for its rows where the tail fuses)
     const bool last = l + 1 == n_layers;
     if (last && wants_tail()) tail.t = new_tensor(1, &prev_n, B, dt);
-    fwd = fused_gemm(forward(l, prev, act[l].t->ptr, B, y, losses, l > 0 ? act[l - 1].t->ptr : nullptr,
+    fwd = fused_gemm(forward(l, prev, a[l].t->ptr, B, y, losses, l > 0 ? a[l - 1].t->ptr : nullptr,
                              tail.t ? tail.t->ptr : nullptr));
-    prev = act[l].t->ptr;
+    prev = a[l].t->ptr;
   }
   // loss gradient wrt z_L, per sample row
   const int64_t nL = w[n_layers - 1]->dims[0];
   Holder cur;
   if (fwd.loss_rows) {
-    cur.t = act[n_layers - 1].t;  // already dz_L
-    act[n_layers - 1].t = nullptr;
-  } else {
+    cur.t = a[n_layers - 1].t;  // already dz_L
+    a[n_layers - 1].t = nullptr;
+  } else if (head_kind <= 2) {
     cur.t = new_tensor(1, &nL, B, dt);
-    launch_loss_grad_rows(dt, act[n_layers - 1].t->ptr, y, cur.t->ptr, losses, B, nL, loss_grad_rows_kind(head_kind), S());
+    launch_loss_grad_rows(dt, a[n_layers - 1].t->ptr, y, cur.t->ptr, losses, B, nL, loss_grad_rows_kind(head_kind), S());
+  } else {  // z_L -> dz_L in place (the bias went in with the GEMM's epilogue)
+    cur.t = a[n_layers - 1].t;
+    a[n_layers - 1].t = nullptr;
+    launch_recon_head(dt, head_kind, cur.t->ptr, nullptr, y, nL, cur.t->ptr, nullptr, losses, B, nL, S());
   }
-  auto a_in = [&](int l) -> const void* { return l > 0 ? act[l - 1].t->ptr : x; };
+  auto a_in = [&](int l) -> const void* { return l > 0 ? a[l - 1].t->ptr : x; };
   // backward, phase 1: every dz_l (the propagation reads W_l, which phase 2 may overwrite in place)
   std::vector<Holder> dz(n_layers);
   dz[n_layers - 1].t = cur.take();
@@ -139,25 +156,35 @@ void StackStep::launch(const void* x, const void* y, void* losses, int64_t B) co
     } else {
       const int64_t m = w[l]->dims[1];
       dz[l - 1].t = new_tensor(1, &m, B, dt);
-      fused_gemm(backward(l, dz[l].t->ptr, act[l - 1].t->ptr, dz[l - 1].t->ptr, B));
+      fused_gemm(backward(l, dz[l].t->ptr, a[l - 1].t->ptr, dz[l - 1].t->ptr, B));
     }
   }
-  // phase 2: the weight gradients, independent of each other.  The two last ones go out as ONE launch when
-  // their shapes allow (one launch floor, ~4 us, less per step: 33.6 -> 28.0 us on config 3).
-  // (Running them on a side stream instead measured slower: the fork/join events cost more than the overlap
-  // buys, 0.0485 -> 0.0591 ms/step.)
+  // phase 2: the weight gradients
+  std::vector<const void*> dzp((size_t)n_layers), ap((size_t)n_layers);
+  for (int l = 0; l < n_layers; ++l) { dzp[(size_t)l] = dz[l].t->ptr; ap[(size_t)l] = a_in(l); }
+  wgrads(dzp.data(), ap.data(), B, false);
+}
+
+// The weight gradients of a step, independent of each other: dz[l] / a_in[l] per layer.  dry: the same walk with its
+// refusals and nothing launched (dz / a_in null) -- check_step asks it, so what is refused is decided in ONE place.
+// The two last ones go out as ONE launch when
+// their shapes allow (one launch floor, ~4 us, less per step: 33.6 -> 28.0 us on config 3).
+// (Running them on a side stream instead measured slower: the fork/join events cost more than the overlap
+// buys, 0.0485 -> 0.0591 ms/step.)
+void StackStep::wgrads(const void* const* dz, const void* const* a_in, int64_t B, bool dry) const {
+  auto grad = [&](int l) { return wgrad(l, dry ? nullptr : dz[l], dry ? nullptr : a_in[l], B); };
   // one sample: every weight gradient is an outer product -- all layers in one launch
   static const int rank1 = [] { const char* e = ab_getenv("TOPS_STEP_RANK1"); return e ? atoi(e) : 1; }();
   if (B == 1 && rank1) {
-    for (int l0 = 0; l0 < n_layers; l0 += RANK1_MAX_LAYERS) {
+    for (int l0 = 0; l0 < n_layers && !dry; l0 += RANK1_MAX_LAYERS) {
       const int cnt = std::min(RANK1_MAX_LAYERS, n_layers - l0);
       const void *dzp[RANK1_MAX_LAYERS], *ap[RANK1_MAX_LAYERS];
       void *wp[RANK1_MAX_LAYERS], *bp[RANK1_MAX_LAYERS];
       int64_t rows[RANK1_MAX_LAYERS], cols[RANK1_MAX_LAYERS];
       for (int q = 0; q < cnt; ++q) {
         const int l = l0 + q;
-        dzp[q] = dz[l].t->ptr;
-        ap[q] = a_in(l);
+        dzp[q] = dz[l];
+        ap[q] = a_in[l];
         wp[q] = gw[l]->ptr;
         bp[q] = gb[l]->ptr;
         rows[q] = w[l]->dims[0];
@@ -168,22 +195,36 @@ void StackStep::launch(const void* x, const void* y, void* losses, int64_t B) co
     return;
   }
   int first = n_layers - 1;
-  if (n_layers >= 2 &&
-      launch_gemm_small_pair(wgrad(n_layers - 2, dz[n_layers - 2].t->ptr, a_in(n_layers - 2), B),
-                             wgrad(n_layers - 1, dz[n_layers - 1].t->ptr, a_in(n_layers - 1), B), S()))
-    first = n_layers - 3;
+  if (n_layers >= 2 && launch_gemm_small_pair(grad(n_layers - 2), grad(n_layers - 1), S(), dry)) first = n_layers - 3;
   for (int l = first; l >= 0; --l) {
-    const GemmProblem p = wgrad(l, dz[l].t->ptr, a_in(l), B);
+    const GemmProblem p = grad(l);
     if (gemm_small_takes(p)) {
-      launch_gemm_small(p, S());
+      if (!dry) launch_gemm_small(p, S());
       continue;
     }
     TO_CHECK(dt == TO_F32, TO_ERR_UNSUPPORTED, "pre-fused fp64 path: a contraction is outside the small-GEMM range");
+    if (dry) continue;
     GemmProblem q = p;
     q.rowsum = nullptr;
     launch_gemm_mfma(q, S());
-    launch_sum_axis(dt, dz[l].t->ptr, gb[l]->ptr, 1, B, w[l]->dims[0], 0, w[l]->dims[0], 1, S());
+    launch_sum_axis(dt, dz[l], gb[l]->ptr, 1, B, w[l]->dims[0], 0, w[l]->dims[0], 1, S());
   }
+}
+
+// A validated step on the batch of x (y: x itself for an autoencoder): operands produced, destinations claimed, launched.
+static void step_on_batch(const StackStep& step, to_tensor x, to_tensor y, to_tensor losses) {
+  const int n_layers = step.n_layers;
+  const to_tensor *w = step.w, *b = step.b, *gw = step.gw, *gb = step.gb;
+  ensure(x);
+  ensure(y);
+  if (losses) { ensure(losses); before_write(losses); }
+  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); ensure(gw[l]); ensure(gb[l]); }
+  for (int l = 0; l < n_layers; ++l) {  // (identities: sgd's parameters get a new one, grad's destinations keep theirs)
+    before_write(gw[l]);
+    before_write(gb[l]);
+    if (step.sgd) { w[l]->id = fresh_id(); b[l]->id = fresh_id(); }
+  }
+  step.launch(x->ptr, y->ptr, losses ? losses->ptr : nullptr, x->batch);
 }
 
 static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
@@ -205,20 +246,10 @@ static void fflayer_stack_impl(int n_layers, const to_tensor* w, const to_tensor
   TO_CHECK(y->dims[0] == fan_in, TO_ERR_SHAPE, "y does not match the output layer");
   if (losses) TO_CHECK(losses->rank == 0 && losses->batch == B && losses->contiguous(), TO_ERR_SHAPE,
                        "losses must be a batched scalar");
-  const StackStep step{n_layers, w, b, gw, gb, hk, head_kind, dt, sgd, rate};
+  const std::vector<int> acts((size_t)n_layers, hk);
+  const StackStep step{n_layers, w, b, gw, gb, acts.data(), head_kind, dt, sgd, rate};
   step.check_wgrads(B);
-
-  // ---- operands produced; destinations claimed -----------------------------------------------------------------------
-  ensure(x);
-  ensure(y);
-  if (losses) { ensure(losses); before_write(losses); }
-  for (int l = 0; l < n_layers; ++l) { ensure(w[l]); ensure(b[l]); ensure(gw[l]); ensure(gb[l]); }
-  for (int l = 0; l < n_layers; ++l) {  // (identities: sgd's parameters get a new one, grad's destinations keep theirs)
-    before_write(gw[l]);
-    before_write(gb[l]);
-    if (sgd) { w[l]->id = fresh_id(); b[l]->id = fresh_id(); }
-  }
-  step.launch(x->ptr, y->ptr, losses ? losses->ptr : nullptr, B);
+  step_on_batch(step, x, y, losses);
 }
 
 to_status to_fflayer_stack_grad(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act,
@@ -243,6 +274,9 @@ to_status to_fflayer_stack_sgd(int n_layers, const to_tensor* w, const to_tensor
 // look at.
 static int64_t g_minibatch_stage_bytes = MINIBATCH_STAGE_DEFAULT;
 
+static void minibatch_steps(const StackStep& step, to_tensor X, to_tensor Y, int64_t n_idx, const int64_t* idx, int64_t M,
+                            to_tensor losses, const std::string& F);
+
 static void minibatch_sgd_impl(int n_layers, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss,
                                to_tensor X, to_tensor Y, int64_t n_idx, const int64_t* idx, int64_t M, double rate,
                                to_tensor losses) {
@@ -260,6 +294,8 @@ static void minibatch_sgd_impl(int n_layers, const to_tensor* w, const to_tensor
   const int dt = X->dtype;
   const int64_t N = X->batch, i0 = X->dims[0];
   const int64_t nL = stack_params_check(n_layers, w, b, nullptr, nullptr, dt, i0);
+  const std::vector<int> acts((size_t)n_layers, hk);
+  const StackStep step{n_layers, w, b, w, b, acts.data(), head_kind, dt, true, rate};
   if (Y) {
     TO_CHECK(Y->dtype == dt, TO_ERR_ARG, F + "X and Y have different dtypes");
     TO_CHECK(Y->rank == 1 && Y->dims[0] == nL && Y->batch == N, TO_ERR_SHAPE,
@@ -268,6 +304,16 @@ static void minibatch_sgd_impl(int n_layers, const to_tensor* w, const to_tensor
   } else {
     TO_CHECK(nL == i0, TO_ERR_SHAPE, F + "without Y the target of a row is the row itself: the output layer must have X's width");
   }
+  minibatch_steps(step, X, Y, n_idx, idx, M, losses, F);
+}
+
+// What the two minibatch entries share behind the validation of their stacks: X [N; i0] contiguous, Y null or [N; n_L]
+// contiguous of X's dtype, n_idx >= 1, M >= 1; step: an sgd step on the stack's own parameters.
+static void minibatch_steps(const StackStep& step, to_tensor X, to_tensor Y, int64_t n_idx, const int64_t* idx, int64_t M,
+                            to_tensor losses, const std::string& F) {
+  const int n_layers = step.n_layers, dt = step.dt;
+  const to_tensor *w = step.w, *b = step.b;
+  const int64_t N = X->batch, i0 = X->dims[0], nL = w[n_layers - 1]->dims[0];
   if (losses) {
     TO_CHECK(losses->dtype == dt, TO_ERR_ARG, F + "X and losses have different dtypes");
     TO_CHECK(losses->rank == 0 && losses->batch == n_idx && losses->contiguous(), TO_ERR_SHAPE,
@@ -282,7 +328,6 @@ static void minibatch_sgd_impl(int n_layers, const to_tensor* w, const to_tensor
   if (M > n_idx) M = n_idx;
   const int64_t n_steps = (n_idx + M - 1) / M, tail_rows = n_idx - (n_steps - 1) * M;
   // nothing half-trained: every refusal of a step, for both batches that occur, before the first launch
-  const StackStep step{n_layers, w, b, w, b, hk, head_kind, dt, true, rate};
   step.check_sgd(M);
   if (tail_rows != M) step.check_sgd(tail_rows);
 
@@ -354,6 +399,245 @@ to_status to_set_minibatch_stage_bytes(int64_t bytes, int64_t* previous_or_null)
   TO_CHECK(bytes >= 0, TO_ERR_ARG, "to_set_minibatch_stage_bytes: a byte count, or 0 for the default");
   if (previous_or_null) *previous_or_null = g_minibatch_stage_bytes;
   g_minibatch_stage_bytes = bytes ? bytes : MINIBATCH_STAGE_DEFAULT;
+  API_END
+}
+
+// ---- encoder / decoder pairs of ffLayer stacks (AutoEncoder.hs) -----------------------------------------------------------
+// Layers 0 .. n_enc-1 are the encoder, n_enc .. L-1 the decoder; act[n_enc-1] = code_act (logistic, tanh or none), the head
+// one of four pairs, the target of a row the row itself.  grad / sgd / minibatch_sgd are StackStep with those per-layer
+// activations on (x, y = x): a uniform stack with one of the two old pairs issues to_fflayer_stack_*'s launches.
+static int ae_act_kind(int act, bool identity_too, const std::string& what) {
+  if (act == TO_ACT_LOGISTIC) return ACT_KIND_LOGISTIC;
+  if (act == TO_ACT_TANH) return ACT_KIND_TANH;
+  if (act == TO_ACT_IDENTITY && identity_too) return ACT_KIND_IDENTITY;
+  fail(TO_ERR_UNSUPPORTED, what + (identity_too ? " must be logistic, tanh or identity" : " must be logistic or tanh"));
+}
+// stack_loss_head's numbers and, behind them, 3 = (tanh, squaredError), 4 = (identity, squaredError): launch_recon_head's pairs
+static int ae_loss_head(int out_act, int loss, const std::string& F) {
+  if (out_act == TO_ACT_SOFTMAX && loss == TO_LOSS_CROSS_ENTROPY) return 1;
+  if (loss == TO_LOSS_SQUARED_ERROR && out_act == TO_ACT_LOGISTIC) return 2;
+  if (loss == TO_LOSS_SQUARED_ERROR && out_act == TO_ACT_TANH) return 3;
+  if (loss == TO_LOSS_SQUARED_ERROR && out_act == TO_ACT_IDENTITY) return 4;
+  fail(TO_ERR_UNSUPPORTED, F + "(softmax, crossEntropy) or (logistic / tanh / identity, squaredError) only");
+}
+static std::vector<int> ae_acts(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int code_act,
+                                const std::string& F) {
+  NONNULL(w); NONNULL(b);
+  TO_CHECK(n_enc >= 1 && n_dec >= 1, TO_ERR_ARG, F + "the encoder and the decoder need at least one layer each");
+  std::vector<int> acts((size_t)(n_enc + n_dec), ae_act_kind(hidden_act, false, F + "the hidden activation"));
+  acts[(size_t)n_enc - 1] = ae_act_kind(code_act, true, F + "the code activation");
+  return acts;
+}
+// an output of the batch of `like`: n-vectors (n = 0: scalars), contiguous, of its dtype
+static void ae_out_check(to_tensor t, to_tensor like, int64_t n, const std::string& F, const char* what) {
+  TO_CHECK(t->dtype == like->dtype, TO_ERR_ARG, F + "x and " + what + " have different dtypes");
+  TO_CHECK((n ? t->rank == 1 && t->dims[0] == n : t->rank == 0) && t->batch == like->batch, TO_ERR_SHAPE,
+           F + what + " must be " + (n ? std::to_string(n) + "-vectors" : std::string("scalars")) + " of the input's batch, got " +
+               shape_str(t));
+  TO_CHECK(t->contiguous(), TO_ERR_ARG, F + what + " must be contiguous");
+}
+// run / decode write caller-allocated tensors while their inputs are still being read (recon == x would have the last GEMM
+// write z over the target rows): an output may overlap neither an input, nor another output, nor a parameter
+static bool ae_overlap(to_tensor s, to_tensor t) {
+  if (!s || !t || !s->ptr || !t->ptr) return false;   // (a handle without storage yet shares none)
+  auto end = [](to_tensor u) {
+    int64_t last = u->batch > 1 ? (u->batch - 1) * u->bstride : 0;
+    for (int d = 0; d < u->rank; ++d) last += (u->dims[d] - 1) * u->strides[d];
+    return static_cast<const char*>(u->ptr) + (last + 1) * (int64_t)u->esize();
+  };
+  return static_cast<const char*>(s->ptr) < end(t) && static_cast<const char*>(t->ptr) < end(s);
+}
+static void ae_no_alias(std::initializer_list<to_tensor> outs, to_tensor in, int n, const to_tensor* w, const to_tensor* b,
+                        const std::string& F) {
+  for (auto o = outs.begin(); o != outs.end(); ++o) {
+    bool bad = ae_overlap(*o, in);
+    for (auto q = outs.begin(); q != o; ++q) bad = bad || ae_overlap(*o, *q);
+    for (int l = 0; l < n; ++l) bad = bad || ae_overlap(*o, w[l]) || ae_overlap(*o, b[l]);
+    TO_CHECK(!bad, TO_ERR_ARG, F + "an output overlaps the input, another output or a parameter");
+  }
+}
+// C[B, n_l] = act(A W_l^T + b_l) the way to_fflayer_stack_infer's hidden layers go: one GEMM with the epilogue where the
+// kernel carries one, else the plain product and one elementwise launch
+static void ae_layer(int dt, to_tensor W, to_tensor bias, int act_kind, const void* A, int64_t a_sm, void* C, int64_t B) {
+  GemmProblem p = row_gemm(dt, A, a_sm, 1, W->ptr, 1, W->dims[1], C, B, W->dims[0], W->dims[1]);
+  p.bias = bias->ptr;
+  p.act = act_kind + 1;
+  if (gemm_epilogue_ok(p)) {
+    if (gemm_small_route(p)) launch_gemm_small(p, S());
+    else run_gemm(p);
+    return;
+  }
+  p.bias = nullptr;
+  p.act = 0;
+  run_gemm(p);
+  launch_bias_act_rows(dt, C, bias->ptr, B, W->dims[0], act_kind, S());
+}
+// layers l0 .. l1-1, each with its activation; the last one into `last_out` (null: scratch).  Returns where the last one is.
+static const void* ae_layers(int dt, const to_tensor* w, const to_tensor* b, const int* acts, int l0, int l1, const void* prev,
+                             int64_t prev_sm, int64_t B, void* last_out, std::deque<Holder>& keep) {
+  for (int l = l0; l < l1; ++l) {
+    const int64_t n = w[l]->dims[0];
+    void* C = last_out;
+    if (l + 1 < l1 || !C) {
+      keep.emplace_back(new_tensor(1, &n, B, dt));
+      C = keep.back().t->ptr;
+    }
+    ae_layer(dt, w[l], b[l], acts[l], prev, prev_sm, C, B);
+    prev = C;
+    prev_sm = n;
+  }
+  return prev;
+}
+// the decoder from the code rows on: its hidden layers, the last contraction into z (out itself, or scratch) and the head
+static void ae_decoder(int dt, int n_enc, int L, const to_tensor* w, const to_tensor* b, const int* acts, int head,
+                       const void* code, int64_t code_sm, const void* target, int64_t t_sm, void* out, void* losses, int64_t B) {
+  std::deque<Holder> keep;
+  const void* prev = ae_layers(dt, w, b, acts, n_enc, L - 1, code, code_sm, B, nullptr, keep);
+  const to_tensor WL = w[L - 1];
+  const int64_t nL = WL->dims[0], prev_sm = L - 1 > n_enc ? WL->dims[1] : code_sm;
+  void* z = out;  // (the head reads each element of z before it writes the same element of out)
+  if (!z) {
+    keep.emplace_back(new_tensor(1, &nL, B, dt));
+    z = keep.back().t->ptr;
+  }
+  run_gemm(row_gemm(dt, prev, prev_sm, 1, WL->ptr, 1, WL->dims[1], z, B, nL, WL->dims[1]));
+  launch_recon_head(dt, head, z, b[L - 1]->ptr, target, t_sm, nullptr, out, losses, B, nL, S());
+}
+
+static void ae_run_impl(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int code_act, int out_act,
+                        int loss, to_tensor x, to_tensor code, to_tensor recon, to_tensor losses) {
+  const std::string F = "to_autoencoder_stack_run: ";
+  require_init();
+  no_capture("to_autoencoder_stack_run");
+  NONNULL(x);
+  const std::vector<int> acts = ae_acts(n_enc, n_dec, w, b, hidden_act, code_act, F);
+  const int head = ae_loss_head(out_act, loss, F), L = n_enc + n_dec;
+  TO_CHECK(code || recon || losses, TO_ERR_ARG, F + "no output asked for (code, recon or losses)");
+  TO_CHECK(x->rank == 1 && x->dims[0] >= 1, TO_ERR_SHAPE, F + "x must be a (batched) vector, got " + shape_str(x));
+  const int dt = x->dtype;
+  const int64_t i0 = x->dims[0], B = x->batch > 0 ? x->batch : 1;
+  const int64_t c = stack_params_check(n_enc, w, b, nullptr, nullptr, dt, i0);
+  TO_CHECK(stack_params_check(n_dec, w + n_enc, b + n_enc, nullptr, nullptr, dt, c) == i0, TO_ERR_SHAPE,
+           F + "the decoder's last layer must have x's width");
+  if (code) ae_out_check(code, x, c, F, "code");
+  if (recon) ae_out_check(recon, x, i0, F, "recon");
+  if (losses) ae_out_check(losses, x, 0, F, "losses");
+  ae_no_alias({code, recon, losses}, x, L, w, b, F);
+  ensure(x);
+  for (int l = 0; l < L; ++l) { ensure(w[l]); ensure(b[l]); }
+  if (code) claim(code);
+  if (recon) claim(recon);
+  if (losses) claim(losses);
+  // rows with unit element stride (a strided vector view is packed first); the rows themselves may lie anywhere
+  Holder xc;
+  const to_tensor xr = unit_stride_rows(x, xc);
+  const int64_t x_sm = x->batch > 0 ? xr->bstride : i0;
+  std::deque<Holder> keep;
+  const void* cp = ae_layers(dt, w, b, acts.data(), 0, n_enc, xr->ptr, x_sm, B, code ? code->ptr : nullptr, keep);
+  if (recon || losses)   // (code alone: the decoder is not run)
+    ae_decoder(dt, n_enc, L, w, b, acts.data(), head, cp, c, xr->ptr, x_sm, recon ? recon->ptr : nullptr,
+               losses ? losses->ptr : nullptr, B);
+}
+
+static void ae_decode_impl(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                           to_tensor code, to_tensor out) {
+  const std::string F = "to_autoencoder_stack_decode: ";
+  require_init();
+  no_capture("to_autoencoder_stack_decode");
+  NONNULL(code); NONNULL(out);
+  const std::vector<int> acts = ae_acts(n_enc, n_dec, w, b, hidden_act, TO_ACT_IDENTITY, F);
+  const int head = ae_loss_head(out_act, out_act == TO_ACT_SOFTMAX ? TO_LOSS_CROSS_ENTROPY : TO_LOSS_SQUARED_ERROR, F);
+  const int L = n_enc + n_dec;
+  TO_CHECK(code->rank == 1 && code->dims[0] >= 1, TO_ERR_SHAPE, F + "code must be a (batched) vector, got " + shape_str(code));
+  const int dt = code->dtype;
+  const int64_t c = code->dims[0], B = code->batch > 0 ? code->batch : 1;
+  const int64_t nL = stack_params_check(n_dec, w + n_enc, b + n_enc, nullptr, nullptr, dt, c);
+  ae_out_check(out, code, nL, F, "out");
+  ae_no_alias({out}, code, n_dec, w + n_enc, b + n_enc, F);
+  ensure(code);
+  for (int l = n_enc; l < L; ++l) { ensure(w[l]); ensure(b[l]); }
+  claim(out);
+  Holder cc;
+  const to_tensor cr = unit_stride_rows(code, cc);
+  ae_decoder(dt, n_enc, L, w, b, acts.data(), head, cr->ptr, code->batch > 0 ? cr->bstride : c, nullptr, 0, out->ptr, nullptr, B);
+}
+
+static void ae_step_impl(const std::string& F, int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act,
+                         int code_act, int out_act, int loss, to_tensor x, const to_tensor* gw, const to_tensor* gb,
+                         to_tensor losses, bool sgd, double rate) {
+  require_init();
+  NONNULL(x); NONNULL(gw); NONNULL(gb);
+  const std::vector<int> acts = ae_acts(n_enc, n_dec, w, b, hidden_act, code_act, F);
+  const int head = ae_loss_head(out_act, loss, F), L = n_enc + n_dec;
+  TO_CHECK(x->rank == 1 && x->batch > 0, TO_ERR_SHAPE, F + "x must be batched vectors, got " + shape_str(x));
+  TO_CHECK(x->contiguous(), TO_ERR_ARG, F + "x must be contiguous");
+  const int dt = x->dtype;
+  TO_CHECK(stack_params_check(L, w, b, gw, gb, dt, x->dims[0]) == x->dims[0], TO_ERR_SHAPE,
+           F + "the decoder's last layer must have x's width");
+  if (losses) ae_out_check(losses, x, 0, F, "losses");
+  const StackStep step{L, w, b, gw, gb, acts.data(), head, dt, sgd, rate};
+  step.check_step(x->batch);   // every refusal before the first launch
+  step_on_batch(step, x, x, losses);
+}
+
+static void ae_minibatch_impl(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int code_act,
+                              int out_act, int loss, to_tensor X, int64_t n_idx, const int64_t* idx, int64_t M, double rate,
+                              to_tensor losses) {
+  const std::string F = "to_autoencoder_stack_minibatch_sgd: ";
+  require_init();
+  no_capture("to_autoencoder_stack_minibatch_sgd");
+  NONNULL(X);
+  const std::vector<int> acts = ae_acts(n_enc, n_dec, w, b, hidden_act, code_act, F);
+  const int head = ae_loss_head(out_act, loss, F), L = n_enc + n_dec;
+  TO_CHECK(n_idx >= 1 && M >= 1, TO_ERR_ARG, F + "needs at least one sample and a minibatch of at least one row");
+  TO_CHECK(X->rank == 1 && X->batch > 0, TO_ERR_SHAPE, F + "X must be batched vectors, got " + shape_str(X));
+  TO_CHECK(X->contiguous(), TO_ERR_ARG, F + "X must be contiguous");
+  const int dt = X->dtype;
+  TO_CHECK(stack_params_check(L, w, b, nullptr, nullptr, dt, X->dims[0]) == X->dims[0], TO_ERR_SHAPE,
+           F + "the decoder's last layer must have X's width");
+  const StackStep step{L, w, b, w, b, acts.data(), head, dt, true, rate};
+  minibatch_steps(step, X, nullptr, n_idx, idx, M, losses, F);
+}
+
+to_status to_autoencoder_stack_run(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int code_act,
+                                   int out_act, int loss, to_tensor x, to_tensor code_or_null, to_tensor recon_or_null,
+                                   to_tensor losses_or_null) {
+  API_BEGIN
+  ae_run_impl(n_enc, n_dec, w, b, hidden_act, code_act, out_act, loss, x, code_or_null, recon_or_null, losses_or_null);
+  API_END
+}
+
+to_status to_autoencoder_stack_decode(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int out_act,
+                                      to_tensor code, to_tensor out) {
+  API_BEGIN
+  ae_decode_impl(n_enc, n_dec, w, b, hidden_act, out_act, code, out);
+  API_END
+}
+
+to_status to_autoencoder_stack_grad(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int code_act,
+                                    int out_act, int loss, to_tensor x, const to_tensor* gw, const to_tensor* gb,
+                                    to_tensor losses_or_null) {
+  API_BEGIN
+  ae_step_impl("to_autoencoder_stack_grad: ", n_enc, n_dec, w, b, hidden_act, code_act, out_act, loss, x, gw, gb,
+               losses_or_null, false, 0.0);
+  API_END
+}
+
+to_status to_autoencoder_stack_sgd(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int code_act,
+                                   int out_act, int loss, to_tensor x, double rate, to_tensor losses_or_null) {
+  API_BEGIN
+  ae_step_impl("to_autoencoder_stack_sgd: ", n_enc, n_dec, w, b, hidden_act, code_act, out_act, loss, x, w, b, losses_or_null,
+               true, rate);
+  API_END
+}
+
+to_status to_autoencoder_stack_minibatch_sgd(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act,
+                                             int code_act, int out_act, int loss, to_tensor X, int64_t n_idx,
+                                             const int64_t* idx_or_null, int64_t minibatch, double rate,
+                                             to_tensor losses_or_null) {
+  API_BEGIN
+  ae_minibatch_impl(n_enc, n_dec, w, b, hidden_act, code_act, out_act, loss, X, n_idx, idx_or_null, minibatch, rate,
+                    losses_or_null);
   API_END
 }
 

@@ -471,6 +471,73 @@ class HipT:
         check(lib().to_set_minibatch_stage_bytes(int(nbytes), C.byref(prev)))
         return prev.value
 
+    # -- encoder / decoder pairs (to_autoencoder_stack_*) -----------------------------------------------------------------
+    # ws / bs: every layer's parameters in input-to-output order, the first n_enc of them the encoder; code_act the encoder's
+    # output activation, (out_act, loss) the reconstruction head; the target of a row is the row itself
+    _AE_ACT = {"logistic": 0, "softmax": 2, "tanh": 3, "identity": 4}
+
+    def _ae_args(self, ws, bs, n_enc, hidden_act, code_act, out_act=None, loss=None):
+        a = [int(n_enc), len(ws) - int(n_enc), _arr(ws), _arr(bs), self._AE_ACT[hidden_act]]
+        if code_act is not None:
+            a.append(self._AE_ACT[code_act])
+        a.append(self._AE_ACT[out_act])
+        if loss is not None:
+            a.append(self._RNN_LOSS[loss])
+        return a
+
+    def autoencoder_run(self, ws, bs, n_enc, x, out_act="logistic", loss="squaredError", hidden_act="logistic",
+                        code_act="logistic", want_code=True, want_recon=True, want_losses=True):
+        """`encode`, `encodeDecode` and `testEncoder` over the batch of x (to_autoencoder_stack_run): (code, recon, losses),
+        None where not asked for"""
+        _, batch = x._shape()
+        code = self._alloc((ws[n_enc - 1].shape[0],), batch) if want_code else None
+        recon = self._alloc((ws[-1].shape[0],), batch) if want_recon else None
+        losses = self._alloc((), batch) if want_losses else None
+        check(lib().to_autoencoder_stack_run(*self._ae_args(ws, bs, n_enc, hidden_act, code_act, out_act, loss), x.h,
+                                             *[t.h if t is not None else None for t in (code, recon, losses)]))
+        return code, recon, losses
+
+    def autoencoder_decode(self, ws, bs, n_enc, code, out_act="logistic", hidden_act="logistic"):
+        """`decode` over the batch of code (to_autoencoder_stack_decode)"""
+        _, batch = code._shape()
+        out = self._alloc((ws[-1].shape[0],), batch)
+        check(lib().to_autoencoder_stack_decode(*self._ae_args(ws, bs, n_enc, hidden_act, None, out_act), code.h, out.h))
+        return out
+
+    def autoencoder_grad(self, ws, bs, n_enc, x, out_act="logistic", loss="squaredError", hidden_act="logistic",
+                         code_act="logistic", want_losses=False):
+        """`encGrad` summed over the batch of x (to_autoencoder_stack_grad): (gW list, gb list, losses [B] or None)"""
+        gW = [self._alloc(w.shape, 0) for w in ws]
+        gB = [self._alloc(b.shape, 0) for b in bs]
+        losses = self._alloc((), x.batch) if want_losses else None
+        check(lib().to_autoencoder_stack_grad(*self._ae_args(ws, bs, n_enc, hidden_act, code_act, out_act, loss), x.h,
+                                              _arr(gW), _arr(gB), losses.h if losses is not None else None))
+        return gW, gB, losses
+
+    def autoencoder_sgd(self, ws, bs, n_enc, x, rate, out_act="logistic", loss="squaredError", hidden_act="logistic",
+                        code_act="logistic", want_losses=False):
+        """`trainEncoder` on one batch, parameters updated in place (to_autoencoder_stack_sgd)"""
+        losses = self._alloc((), x.batch) if want_losses else None
+        check(lib().to_autoencoder_stack_sgd(*self._ae_args(ws, bs, n_enc, hidden_act, code_act, out_act, loss), x.h,
+                                             float(rate), losses.h if losses is not None else None))
+        return losses
+
+    def autoencoder_minibatch_sgd(self, ws, bs, n_enc, X, rate, minibatch, idx=None, n=None, out_act="logistic",
+                                  loss="squaredError", hidden_act="logistic", code_act="logistic", want_losses=False):
+        """stack_minibatch_sgd with Y None for an encoder / decoder pair (to_autoencoder_stack_minibatch_sgd)"""
+        arr = None
+        if idx is not None:
+            arr = np.ascontiguousarray(idx, dtype=np.int64)
+            n = len(arr) if n is None else n
+        elif n is None:
+            n = X.batch
+        losses = self._alloc((), int(n)) if want_losses and n >= 1 else None
+        check(lib().to_autoencoder_stack_minibatch_sgd(
+            *self._ae_args(ws, bs, n_enc, hidden_act, code_act, out_act, loss), X.h, int(n),
+            arr.ctypes.data_as(C.POINTER(C.c_int64)) if arr is not None else None, int(minibatch), float(rate),
+            losses.h if losses is not None else None))
+        return losses
+
     def stack_online_sgd(self, ws, bs, X, Y, n, rate, idx=None, out_act="softmax", loss="crossEntropy",
                          hidden_act="logistic"):
         """per-sample SGD over rows idx[0..n) (None: rows 0..n-1) of X / Y in one launch, parameters updated in place

@@ -264,6 +264,33 @@ to_status to_plan_cache_clear(void);
 /* host time spent inside this library's entry points and how many were called, since start (the rest of a step's
  * host time is the caller's own) */
 to_status to_api_time(int64_t* ns, int64_t* calls);
+/* Debug: which kernel families a contraction would go to, without launching anything (csrc/gemm_route.cpp).
+ * The families are numbered in the order the plan asks them. */
+enum {
+  TO_GEMM_FAMILY_GEMV = 0,
+  TO_GEMM_FAMILY_T32 = 1, /* development builds with TOPS_T32_FIRST=1 only */
+  TO_GEMM_FAMILY_SKINNYK = 2,
+  TO_GEMM_FAMILY_SKINNYK64 = 3,
+  TO_GEMM_FAMILY_KW16 = 4,
+  TO_GEMM_FAMILY_KW = 5,
+  TO_GEMM_FAMILY_KW64 = 6,
+  TO_GEMM_FAMILY_SMALL = 7,
+  TO_GEMM_FAMILY_MFMA = 8,
+  TO_GEMM_FAMILY_F64 = 9,
+  TO_GEMM_FAMILY_NAIVE = 10
+};
+enum { TO_GEMM_EPI_BIAS = 1, TO_GEMM_EPI_ACT = 2, TO_GEMM_EPI_DACT = 4, TO_GEMM_EPI_BETA = 8, TO_GEMM_EPI_ROWSUM = 16 };
+/* The problem: C[m, n] = A[m, k] . B[k, n] of `dtype`, `batch` >= 1 of them (reduce_batch: summed into one C), each operand
+ * contiguous or (x_transposed) stored transposed, C contiguous, alpha = 1; `epilogue` is a set of TO_GEMM_EPI_* (BETA:
+ * beta = 1 with an addend).  The operands are aligned dummies that nothing dereferences.
+ * Out: *n_leaves launches, the first `capacity` of their families in launch order (-1: the library would refuse the
+ * problem, to_last_error says why); whether the library fuses an epilogue into this product (*epilogue_ok) and whether
+ * its callers hand it to the small-GEMM kernel themselves (*small_route); whether the wave-split kernels' workspace for
+ * several workgroups per tile exists (*split_workspace: the placement probe of to_init held).  The last three may be NULL.
+ * TO_ERR_STATE before to_init. */
+to_status to_gemm_route_query(int dtype, int64_t m, int64_t n, int64_t k, int64_t batch, int reduce_batch, int a_transposed,
+                              int b_transposed, int epilogue, int capacity, int* families, int* n_leaves, int* epilogue_ok,
+                              int* small_route, int* split_workspace);
 /* stream capture of everything enqueued between begin/end into a HIP graph */
 to_status to_graph_begin(void);
 to_status to_graph_end(to_graph* out);

@@ -13,6 +13,9 @@ c_graph = C.c_void_p
 i64p = C.POINTER(C.c_int64)
 TO_F32 = 0
 TO_F64 = 1
+# TO_GEMM_FAMILY_* by number, TO_GEMM_EPI_* by name (to_gemm_route_query)
+GEMM_FAMILIES = ("gemv", "t32", "skinnyk", "skinnyk64", "kw16", "kw", "kw64", "small", "mfma", "f64", "naive")
+GEMM_EPILOGUE_BITS = {"bias": 1, "act": 2, "dact": 4, "beta": 8, "rowsum": 16}
 
 # name -> argtypes ; every function returns int32 status except to_last_error
 SIGNATURES = {
@@ -88,6 +91,9 @@ SIGNATURES = {
     "to_lazy_stats": [i64p, i64p, i64p, i64p],
     "to_lazy_time": [i64p, i64p],
     "to_api_time": [i64p, i64p],
+    "to_gemm_route_query": [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                            C.POINTER(C.c_int)],
     "to_transfer_stats": [i64p, i64p, i64p, i64p],
     "to_plan_cache_stats": [i64p, i64p, i64p],
     "to_plan_cache_clear": [],

@@ -63,170 +63,6 @@ static Group collapse(int n, const int64_t* dims, const int64_t* strides) {
   return g;
 }
 
-// A sub-block of the output (rows [r0, r0+m), columns [c0, c0+n)) as a problem of its own.
-static GemmProblem gemm_block(const GemmProblem& p, int64_t r0, int64_t m, int64_t c0, int64_t n) {
-  GemmProblem q = p;
-  const int64_t es = p.dtype == TO_F64 ? 8 : 4;
-  auto adv = [es](const void* ptr, int64_t elems) -> const void* {
-    return ptr ? static_cast<const void*>(static_cast<const char*>(ptr) + elems * es) : nullptr;
-  };
-  q.M = m; q.N = n;
-  q.A = adv(p.A, r0 * p.a_sm);
-  q.B = adv(p.B, c0 * p.b_sn);
-  q.C = const_cast<void*>(adv(p.C, r0 * p.c_sm + c0));
-  q.Cin = adv(p.Cin, r0 * p.c_sm + c0);
-  q.bias = adv(p.bias, c0);
-  q.dact = adv(p.dact, r0 * p.c_sm + c0);
-  return q;
-}
-
-// Which kernel run_gemm hands a (non-empty, unsplit) problem to.
-enum GemmRoute { ROUTE_SMALL, ROUTE_MFMA, ROUTE_F64, ROUTE_NAIVE };
-static GemmRoute gemm_route(const GemmProblem& p) {
-  const bool sliver = p.K >= 256 && p.M * p.N >= 256 && gemm_small_can(p) &&
-                      ((p.M + 15) / 16) * ((p.N + 15) / 16) * p.batch <= 4096;
-  if (gemm_mfma_worthwhile(p) && gemm_small_applicable(p)) return ROUTE_SMALL;  // few tiles, long K
-  if (gemm_mfma_worthwhile(p) && (p.reduce_batch || p.batch <= 65535)) return p.dtype == TO_F64 ? ROUTE_F64 : ROUTE_MFMA;
-  // a sliver (fewer than 8 rows or columns) with a long K -- e.g. the border strip of a split: one thread per
-  // output element would walk K serially (4 x 4096 x 4096: 0.95 ms); the small-GEMM kernel splits K
-  if (sliver) return ROUTE_SMALL;
-  return ROUTE_NAIVE;
-}
-
-bool gemm_small_route(const GemmProblem& p) {
-  if (p.M == 0 || p.N == 0 || p.K == 0 || p.batch != 1 || p.reduce_batch) return false;
-  if (gemv_form(p)) return false;   // (a large matVec / vecMat / outer product: gemv.hip, through run_gemm)
-  // (a few tiles under a very long K -- a weight gradient over a data set, 300 x 60000 x 784: one workgroup a tile here whatever K
-  //  is, 400 us; 291 split over workgroups in gemm_kwave.hip, which carries alpha / beta C / bias / activation but no row sums)
-  if (p.K >= 8192 && !p.rowsum && !p.loss_rows && !p.tail_out && gemm_kw_long_k(p)) return false;
-  return gemm_small_takes(p);
-}
-
-// The fused elementwise epilogue (alpha, beta*Cin, bias, act, dact) exists in the small-GEMM kernel (both element
-// types), the tiled fp32 kernel and the one-thread-per-element fallback (where border strips and K tails of a problem
-// run_gemm splits may land) and both wave-split kernels (gemm_kwave*.hip); the tiled fp64 kernel has alpha/beta only.
-// (lazy.cpp launches the small-GEMM kernel itself when gemm_small_route holds, and run_gemm otherwise.)
-bool gemm_epilogue_ok(const GemmProblem& p) {
-  if (p.M == 0 || p.N == 0 || p.K == 0 || p.batch == 0) return false;
-  if (gemm_small_route(p) || gemm_skinnyk_applicable(p) || gemm_skinnyk64_applicable(p) || gemv_form(p)) return true;
-  if (p.dtype == TO_F64) return gemm_kw64_applicable(p);
-  const GemmRoute r = gemm_route(p);
-  return r == ROUTE_SMALL || r == ROUTE_MFMA;
-}
-
-void run_gemm(const GemmProblem& p) {
-  if (p.M == 0 || p.N == 0 || p.batch == 0) return;
-  TO_CHECK(p.M <= 2147483647LL && p.N <= 2147483647LL && p.K <= 2147483647LL, TO_ERR_SHAPE,
-           "collapsed GEMM extent exceeds 2^31-1");
-  // Large GEMMs whose extents are no multiple of the 256x256 (fp64: 256x128) tile, or whose tile count is no multiple of
-  // the 256 CUs: the fast full-tile kernel gets the largest block of (nearly) WHOLE ROUNDS of tiles, the two border
-  // strips go their own way (smaller tiles, split-K, the small-GEMM kernel).  A ragged last round of big tiles
-  // costs a whole round: 4100x4096x4096 took 2.38 ms against 0.95 ms for 4096^3.
-  // A K that is no multiple of the 16-deep k-tile puts EVERY tile on the guarded (bounds-checked, scalar-load) path:
-  // 1000^3 ran at 25 TF.  Run the multiple-of-16 part unguarded and add the K tail (< 16) in a second, tiny launch
-  // (C = alpha A2.B2 + 1 C).  Only for linear epilogues; the summation order changes within the 1e-5 bar.
-  // a few hundred 64x64 tiles: the K loop split over the waves of each tile's workgroup (K tails included)
-  // one extent is 1: matVec / vecMat / an outer product beyond the small-GEMM kernel's range -- HBM-bound streaming kernels
-  if (gemv_form(p, true)) {
-    launch_gemv(p, S());
-    return;
-  }
-  {   // (development builds, TOPS_T32_FIRST=1: the four-wave 32x32-tile kernel ahead of the wave-split one, for A/B runs)
-    static const int t32_first = [] { const char* e = ab_getenv("TOPS_T32_FIRST"); return e ? atoi(e) : 0; }();
-    if (t32_first && gemm_t32_applicable(p)) {
-      launch_gemm_t32(p, S());
-      return;
-    }
-  }
-  // short K, B small enough to live in LDS, a long stream of rows (config 5): the barrier-free streaming kernel -- ahead of the
-  // wave-split kernel, whose rule for "more than 1,024 tiles the big tiles do not fit" would take these too (0.150 -> 0.217 ms)
-  if (gemm_skinnyk_applicable(p)) {
-    launch_gemm_skinnyk(p, S());
-    return;
-  }
-  if (gemm_skinnyk64_applicable(p)) {
-    launch_gemm_skinnyk64(p, S());
-    return;
-  }
-  // ... on the tile shape whose count fits the CUs: 48x48 / 48x64 / 64x48 / 80x80 where that beats the 64x64 routes (768^3: 256
-  // tiles of 48x48 instead of 144 of 64x64 split three ways)
-  if (gemm_kw16_applicable(p)) {
-    launch_gemm_kw16(p, S());
-    return;
-  }
-  if (gemm_kw_applicable(p)) {
-    launch_gemm_kw(p, S());
-    return;
-  }
-  if (gemm_kw64_applicable(p)) {
-    launch_gemm_kw64(p, S());
-    return;
-  }
-  if (p.K % 16 != 0 && p.K >= 128 && p.M * p.N >= 65536 && !p.reduce_batch && !p.rowsum && !p.loss_rows && p.act == 0 &&
-      !p.dact) {
-    const int64_t es = p.dtype == TO_F64 ? 8 : 4, K0 = p.K / 16 * 16;
-    GemmProblem head = p, tail = p;
-    head.K = K0;
-    head.bias = nullptr;  // the bias belongs to the launch that finishes the element
-    tail.K = p.K - K0;
-    tail.A = static_cast<const char*>(p.A) + K0 * p.a_sk * es;
-    tail.B = static_cast<const char*>(p.B) + K0 * p.b_sk * es;
-    tail.Cin = p.C;
-    tail.beta = 1.0;
-    run_gemm(head);
-    run_gemm(tail);
-    return;
-  }
-  const bool f64 = p.dtype == TO_F64;
-  auto full_rounds = [f64](const GemmProblem& q) { return f64 ? gemm_f64_w4_full_rounds(q) : gemm_w4_full_rounds(q); };
-  const int64_t TNW = f64 ? 128 : 256;  // tile width (fp64: 256 x 128 tiles)
-  if (!f64 && gemm_w4_edge_whole(p) && gemm_route(p) == ROUTE_MFMA) {  // ragged, but whole rounds of tiles with its edge tiles
-    launch_gemm_mfma(p, S());
-    return;
-  }
-  if (!p.reduce_batch && !p.rowsum && !p.loss_rows && p.M >= 256 && p.N >= 256 && !full_rounds(p)) {
-    const int64_t tm = p.M / 256, tn = p.N / TNW;
-    int64_t best = 0, bm = 0, bn = 0;
-    for (int64_t dm = 0; dm < 8 && dm < tm; ++dm)
-      for (int64_t dn = 0; dn < 8 && dn < tn; ++dn) {
-        const int64_t t = (tm - dm) * (tn - dn) * p.batch;
-        if (t > best && full_rounds(gemm_block(p, 0, (tm - dm) * 256, 0, (tn - dn) * TNW))) { best = t; bm = tm - dm; bn = tn - dn; }
-      }
-    // worth it when the block carries at least half of the work
-    if (best > 0 && 2 * bm * bn * 256 * TNW >= p.M * p.N) {
-      const GemmProblem main = gemm_block(p, 0, bm * 256, 0, bn * TNW);
-      if (full_rounds(main)) {
-        run_gemm(main);
-        if (bn * TNW < p.N) run_gemm(gemm_block(p, 0, p.M, bn * TNW, p.N - bn * TNW));       // right strip
-        if (bm * 256 < p.M) run_gemm(gemm_block(p, bm * 256, p.M - bm * 256, 0, bn * TNW));  // bottom strip
-        return;
-      }
-    }
-  }
-  // Mid sizes whose extents are no multiple of 4 (multiples of 4 run whole on the pinned 128-tile kernel, edge tiles
-  // included): the block of whole 128x128 tiles goes to that kernel, the two border strips their own way (slivers
-  // with a long K: the small-GEMM kernel).  Otherwise every tile is on the guarded scalar-load path.
-  if (!f64 && p.batch == 1 && !p.reduce_batch && !p.rowsum && !p.loss_rows && p.K % 16 == 0 && p.M >= 384 && p.N >= 384 &&
-      (p.M % 4 != 0 || p.N % 4 != 0) && p.beta == 0.0 && p.alpha == 1.0 && !p.bias && !p.dact && p.act == 0) {
-    const int64_t bm = p.M / 128, bn = p.N / 128;
-    if (bm * bn >= 16 && bm * bn <= 288 && 4 * bm * bn * 128 * 128 >= 3 * p.M * p.N) {
-      run_gemm(gemm_block(p, 0, bm * 128, 0, bn * 128));
-      if (bn * 128 < p.N) run_gemm(gemm_block(p, 0, p.M, bn * 128, p.N - bn * 128));          // right strip
-      if (bm * 128 < p.M) run_gemm(gemm_block(p, bm * 128, p.M - bm * 128, 0, bn * 128));     // bottom strip
-      return;
-    }
-  }
-  switch (gemm_route(p)) {
-    case ROUTE_SMALL: launch_gemm_small(p, S()); break;  // latency-bound shapes: in-workgroup split-K, no LDS staging
-    case ROUTE_MFMA: launch_gemm_mfma(p, S()); break;
-    case ROUTE_F64:
-      TO_CHECK(!p.bias && !p.act && !p.dact, TO_ERR_STATE, "internal: fused epilogue routed to the tiled fp64 kernel");
-      launch_gemm_f64(p, S());
-      break;
-    default: launch_gemm_naive(p, S()); break;
-  }
-}
-
 // a : ms++os, b : Reverse os ++ ns.  reduce: sum the result over the hidden batch.
 // The batch rule is a LOWERING (round 4): called on batched data the reference's `gmul (transp x) dtdz` (TOp.hs:86-88)
 // is one outer product PER SAMPLE, B*o*i numbers whose only use in a gradient is their sum over the batch.  In every

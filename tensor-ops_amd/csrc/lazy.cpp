@@ -1161,7 +1161,7 @@ struct Exec {
 
   void launch_one(const Gr& g, Launch& L) {
     describe_gemm(L.p);
-    if (g.mem.size() > 1 && gemm_small_route(L.p)) launch_gemm_small(L.p, S());
+    if (g.mem.size() > 1) run_gemm_small_first(L.p);
     else run_gemm(L.p);
   }
 

@@ -1,5 +1,6 @@
 // Host-side op implementations shared by the eager entry points (api.cpp, stack_ff.cpp, stack_rnn.cpp) and the deferred
-// executor (lazy.cpp).  Everything here takes MATERIALISED handles (ptr != nullptr).
+// executor (lazy.cpp).  Everything here takes MATERIALISED handles (ptr != nullptr).  (Where a contraction goes -- run_gemm,
+// gemm_epilogue_ok, gemm_small_route -- is gemm_route.hpp, included below.)
 #pragma once
 #include <map>
 #include <unordered_map>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "gemm_route.hpp"   // run_gemm and the routing predicates
 
 namespace to {
 
@@ -23,13 +25,6 @@ uint64_t fresh_id();
 hipStream_t S();
 void require_init();
 void no_capture(const char* what);
-
-// ---- GEMM routing ----------------------------------------------------------------------------------
-void run_gemm(const GemmProblem& p);
-// would run_gemm honour alpha/beta/Cin/bias/act/dact of this problem (every kernel it may pick carries them)?
-bool gemm_epilogue_ok(const GemmProblem& p);
-// is the problem in the range of the small-GEMM kernel, the only one with rowsum / loss head / tail epilogues?
-bool gemm_small_route(const GemmProblem& p);
 
 // ---- gmul planning -----------------------------------------------------------------------------------
 // `gmul lM lO lN a b` as ONE GemmProblem.  dry = true: shapes only -- validates, derives

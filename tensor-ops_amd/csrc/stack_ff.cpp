@@ -456,22 +456,6 @@ static void ae_no_alias(std::initializer_list<to_tensor> outs, to_tensor in, int
     TO_CHECK(!bad, TO_ERR_ARG, F + "an output overlaps the input, another output or a parameter");
   }
 }
-// C[B, n_l] = act(A W_l^T + b_l) the way to_fflayer_stack_infer's hidden layers go: one GEMM with the epilogue where the
-// kernel carries one, else the plain product and one elementwise launch
-static void ae_layer(int dt, to_tensor W, to_tensor bias, int act_kind, const void* A, int64_t a_sm, void* C, int64_t B) {
-  GemmProblem p = row_gemm(dt, A, a_sm, 1, W->ptr, 1, W->dims[1], C, B, W->dims[0], W->dims[1]);
-  p.bias = bias->ptr;
-  p.act = act_kind + 1;
-  if (gemm_epilogue_ok(p)) {
-    if (gemm_small_route(p)) launch_gemm_small(p, S());
-    else run_gemm(p);
-    return;
-  }
-  p.bias = nullptr;
-  p.act = 0;
-  run_gemm(p);
-  launch_bias_act_rows(dt, C, bias->ptr, B, W->dims[0], act_kind, S());
-}
 // layers l0 .. l1-1, each with its activation; the last one into `last_out` (null: scratch).  Returns where the last one is.
 static const void* ae_layers(int dt, const to_tensor* w, const to_tensor* b, const int* acts, int l0, int l1, const void* prev,
                              int64_t prev_sm, int64_t B, void* last_out, std::deque<Holder>& keep) {
@@ -482,7 +466,7 @@ static const void* ae_layers(int dt, const to_tensor* w, const to_tensor* b, con
       keep.emplace_back(new_tensor(1, &n, B, dt));
       C = keep.back().t->ptr;
     }
-    ae_layer(dt, w[l], b[l], acts[l], prev, prev_sm, C, B);
+    stack_layer_forward(dt, w[l], b[l], acts[l], prev, prev_sm, C, B);
     prev = C;
     prev_sm = n;
   }
@@ -736,18 +720,7 @@ static void fflayer_stack_infer_impl(int n_layers, const to_tensor* w, const to_
   for (int l = 0; l + 1 < n_layers; ++l) {
     const int64_t n = w[l]->dims[0];
     act[l].t = new_tensor(1, &n, B, dt);
-    GemmProblem p = layer(prev, prev_sm, w[l], act[l].t->ptr);
-    p.bias = b[l]->ptr;
-    p.act = hk + 1;
-    if (gemm_epilogue_ok(p)) {
-      if (gemm_small_route(p)) launch_gemm_small(p, S());
-      else run_gemm(p);
-    } else {  // (the tiled fp64 kernel: alpha / beta only)
-      p.bias = nullptr;
-      p.act = 0;
-      run_gemm(p);
-      launch_bias_act_rows(dt, act[l].t->ptr, b[l]->ptr, B, n, hk, S());
-    }
+    stack_layer_forward(dt, w[l], b[l], hk, prev, prev_sm, act[l].t->ptr, B);
     prev = act[l].t->ptr;
     prev_sm = n;
   }

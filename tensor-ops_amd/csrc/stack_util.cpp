@@ -62,11 +62,7 @@ GemmProblem row_gemm(int dt, const void* A, int64_t a_sm, int64_t a_sk, const vo
 }
 
 void gemm_with_epilogue(GemmProblem p) {
-  if (gemm_epilogue_ok(p)) {
-    if (gemm_small_route(p)) launch_gemm_small(p, S());
-    else run_gemm(p);
-    return;
-  }
+  if (gemm_epilogue_ok(p)) return run_gemm_small_first(p);
   const int act = p.act, dact_kind = p.dact_kind;
   const void* dact = p.dact;
   if (p.bias) {  // C = bias rows, then C += A B
@@ -80,6 +76,17 @@ void gemm_with_epilogue(GemmProblem p) {
   run_gemm(p);
   if (act) ew2(p.dtype, act == 2 ? EW_TANH : EW_LOGISTIC, p.C, p.C, nullptr, p.M * p.N);
   else if (dact) ew2(p.dtype, dact_kind ? EW_MUL_1MH2 : EW_MUL_H1MH, p.C, p.C, dact, p.M * p.N);
+}
+
+void stack_layer_forward(int dt, to_tensor W, to_tensor bias, int act_kind, const void* A, int64_t a_sm, void* C, int64_t B) {
+  GemmProblem p = row_gemm(dt, A, a_sm, 1, W->ptr, 1, W->dims[1], C, B, W->dims[0], W->dims[1]);
+  p.bias = bias->ptr;
+  p.act = act_kind + 1;
+  if (gemm_epilogue_ok(p)) return run_gemm_small_first(p);
+  p.bias = nullptr;   // (the tiled fp64 kernel: alpha / beta only)
+  p.act = 0;
+  run_gemm(p);
+  launch_bias_act_rows(dt, C, bias->ptr, B, W->dims[0], act_kind, S());
 }
 
 void run_online_sgd(int dt, int n_layers, const int64_t* dims, void* const* W, void* const* b, to_tensor X, to_tensor Y,

@@ -1,5 +1,6 @@
 // What the one-call stack entries (stack_ff.cpp, stack_rnn.cpp) and to_graph_online_sgd (api.cpp) share.  Every entry runs
-// in the same order: validate, ensure the operands, claim the destinations, launch.
+// in the same order: validate, ensure the operands, claim the destinations, launch.  (gemm_small_takes, which they ask before a
+// step's launches, lives with the other routing predicates in gemm_route.hpp.)
 #pragma once
 #include "ops.hpp"
 
@@ -29,19 +30,15 @@ inline to_tensor unit_stride_rows(to_tensor t, Holder& h) {
 // out[i] = kind(x0[i]) or kind(x0[i], x1[i]) (EwKind; x1 null: one input), i < n
 void ew2(int dt, int kind, void* out, const void* x0, const void* x1, int64_t n);
 
-// Does the small-GEMM kernel -- the only one with every fused epilogue for both element types -- take this one problem?
-// (Every caller has batch == 1.  There `gemm_small_applicable(p) ||` in front of this changes nothing: applicable is can,
-//  the same tile bound and M * N >= 256 on top, so it implies this.)
-inline bool gemm_small_takes(const GemmProblem& p) {
-  const int64_t t64 = ((p.M + 63) / 64) * ((p.N + 63) / 64);
-  return gemm_small_can(p) && t64 < 200;
-}
 // C[M, N] (contiguous) = A[M, K] (rows a_sm apart) . Bop where Bop(k, n) = B[k * b_sk + n * b_sn]
 GemmProblem row_gemm(int dt, const void* A, int64_t a_sm, int64_t a_sk, const void* B, int64_t b_sk, int64_t b_sn, void* C,
                      int64_t M, int64_t N, int64_t K);
 // C = A . B(op) with the epilogue of p (bias, act = logistic / tanh, dact = h (1 - h) / 1 - h h by dact_kind, beta * Cin); a
 // kernel without one gets the plain product and the epilogue as separate launches.  C is contiguous [M, N].
 void gemm_with_epilogue(GemmProblem p);
+// C[B, n] = act(A W^T + b), one layer of a stack over B rows (act_kind: ACT_KIND_*): one GEMM with the epilogue where the
+// kernel carries one, else the plain product and one elementwise launch
+void stack_layer_forward(int dt, to_tensor W, to_tensor bias, int act_kind, const void* A, int64_t a_sm, void* C, int64_t B);
 
 // The persistent online-SGD kernel over n_idx > 0 samples of X / Y (idx_host null: rows 0 .. n_idx-1), then a stream
 // synchronise; throws TO_ERR_HIP when its watchdog aborted the run (the parameters are then unchanged).

@@ -733,6 +733,21 @@ class HipT:
         check(lib().to_stats(C.byref(a), C.byref(b), C.byref(c)))
         return {"live_handles": a.value, "pool_bytes": b.value, "launches": c.value}
 
+    def gemm_route(self, m, k, n, dtype="f32", batch=1, reduce_batch=False, a_transposed=False, b_transposed=False,
+                   epilogue=()):
+        """Debug (to_gemm_route_query): where the contraction [m, k] . [k, n] would go, launching nothing.  `epilogue`: names
+        out of bias / act / dact / beta / rowsum.  "families": the kernel family of each launch, in order (None: the library
+        would refuse the problem)."""
+        cap = 64
+        fam = (C.c_int * cap)()
+        nl, ok, small, ws = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        bits = sum(capi.GEMM_EPILOGUE_BITS[e] for e in epilogue)
+        check(lib().to_gemm_route_query(capi.TO_F64 if dtype in ("f64", capi.TO_F64) else capi.TO_F32, m, n, k,
+                                        batch, int(reduce_batch), int(a_transposed), int(b_transposed), bits, cap, fam,
+                                        C.byref(nl), C.byref(ok), C.byref(small), C.byref(ws)))
+        return {"families": None if nl.value < 0 else [capi.GEMM_FAMILIES[fam[i]] for i in range(nl.value)],
+                "epilogue_ok": bool(ok.value), "small_route": bool(small.value), "split_workspace": bool(ws.value)}
+
     def transfer_stats(self):
         v = [C.c_int64() for _ in range(4)]
         check(lib().to_transfer_stats(*[C.byref(x) for x in v]))

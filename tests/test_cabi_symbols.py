@@ -56,6 +56,18 @@ def test_no_cpu_fallback(built):
         assert L.to_alloc(0, 1, d, 0, C.byref(t)) != 0  # not initialised -> loud error
 
 
+def test_route_query_refuses_before_init(built):
+    """The debug query of the routing decision reads state to_init sets (the placement probe): TO_ERR_STATE without it, and
+    its outputs untouched.  In a process of its own, which has not initialised the library whatever this one has done."""
+    import sys
+    code = ("import ctypes as C; from tensor_ops_amd import capi; L = capi.lib(); fam = (C.c_int * 4)(); "
+            "out = [C.c_int(-7) for _ in range(4)]; "
+            "st = L.to_gemm_route_query(0, 64, 64, 64, 1, 0, 0, 0, 0, 4, fam, *[C.byref(o) for o in out]); "
+            "print(st, [o.value for o in out], L.to_last_error().decode())")
+    got = subprocess.check_output([sys.executable, "-c", code], cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert got.decode().startswith("4 [-7, -7, -7, -7] ") and "to_init" in got.decode(), got   # 4: TO_ERR_STATE
+
+
 def test_kernels_are_gfx950(built):
     """The shared object carries gfx950 code objects only (no other arch, no generic fallback)."""
     blob = open(built, "rb").read()

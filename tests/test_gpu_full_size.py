@@ -20,6 +20,17 @@ def T():
     return HipT(0)
 
 
+# Shapes of the gemm_kwave.hip tests below that gemm_kw16.hip's tile menu has taken since those tests were written (its fitted
+# cost beats the 64x64 routes' there; DESIGN.md 3.1 lists 1088^3, 1100^3 and 768 x 4096 x 768 in its row): recorded from the
+# routing cascade before it became gemm_plan (tests/golden/gemm_routes.txt).  Every case pins exactly one family.
+TILE_MENU_TOOK = {(1088, 1088, 1088), (1100, 1100, 1100), (768, 784, 768), (768, 790, 772), (1024, 1024, 512), (704, 704, 704),
+                  (768, 4096, 768)}
+
+
+def route(T, m, k, n, ta=0, tb=0):
+    return T.gemm_route(m, k, n, a_transposed=ta, b_transposed=tb)["families"]
+
+
 def rel_err(got, want):
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
     return np.linalg.norm((got - want).ravel()) / np.linalg.norm(want.ravel())
@@ -32,6 +43,7 @@ def test_c2_gmul_4096(T):
     a = rng.uniform(-1, 1, size=(n, n)).astype(np.float32)
     b = rng.uniform(-1, 1, size=(n, n)).astype(np.float32)
     da, db = T.put(a), T.put(b)
+    assert route(T, n, n, n) == ["mfma"]
     c = T.gmul(1, 1, 1, da, db).numpy()
     rows = rng.choice(n, size=48, replace=False)
     want = a[rows].astype(np.float64) @ b.astype(np.float64)
@@ -97,7 +109,11 @@ def test_few_tiles_several_workgroups_per_tile_bit_exact_on_integers(T, ta, tb, 
     768 x 784 x 768 and 768 x 790 x 772 three ways (the second with a K tail of 6 and a ragged last tile column),
     500 x 2056 x 520 three ways with ragged tiles both ways and a K tail of 8, 512 x 2048 x 512 four ways, 384 x 4096 x 384
     six ways, 256 x 4100 x 256 eight ways, 132 x 3000 x 1028 (three tile rows, the last of four rows), 1024 x 1024 x 512 and
-    704^3 two ways, 768 x 4096 x 768 three ways with two workgroups per CU.  Whole output, exact on small integers."""
+    704^3 two ways, 768 x 4096 x 768 three ways with two workgroups per CU.  Whole output, exact on small integers.
+    (768 x 784 x 768, 768 x 790 x 772, 1024 x 1024 x 512, 704^3 and 768 x 4096 x 768 NO LONGER REACH the KS-way split: gemm_kw16.hip's
+    tile menu takes them, TILE_MENU_TOOK, and what is said above about them describes a kernel they do not run on.  The route
+    asserted is the one taken; the KS-way split is held by the other five shapes: KS = 3, 4, 6, 8 and the three tile rows.)"""
+    assert route(T, m, k, n, ta, tb) == ["kw16" if (m, k, n) in TILE_MENU_TOOK else "kw"]
     rng = np.random.default_rng(SEED + 77 + 2 * ta + tb)
     a = rng.integers(-2, 3, size=(m, k)).astype(np.float32)
     b = rng.integers(-2, 3, size=(k, n)).astype(np.float32)
@@ -121,9 +137,12 @@ def test_more_tiles_than_cus_stream_k_bit_exact_on_integers(T, ta, tb, m, k, n):
     contributor to arrive.  1088^3 (289 tiles), 1152 x 2048 x 1152 (324 tiles, a share is 81 of a tile's 128 k-tiles),
     1150 x 2056 x 1156 (ragged tiles both ways, a K tail of 8: added by the run that ends a tile), 1472 x 1482 x 1470 (529
     tiles, K tail of 10, ragged), 1792 x 1800 x 1792 (784 tiles), 1100^3.  Whole output, exact on small integers, three
-    launches each (the counters must be back at zero for the next one)."""
+    launches each (the counters must be back at zero for the next one).  (1088^3 and 1100^3 NO LONGER REACH stream-K: gemm_kw16.hip's
+    64x80 tiles take them, TILE_MENU_TOOK, and what is said above about them describes a kernel they do not run on.  The route
+    asserted is the one taken; stream-K is held by the other four shapes.)"""
     if (ta and m % 4) or (not tb and n % 4):
         pytest.skip("an m- / n-contiguous operand needs whole quads")
+    assert route(T, m, k, n, ta, tb) == ["kw16" if (m, k, n) in TILE_MENU_TOOK else "kw"]
     rng = np.random.default_rng(SEED + 177 + 2 * ta + tb)
     a = rng.integers(-2, 3, size=(m, k)).astype(np.float32)
     b = rng.integers(-2, 3, size=(k, n)).astype(np.float32)
@@ -151,6 +170,7 @@ def test_tile_menu_of_16x16_blocks_bit_exact_on_integers(T, ta, tb, m, k, n):
     exact on small integers, three launches each, all four operand layouts."""
     if (ta and m % 4) or (not tb and n % 4):
         pytest.skip("an m- / n-contiguous operand needs whole quads")
+    assert route(T, m, k, n, ta, tb) == ["kw16"]
     rng = np.random.default_rng(SEED + 277 + 2 * ta + tb)
     a = rng.integers(-2, 3, size=(m, k)).astype(np.float32)
     b = rng.integers(-2, 3, size=(k, n)).astype(np.float32)
@@ -174,6 +194,7 @@ def test_more_than_1024_tiles_the_big_tiles_do_not_fit_bit_exact_on_integers(T, 
     workgroup (5120 x K x 5120 = 25 rounds of 256 exactly).  Whole output, exact on small integers, one launch, all four layouts."""
     if (ta and m % 4) or (not tb and n % 4):
         pytest.skip("an m- / n-contiguous operand needs whole quads")
+    assert route(T, m, k, n, ta, tb) == ["kw"]
     rng = np.random.default_rng(SEED + 377 + 2 * ta + tb)
     a = rng.integers(-2, 3, size=(m, k)).astype(np.float32)
     b = rng.integers(-2, 3, size=(k, n)).astype(np.float32)
@@ -203,7 +224,8 @@ def test_full_tile_kernel_with_a_hidden_batch(T, batched_b):
 def test_c5_stays_on_the_streaming_kernel(T):
     """A route guard with a clock on it: config 5a ('[512,512,64] x '[64,512]) takes 0.15 ms on gemm_skinnyk3_kernel and 0.22 ms on
     the wave-split kernel, whose widened rules (round 6, last) would accept it -- run_gemm asks the streaming kernel first.  The
-    bound is loose (0.19 ms) and taken as the best of three timed batches."""
+    bound is loose (0.19 ms) and taken as the best of three timed batches.  The route itself is asserted first."""
+    assert route(T, 512 * 512, 64, 512) == ["skinnyk"]
     a = T.genRand((512, 512, 64), "uniform", -1.0, 1.0, SEED + 91)
     b = T.genRand((64, 512), "uniform", -1.0, 1.0, SEED + 92)
     for _ in range(100):

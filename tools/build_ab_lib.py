@@ -7,8 +7,8 @@
 (TOPS_HIP_LIB is what the ctypes layer loads; LD_LIBRARY_PATH makes the host mirror, which names libtensorops_hip.so as a
 dependency, resolve to the same file -- its RUNPATH is searched after LD_LIBRARY_PATH.)
 
-(api.cpp and stack_ff.cpp are always among the recompiled files, so that to_build_info reports a development build and the
-step's own knobs, TOPS_STEP_FUSE_TAIL and TOPS_STEP_RANK1, are read.)  The product library is not touched.  Measurement tooling."""
+(api.cpp, gemm_route.cpp and stack_ff.cpp are always among the recompiled files, so that to_build_info reports a development
+build and the routing knob TOPS_T32_FIRST and the step's own knobs, TOPS_STEP_FUSE_TAIL and TOPS_STEP_RANK1, are read.)  The product library is not touched.  Measurement tooling."""
 import importlib.util
 import os
 import subprocess
@@ -21,7 +21,7 @@ spec.loader.exec_module(B)
 
 
 def main():
-    files = sorted(set(sys.argv[1:]) | {"api.cpp", "stack_ff.cpp"})
+    files = sorted(set(sys.argv[1:]) | {"api.cpp", "gemm_route.cpp", "stack_ff.cpp"})
     for f in files:
         assert f in B.SOURCES, f
     B.build()   # the product objects

@@ -19,24 +19,32 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <class S>
 struct SmallArgsT {
+  // ---- the hot block: what stands in front of the first operand load -- the leading 64 bytes, and the strides behind
+  // them.  The step's kernels pin it (small_pin_hot) so that it is requested at the kernel's entry in one batch of scalar
+  // loads and waited for ONCE; everything further down is waited for where it is first used.
   const S* A;
   const S* B;
-  S* C;
-  const S* Cin;
-  int M, N, K;
-  long a_sm, a_sk, b_sk, b_sn, c_sm;
-  long a_sb, b_sb, c_sb;
-  int a_vec, b_vec;  // 16-byte loads along k legal (k-contiguous modes only)
   unsigned a_bytes, b_bytes;  // extents for the buffer descriptors (hardware bounds check)
-  int tiles_n;
-  int tiles_m;       // (tile grid; with tile_order != 0 the workgroup -> tile map below is XCD-aware)
+  int M, N, K;
+  int kper;          // k extent per wave (multiple of the chunk)
   int tile_order;    // 0: bid row-major.  1 / 2: XCD x (= bid % 8, where the hardware puts the workgroup) owns a
                      // contiguous run of the row-major (1) / column-major (2) tile sequence, so its private L2
                      // pulls a few A panels + all of B (1) or a few B panels + all of A (2) instead of everything
-  int kper;          // k extent per wave (multiple of the chunk)
-  S alpha, beta;
+  unsigned map_d, map_mag, map_q, map_r;   // tile_of's constants, planned on the host (small_plan_map) from the tile grid and the order
+  int tiles_n;       // (the sixteenth dword, pinned with the rest: a dword of the block that nobody holds on to is a register the
+                     //  compiler may write ahead of the wait, which then has to come early)
+  int a_sm, a_sk, b_sk, b_sn;   // element strides, low 32 bits: they only ever enter 32-bit byte offsets (gemm_small_can: an
+  int a_sb, b_sb;               // operand spans < 2 GiB), and the low 32 bits of a sum of products need only the factors' low 32 bits
+  // ---- the epilogue's operands (the weight-gradient pair's 32x32 body asks for them ahead of its operands) ----
+  S* C;
+  const S* Cin;
   const S* bias;
   const S* dact;
+  long c_sm, c_sb;
+  // ---- cold ----
+  int a_vec, b_vec;  // 16-byte loads along k legal (k-contiguous modes only)
+  int tiles_m;       // (tile grid, with tiles_n above; with tile_order != 0 the workgroup -> tile map is XCD-aware)
+  S alpha, beta;
   int act;
   int dact_kind;
   S* rowsum;  // optional [batch][M]: sum_k A[m,k] (the bias gradient next to dW = dZ^T.X)
@@ -55,9 +63,35 @@ struct SmallArgsT {
 #endif
 };
 
+// Every member of the hot block as an input of an empty asm statement at the kernel's entry: their scalar loads go out
+// together ahead of it and one s_waitcnt covers them.  Left alone, the compiler requests a member where it is first used --
+// the tile grid first, the pointers and strides behind tile_of's arithmetic, a serial round trip each time.  EPI: the
+// epilogue's operands too (a body whose first vector loads are the epilogue prefetches).
+template <bool EPI, class S>
+__device__ __forceinline__ void small_pin_hot(const SmallArgsT<S>& g) {
+  if constexpr (EPI) {
+    // what stands in front of the epilogue prefetches: the tile map, the extents, the epilogue's operands.  (The operands'
+    // own members are asked for right behind the branch on n1, under the tile map's arithmetic and the prefetches: pinning
+    // them here as well holds some forty scalar registers across a body that has none to spare.)
+    asm volatile("" ::"s"(g.M), "s"(g.N), "s"(g.tile_order), "s"(g.map_d), "s"(g.map_mag), "s"(g.map_q), "s"(g.map_r), "s"(g.Cin), "s"(g.bias),
+                 "s"(g.dact), "s"(g.c_sm));
+  } else {
+    asm volatile("" ::"s"(g.A), "s"(g.B), "s"(g.a_bytes), "s"(g.b_bytes), "s"(g.M), "s"(g.N), "s"(g.K), "s"(g.kper), "s"(g.tile_order),
+                 "s"(g.map_d), "s"(g.map_mag), "s"(g.map_q), "s"(g.map_r), "s"(g.tiles_n), "s"(g.a_sm), "s"(g.a_sk), "s"(g.b_sk), "s"(g.b_sn));
+  }
+}
+
 #ifdef TOPS_AB_KNOBS
+// (who stamps is worked out at the stamp, not at the entry: `dbg` is a cold member.  Slot 0, the entry, is the clock read by
+//  the body's first instruction; it is stored with the first stamp behind the operand loads -- SM_STAMP_ENTRY -- so that
+//  nothing in front of the first load waits for the clock or for `dbg`)
+#define SM_STAMP_ON stamp_on
 #define SM_STAMP(i) do { if (stamp_on) g.dbg[i] = wall_clock64(); } while (0)
+#define SM_STAMP_ENTRY() do { stamp_on = g.dbg && bid == 0 && tid == 0; if (stamp_on) g.dbg[0] = t_entry; } while (0)
+#define SM_ENTRY_CLOCK() wall_clock64()
 #else
+#define SM_STAMP_ENTRY() do { } while (0)
+#define SM_ENTRY_CLOCK() 0ll
 #define SM_STAMP(i) do { } while (0)
 #endif
 
@@ -65,19 +99,16 @@ struct SmallArgsT {
 // workgroup -> tile.  The 8 XCDs each have their own L2 and workgroup b lands on XCD b % 8: with the plain
 // row-major map every XCD touches every panel of both operands and the fabric carries 8 copies of them
 // (config 3 forward, 1024x784x256: 26.6 MB fetched for 4 MB of operands, rocprofv3 FETCH_SIZE).
+// No division and no branch: the run's start is x q + min(x, r) (q = T / 8, r = T % 8: bijective for any T), and the
+// quotient by the grid's extent is a multiply-high by the reciprocal the host planned (small_plan_map: exact below 2^16).
 template <class G>
 __device__ __forceinline__ void tile_of(const G& g, int bid, int& tile_m, int& tile_n) {
-  if (g.tile_order) {
-    const int T = g.tiles_m * g.tiles_n, x = bid & 7, q = T >> 3, r = T & 7;
-    bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);   // bijective for any T
-  }
-  if (g.tile_order == 2) {
-    tile_n = bid / g.tiles_m;
-    tile_m = bid - tile_n * g.tiles_m;
-  } else {
-    tile_m = bid / g.tiles_n;
-    tile_n = bid - tile_m * g.tiles_n;
-  }
+  const unsigned x = (unsigned)bid & 7u;
+  const unsigned run = x * g.map_q + (x < g.map_r ? x : g.map_r) + ((unsigned)bid >> 3);
+  const unsigned t = g.tile_order ? run : (unsigned)bid;
+  const unsigned hi = g.map_d == 1u ? t : __umulhi(t, g.map_mag), lo = t - hi * g.map_d;   // t / d, t % d
+  tile_m = (int)(g.tile_order == 2 ? lo : hi);
+  tile_n = (int)(g.tile_order == 2 ? hi : lo);
 }
 
 __device__ __forceinline__ float tanh_s(float x) { return tanhf(x); }
@@ -134,9 +165,23 @@ __device__ __forceinline__ double xor16(double x) { return __shfl_xor(x, OFF, 64
 //      development build (SM_STAMP) generates the same load / MFMA order as the product (tests/test_step_schedule.py).
 // STAG: the four waves of a SIMD (w, w + 4, w + 8, w + 12) issue their loads at falling priority, so the CU's one
 //      vector-memory path completes whole waves in turn instead of a sixteenth of everybody's.
-template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0, bool EXT = false, int PARTS = 0, bool STAG = false, int TAILK = 0>   // ONESHOT: 0, or the chunks one batch holds; TAILK: GemmProblem::tail_kind
+// HEAD (the loss-head kernels: fp32, 16x16, the compiler-ordered one-shot): the operand batch leaves FIRST, the fused tail's
+//      sixteen operands right behind it as branch-free bounds-checked buffer loads (a lane outside the tail's extents, or a
+//      launch without a tail, reads zeros), then the epilogue prefetch; the MFMAs run whether or not the wave has a K slice (a
+//      wave without one loaded zeros: 0 + 0 x 0, the same bits) -- so nothing but the K loop's MFMAs and the accumulator's
+//      LDS write lies between the loads and the reduction barrier.  Every other body: the epilogue prefetch first, the
+//      tail's loads behind the MFMAs, as before.
+template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0, bool EXT = false, int PARTS = 0, bool STAG = false, int TAILK = 0, bool HEAD = false, bool KMASK = false>   // ONESHOT: 0, or the chunks one batch holds; TAILK: GemmProblem::tail_kind
 __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const int bid, const long bz, S* ext_lds = nullptr,
-                                                const int tid_in = -1) {
+                                                const int tid_in = -1, const long long t_entry_in = 0, const bool have_entry = false) {
+#ifdef TOPS_AB_KNOBS
+  // the clock at the kernel's first instruction (a kernel that pins its hot block reads it ahead of the pin and hands it in;
+  // elsewhere: the body's first instruction)
+  long long t_entry = have_entry ? t_entry_in : wall_clock64();
+  if (have_entry) asm volatile("" : "+v"(t_entry));   // (kept in a vector register pair: the bodies have no scalar registers to spare)
+  bool stamp_on = false;   // (set by SM_STAMP_ENTRY, the first stamp of every path)
+#endif
+  static_assert(!HEAD || (sizeof(S) == 4 && TS == 16 && ONESHOT && PARTS == 0), "HEAD: the fp32 16x16 one-shot in the compiler's order");
   constexpr int ES = (int)sizeof(S);
   static_assert(ES == 4 || TS == 16, "the fp64 matrix instruction is 16x16x4");
   constexpr int KG = (TS == 32) ? 2 : 4;      // k-groups per MFMA
@@ -160,10 +205,6 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
   }
   const int tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & (TS - 1), half = lane / TS;   // half = k-group of this lane
-#ifdef TOPS_AB_KNOBS
-  const bool stamp_on = g.dbg && bid == 0 && tid == 0;
-#endif
-  SM_STAMP(0);
   int tile_m, tile_n;
   tile_of(g, bid, tile_m, tile_n);
   const long m = (long)tile_m * TS + l31, n = (long)tile_n * TS + l31;
@@ -191,8 +232,8 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
       const_cast<S*>(g.A), 0, g.a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<S*>(g.B), 0, g.b_bytes, 0x00020000);
-  const int a_base = (int)((bz * g.a_sb + (mv ? m : 0) * g.a_sm) * ES);
-  const int b_base = (int)((bz * g.b_sb + (nv ? n : 0) * g.b_sn) * ES);
+  const int a_base = (int)(((unsigned)bz * (unsigned)g.a_sb + (unsigned)(mv ? m : 0) * (unsigned)g.a_sm) * (unsigned)ES);
+  const int b_base = (int)(((unsigned)bz * (unsigned)g.b_sb + (unsigned)(nv ? n : 0) * (unsigned)g.b_sn) * (unsigned)ES);
   const int a_sk4 = (int)g.a_sk * ES, b_sk4 = (int)g.b_sk * ES;
   // arithmetic select (no short-circuit &&, no ?:) so that no control flow is generated
   auto sel = [](bool ok, int off) { const int msk = -(int)ok; return (off & msk) | (0x7fffffff & ~msk); };
@@ -219,6 +260,22 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
       d[2] = __hiloint2double((int)w.y, (int)w.x); d[3] = __hiloint2double((int)w.w, (int)w.z);
     }
   };
+  // KMASK (the weight-gradient pair's second body only; every other instance keeps `sel`): the same select for the element
+  // loads of a compiler-ordered stage, from integers alone -- the sign of kend - 1 - k, or-ed with an all-ones word for a row /
+  // column beyond the extent.  As comparisons, the 32 `k < kend` of that body's one-shot stage of 64 element loads are hoisted
+  // ahead of the loads, a scalar register pair each, and the pair kernel -- at the scalar register limit already -- spills
+  // them (tests/test_step_schedule.py: no form of the pair may); the empty asm keeps the compiler from turning the sign word
+  // back into a comparison.  Same offsets, same loads.
+  auto selk = [&](bool in, int k, int off) {
+    if constexpr (KMASK) {
+      int msk = (kend - 1 - k) >> 31;
+      asm("" : "+v"(msk));
+      msk |= -(int)!in;
+      return (off & ~msk) | (0x7fffffff & msk);
+    } else {
+      return sel(in & (k < kend), off);
+    }
+  };
   auto load_stage = [&](S (&a)[ST][4], S (&b)[ST][4], int k0) {
 #pragma unroll
     for (int c = 0; c < ST; ++c) {
@@ -227,13 +284,13 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
         ld4(ra, mv & (kb < kend), a_base + kb * ES, a[c]);
       } else {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) a[c][j] = ld1(ra, sel(mv & (kb + j < kend), a_base + (kb + j) * a_sk4));
+        for (int j = 0; j < 4; ++j) a[c][j] = ld1(ra, selk(mv, kb + j, a_base + (kb + j) * a_sk4));
       }
       if (BMODE == 1 && g.b_vec) {
         ld4(rb, nv & (kb < kend), b_base + kb * ES, b[c]);
       } else {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) b[c][j] = ld1(rb, sel(nv & (kb + j < kend), b_base + (kb + j) * b_sk4));
+        for (int j = 0; j < 4; ++j) b[c][j] = ld1(rb, selk(nv, kb + j, b_base + (kb + j) * b_sk4));
       }
     }
   };
@@ -301,7 +358,7 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
   const S* Ci = g.Cin ? g.Cin + bz * g.c_sb : nullptr;
   const S* Hd = g.dact ? g.dact + bz * g.c_sb : nullptr;
   S pf_ci[NRW], pf_hd[NRW], pf_bias = S(0);
-  {
+  auto prefetch_epilogue = [&] {
     const long col = (long)tile_n * TS + l31;
     if (g.bias && col < g.N) pf_bias = g.bias[col];
 #pragma unroll
@@ -313,15 +370,51 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
       pf_ci[i] = (Ci && ok) ? Ci[row * g.c_sm + col] : S(0);
       pf_hd[i] = (Hd && ok) ? Hd[row * g.c_sm + col] : S(0);
     }
-  }
+  };
+  if constexpr (!HEAD) prefetch_epilogue();
   constexpr int SK = CK * ST;
-  SM_STAMP(1);   // (set-up done, the epilogue's operands asked for)
+  if constexpr (!HEAD) {
+    SM_STAMP_ENTRY();
+    SM_STAMP(1);   // (set-up done, the epilogue's operands asked for)
+  }
+  S tl_bw[2][4], tl_hv[2][4];   // operands of the fused tail (GemmProblem::tail_*)
   if constexpr (ONESHOT) {
-    if constexpr (PARTS == 0) {
+    if constexpr (HEAD) {
+      load_stage(a0, b0, kbeg);   // (kper <= SK; a wave whose slice is empty -- kbeg >= kend -- has every lane masked)
+      __builtin_amdgcn_sched_barrier(0);   // (the tail's members are cold: nothing of theirs in front of the operand loads)
+      {
+        const bool tl = g.loss_rows && g.tail_out;
+        const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<S*>(g.tail_w), 0, tl ? g.N * g.tail_n * ES : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(const_cast<S*>(g.tail_h), 0, tl ? g.M * g.tail_n * ES : 0, 0x00020000);
+        const int kg = half, ntiles = (g.tail_n + 15) >> 4;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int t = wave + u * NW, col = t * 16 + l31;
+          const bool cv = (t < ntiles) & (col < g.tail_n);
+#pragma unroll
+          for (int st = 0; st < 4; ++st) {
+            const int k = 4 * st + kg;
+            tl_bw[u][st] = ld1(rw, sel(cv & (k < g.N), (k * g.tail_n + col) * ES));
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = tile_m * 16 + row16(kg, r);
+            tl_hv[u][r] = ld1(rh, sel(cv & (row < g.M), (row * g.tail_n + col) * ES));
+          }
+        }
+      }
+      prefetch_epilogue();
+      __builtin_amdgcn_sched_barrier(0);   // every load of this body is out; from here to the barrier: MFMAs and LDS writes
+      SM_STAMP_ENTRY();
+#ifdef TOPS_AB_KNOBS
+      if (SM_STAMP_ON) { SM_STAMP(2); __builtin_amdgcn_s_waitcnt(0x0F70); SM_STAMP(3); }   // (the loads issued; all of them landed -- stamped wave only)
+#endif
+      mma_stage(a0, b0);
+    } else if constexpr (PARTS == 0) {
       if (kbeg < kend) {  // kper <= SK by construction (launch_gemm_small)
         load_stage(a0, b0, kbeg);
 #ifdef TOPS_AB_KNOBS
-        if (stamp_on) { SM_STAMP(2); __builtin_amdgcn_s_waitcnt(0x0F70); SM_STAMP(3); }   // (the batch issued; all of it landed -- stamped wave only)
+        if (SM_STAMP_ON) { SM_STAMP(2); __builtin_amdgcn_s_waitcnt(0x0F70); SM_STAMP(3); }   // (the batch issued; all of it landed -- stamped wave only)
 #endif
         mma_stage(a0, b0);
       }
@@ -373,8 +466,7 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
 
   // operands of the fused tail (GemmProblem::tail_*): independent of this kernel's own result, so their
   // loads are issued now and land during the reduction and the loss head
-  S tl_bw[2][4], tl_hv[2][4];
-  if constexpr (TS == 16) {
+  if constexpr (TS == 16 && !HEAD) {
     if (g.loss_rows && g.tail_out) {
       const int l15 = lane & 15, kg = lane >> 4;
       const int ntiles = (g.tail_n + 15) / 16;
@@ -517,7 +609,7 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
     }
   }
 #ifdef TOPS_AB_KNOBS
-  if (stamp_on) { __builtin_amdgcn_s_waitcnt(0); SM_STAMP(8); }   // (this wave's stores acknowledged)
+  if (SM_STAMP_ON) { __builtin_amdgcn_s_waitcnt(0); SM_STAMP(8); }   // (this wave's stores acknowledged)
 #endif
 }
 
@@ -533,16 +625,20 @@ __global__ __launch_bounds__(NW * 64) void gemm_small_kernel(SmallArgsT<S> g) {
 // path for operands that cannot take quads; here the launcher has checked that both can (a_vec, b_vec), so that path is
 // not in the instruction stream.  Same MFMAs on the same data in the same order: the same bits.
 __global__ __launch_bounds__(8 * 64) void gemm_small_head_kernel(SmallArgsT<float> g) {
+  const long long t_entry = SM_ENTRY_CLOCK();
+  small_pin_hot<false>(g);
   g.a_vec = 1;
   g.b_vec = 1;
-  gemm_small_body<float, 0, 1, 8, 16, 2>(g, (int)blockIdx.x, (long)blockIdx.z);
+  gemm_small_body<float, 0, 1, 8, 16, 2, false, 0, false, 0, true>(g, (int)blockIdx.x, (long)blockIdx.z, nullptr, -1, t_entry, true);
 }
 // ... and the same launch behind a tanh hidden layer: the tail multiplies by 1 - h h (a kernel of its own, so that the
 // logistic step's kernel above is the code it was)
 __global__ __launch_bounds__(8 * 64) void gemm_small_head_tanh_kernel(SmallArgsT<float> g) {
+  const long long t_entry = SM_ENTRY_CLOCK();
+  small_pin_hot<false>(g);
   g.a_vec = 1;
   g.b_vec = 1;
-  gemm_small_body<float, 0, 1, 8, 16, 2, false, 0, false, ACT_KIND_TANH>(g, (int)blockIdx.x, (long)blockIdx.z);
+  gemm_small_body<float, 0, 1, 8, 16, 2, false, 0, false, ACT_KIND_TANH, true>(g, (int)blockIdx.x, (long)blockIdx.z, nullptr, -1, t_entry, true);
 }
 
 // Two independent latency-bound GEMMs in ONE launch (the weight gradients of two layers once both
@@ -554,12 +650,18 @@ __global__ __launch_bounds__(8 * 64) void gemm_small_head_tanh_kernel(SmallArgsT
 template <class S, int A1, int B1, int NW1, int TS1, int OS1, int A2, int B2, int NW2, int TS2, int OS2, int P1 = 0, bool STAG1 = false>
 __global__ __launch_bounds__((NW1 > NW2 ? NW1 : NW2) * 64) void gemm_small_pair_kernel(SmallArgsT<S> g1,
                                                                                          SmallArgsT<S> g2, int n1) {
-  if ((int)blockIdx.x < n1) {
+  // n1 and the first problem's hot block in ONE batch of scalar loads, one wait: the workgroups of the first problem -- the
+  // large one, whose tiles the launch waits for -- no longer pay n1's round trip ahead of their own arguments'.  (The second
+  // problem's few workgroups fetch theirs behind the branch, as before: pinning both blocks spills scalar registers.)
+  const long long t_entry = SM_ENTRY_CLOCK();
+  asm volatile("" ::"s"(n1));
+  small_pin_hot<true>(g1);
+  if (__builtin_expect((int)blockIdx.x < n1, 1)) {
     if (NW1 < NW2 && (int)(threadIdx.x >> 6) >= NW1) return;
-    gemm_small_body<S, A1, B1, NW1, TS1, OS1, false, P1, STAG1>(g1, (int)blockIdx.x, 0);
+    gemm_small_body<S, A1, B1, NW1, TS1, OS1, false, P1, STAG1>(g1, (int)blockIdx.x, 0, nullptr, -1, t_entry, true);
   } else {
     if (NW2 < NW1 && (int)(threadIdx.x >> 6) >= NW2) return;
-    gemm_small_body<S, A2, B2, NW2, TS2, OS2>(g2, (int)blockIdx.x - n1, 0);
+    gemm_small_body<S, A2, B2, NW2, TS2, OS2, false, 0, false, 0, false, true>(g2, (int)blockIdx.x - n1, 0, nullptr, -1, t_entry, true);
   }
 }
 
@@ -765,8 +867,8 @@ __device__ __forceinline__ void gemm_small_f64_t32_body(const SmallArgsT<double>
   int a_base[2], b_base[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    a_base[h] = (int)((bz * g.a_sb + (mv[h] ? m[h] : 0) * g.a_sm) * 8);
-    b_base[h] = (int)((bz * g.b_sb + (nv[h] ? n[h] : 0) * g.b_sn) * 8);
+    a_base[h] = (int)(((unsigned)bz * (unsigned)g.a_sb + (unsigned)(mv[h] ? m[h] : 0) * (unsigned)g.a_sm) * 8u);
+    b_base[h] = (int)(((unsigned)bz * (unsigned)g.b_sb + (unsigned)(nv[h] ? n[h] : 0) * (unsigned)g.b_sn) * 8u);
   }
   const int a_sk8 = (int)g.a_sk * 8, b_sk8 = (int)g.b_sk * 8;
   auto sel = [](bool ok, int off) { const int msk = -(int)ok; return (off & msk) | (0x7fffffff & ~msk); };
@@ -959,6 +1061,19 @@ static int pick_tile_order(const GemmProblem& p, int ts, int tiles_m, int tiles_
   return col_cost < row_cost ? 2 : 1;
 }
 
+// tile_of's constants for the grid and the order the arguments carry: the eighth of the tile count and its remainder, the
+// extent the tile index is divided by and its reciprocal.  ceil(2^32 / d) gives the exact quotient by a multiply-high for
+// every tile index below 2^16 (gemm_small_can: at most 65,535 tiles) when d < 2^16; d = 1 needs none.
+// To be called again whenever tiles_m, tiles_n or tile_order change.
+template <class S>
+static void small_plan_map(SmallArgsT<S>& g) {
+  const unsigned T = (unsigned)g.tiles_m * (unsigned)g.tiles_n;
+  g.map_q = T >> 3;
+  g.map_r = T & 7u;
+  g.map_d = (unsigned)(g.tile_order == 2 ? g.tiles_m : g.tiles_n);
+  g.map_mag = g.map_d >= 2u ? (unsigned)(0xFFFFFFFFull / g.map_d + 1ull) : 0u;
+}
+
 template <class S, int NW, int TS, int ONESHOT = 0, int TAILK = 0>
 static void launch_nw(SmallArgsT<S>& g, const GemmProblem& p, int amode, int bmode, hipStream_t s) {
   constexpr int CK = (TS == 32) ? 8 : 16;
@@ -968,6 +1083,7 @@ static void launch_nw(SmallArgsT<S>& g, const GemmProblem& p, int amode, int bmo
   g.tiles_n = (int)((p.N + TS - 1) / TS);
   g.tiles_m = tiles_m;
   g.tile_order = pick_tile_order(p, TS, g.tiles_m, g.tiles_n);
+  small_plan_map(g);
   dim3 grid(tiles_m * g.tiles_n, 1, (unsigned)p.batch), block(NW * 64);
   switch (amode * 2 + bmode) {
     case 0: launch_k((gemm_small_kernel<S, 0, 0, NW, TS, ONESHOT, TAILK>), grid, block, 0, s, g); break;
@@ -992,7 +1108,7 @@ static long long* small_stamps(int which) {
       // (a staged body -- PARTS >= 1 -- stamps 2 and 3 without a wait: the loads ahead of the first MFMA are out; the first part's MFMAs are issued)
       static const char* names[9] = {"entry", "set-up done", "operand batch issued", "operand batch landed", "MFMAs done, partial in LDS",
                                      "all partials there (barrier)", "reduced + epilogue / loss head, stores issued", "tail done", "stores acknowledged"};
-      std::fprintf(stderr, "[small stamps %d] tile 0, thread 0, us since its workgroup began:", want);
+      std::fprintf(stderr, "[small stamps %d] tile 0, thread 0, us since the first instruction of its kernel (a kernel that pins its argument block) or body:", want);
       for (int i = 1; i < 9; ++i)
         if (keep[i]) std::fprintf(stderr, "\n  %6.2f  %s", (keep[i] - keep[0]) * 0.01, names[i]);
       std::fprintf(stderr, "\n");
@@ -1019,8 +1135,8 @@ static SmallPlan plan_small(const GemmProblem& p, SmallArgsT<S>& g) {
   g.A = (const S*)p.A; g.B = (const S*)p.B; g.C = (S*)p.C;
   g.Cin = (p.beta != 0.0) ? (const S*)p.Cin : nullptr;
   g.M = (int)p.M; g.N = (int)p.N; g.K = (int)p.K;
-  g.a_sm = p.a_sm; g.a_sk = p.a_sk; g.b_sk = p.b_sk; g.b_sn = p.b_sn; g.c_sm = p.c_sm;
-  g.a_sb = p.a_sb; g.b_sb = p.b_sb; g.c_sb = p.c_sb;
+  g.a_sm = (int)p.a_sm; g.a_sk = (int)p.a_sk; g.b_sk = (int)p.b_sk; g.b_sn = (int)p.b_sn; g.c_sm = p.c_sm;
+  g.a_sb = (int)p.a_sb; g.b_sb = (int)p.b_sb; g.c_sb = p.c_sb;
   g.alpha = (S)p.alpha; g.beta = (S)p.beta;
   g.bias = (const S*)p.bias; g.dact = (const S*)p.dact; g.act = p.act; g.dact_kind = p.dact_kind;
   g.rowsum = (S*)p.rowsum;
@@ -1095,12 +1211,14 @@ static SmallPlan plan_small(const GemmProblem& p, SmallArgsT<S>& g) {
     g.tiles_n = (int)((p.N + 31) / 32);
     g.tiles_m = (int)((p.M + 31) / 32);
     g.tile_order = pick_tile_order(p, 32, g.tiles_m, g.tiles_n);
+    small_plan_map(g);
     return c;
   }
   g.kper = (int)(((chunks + c.nw - 1) / c.nw) * ck);
   g.tiles_n = (int)((p.N + c.ts - 1) / c.ts);
   g.tiles_m = (int)((p.M + c.ts - 1) / c.ts);
   g.tile_order = pick_tile_order(p, c.ts, g.tiles_m, g.tiles_n);
+  small_plan_map(g);
   return c;
 }
 
@@ -1325,10 +1443,12 @@ bool launch_gemm_small_seam(const GemmProblem& pf, const GemmProblem& ph, hipStr
   if (ph.K > 8 * 2 * 16) return false;            // one batch of two 16-k chunks per wave
   c.head.kper = (int)((((ph.K + 15) / 16 + 7) / 8) * 16);
   c.head.tile_order = 0;                          // head tile = 2 * row block + half
+  small_plan_map(c.head);
   const int T = c.fwd.tiles_m * c.fwd.tiles_n;
   // every XCD must own whole row blocks: runs of T / 8 tiles of the row-major sequence, no remainder, tiles_n | run
   if (T % 8 != 0 || (T / 8) % c.fwd.tiles_n != 0 || c.fwd.tiles_m > 128) return false;
   c.fwd.tile_order = 1;
+  small_plan_map(c.fwd);
   // (a row block whose second 16-row half lies beyond M: every row of that head tile is masked, every load bounds-checked)
   if (!g_seam_ctr) return false;   // (allocated by to_init: never inside a stream capture)
   c.ctr = g_seam_ctr;

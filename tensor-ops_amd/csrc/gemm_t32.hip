@@ -37,10 +37,20 @@ namespace to {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-struct T32Args {   // (pointers first, then 8-byte, then 4-byte members: a float wedged between pointers made the compiler keep a
-                   //  slice of the argument block in scratch and read `bias` / `dact` back from memory, ~1 us each, serially)
+struct T32Args {
+  // ---- the hot block: everything in front of the first operand load, in the leading 80 bytes.  The kernels pin it
+  // (t32_pin_hot) so that it is requested at the entry in one batch of scalar loads and waited for ONCE; the members behind
+  // it are waited for where they are first used, with the operand loads in flight.
   const float* A;
   const float* B;
+  long a_sx, b_sx;   // element stride between consecutive rows of the operand's IMAGE: KC: between x; XC: between k
+  int M, N, K;
+  int tiles_m, tiles_n;
+  int lgm, lgn;      // the XCDs as a 2^lgm x 2^lgn grid over the tiles (t32_tile_of; planned by t32_plan_map)
+  unsigned wmag0, wmag1;   // ceil(2^32 / w) for the two widths an XCD's rectangle can have, tiles_n >> lgn and one more (t32_plan_map)
+  int pd;            // chunks a wave keeps in flight (<= NS)
+  // ---- the cold members (pointers, then 8-byte, then 4-byte members: a float wedged between pointers made the compiler keep
+  //  a slice of the argument block in scratch and read `bias` / `dact` back from memory, ~1 us each, serially)
   float* C;
   const float* Cin;
   const float* bias;
@@ -48,18 +58,24 @@ struct T32Args {   // (pointers first, then 8-byte, then 4-byte members: a float
   float* rowsum;
   const float* rowsum_in;
   unsigned long long* dbg;   // development builds (TOPS_T32_STAMPS=1): ticks of the 100 MHz clock at six points of workgroups 0 and last
-                             // (thread 0: slots 0..15), and of every wave's "K loop done" / "partial written" (lane 0: slots 16..47)
-  long a_sx, b_sx;   // element stride between consecutive rows of the operand's IMAGE: KC: between x; XC: between k
+                             // (thread 0: slot 0 = the body's first instruction, 1..5 as printed, 6 = the first operand load is out; slot 7 of the second record -- word 15 -- marks the joined launch),
+                             // and of every wave's "K loop done" / "partial written" (lane 0: slots 16..47)
   long c_sm;
-  int M, N, K;
-  int tiles_m, tiles_n;
-  int gm, gn;        // the XCDs as a gm x gn grid over the tiles (t32_tile_of)
+  int gm, gn;        // the XCD grid (host side: t32_grid; the kernels read lgm / lgn)
   int act, dact_kind;
   int rowsum_acc;
-  int pd;            // chunks a wave keeps in flight (<= NS)
   float alpha, beta;
   float rowsum_alpha;
 };
+
+// Every member of the hot block as an input of ONE empty asm statement at the kernel's entry: their scalar loads are
+// issued together, ahead of it, and one s_waitcnt covers them -- left alone, the compiler requests a member where it is
+// first used (A and B behind the tile map's arithmetic and behind the branch that sends surplus workgroups home), a serial
+// round trip each time.
+__device__ __forceinline__ void t32_pin_hot(const T32Args& g) {
+  asm volatile("" ::"s"(g.A), "s"(g.B), "s"(g.a_sx), "s"(g.b_sx), "s"(g.M), "s"(g.N), "s"(g.K), "s"(g.tiles_m), "s"(g.tiles_n),
+               "s"(g.lgm), "s"(g.lgn), "s"(g.wmag0), "s"(g.wmag1), "s"(g.pd));
+}
 
 // what a lane without a valid source fetches instead: its 16 bytes of the image become zeros (a k beyond the wave's run
 // must contribute nothing; an x beyond the extent only reaches rows / columns that are never stored)
@@ -76,13 +92,18 @@ constexpr int T32_WAVE = T32_NS * T32_STAGE;               // floats per wave
 // A and tiles_n / gn of B -- dZ1^T X (8 x 25 tiles): a 2 x 4 grid pulls 10 panels of 128 KB through each XCD's fabric
 // port where runs of the row-major sequence pulled 26 (the whole of X into every L2: the K loop ran at half the MFMA rate).
 // The grid is 8 x the largest rectangle; workgroups beyond their XCD's rectangle leave at once.
-__device__ __forceinline__ bool t32_tile_of(int tiles_m, int tiles_n, int gm, int gn, int bid, int& tm, int& tn) {
-  const int x = bid & 7, local = bid >> 3, xm = x / gn, xn = x - xm * gn;
-  const int r0 = tiles_m * xm / gm, r1 = tiles_m * (xm + 1) / gm, c0 = tiles_n * xn / gn, c1 = tiles_n * (xn + 1) / gn;
+// No division here: the grid's extents are powers of two (shifts), and the one true quotient, local / w, is a multiply-high
+// by the reciprocal the host planned for that width (t32_plan_map: exact for local, w < 2^16).
+__device__ __forceinline__ bool t32_tile_of(const T32Args& g, int bid, int& tm, int& tn) {
+  const int x = bid & 7, local = bid >> 3, xm = x >> g.lgn, xn = x & ((1 << g.lgn) - 1);
+  const int r0 = (g.tiles_m * xm) >> g.lgm, r1 = (g.tiles_m * (xm + 1)) >> g.lgm;
+  const int c0 = (g.tiles_n * xn) >> g.lgn, c1 = (g.tiles_n * (xn + 1)) >> g.lgn;
   const int w = c1 - c0;
   if (w <= 0 || local >= (r1 - r0) * w) return false;
-  tm = r0 + local / w;
-  tn = c0 + local - (local / w) * w;
+  const unsigned mag = w == (g.tiles_n >> g.lgn) ? g.wmag0 : g.wmag1;
+  const int q = w == 1 ? local : (int)__umulhi((unsigned)local, mag);   // local / w
+  tm = r0 + q;
+  tn = c0 + local - q * w;
   return true;
 }
 
@@ -120,21 +141,38 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
   static_assert(WAVE_F >= 1024 + 64, "a wave's stage memory holds its partial tile and its row sums");
   static_assert(!ARAG || !AKC, "the dword form is for a row-contiguous A");
   constexpr int NA = ARAG ? 16 : 4, PER = NA + 4;   // DMA instructions per chunk
+#ifdef TOPS_AB_KNOBS
+  // the body's first instruction (the clock's value is only stored behind the first operand load: no wait of its own here)
+  const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
+#endif
+  t32_pin_hot(g);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, half = lane >> 5;
-  unsigned long long* const dbg = (g.dbg && tid == 0 && (bid == 0 || bid == (int)gridDim.x - 1)) ? g.dbg + (bid == 0 ? 0 : 8) : nullptr;
-  auto stamp = [&](int i) { if (dbg) dbg[i] = __builtin_amdgcn_s_memrealtime(); };
 #ifdef TOPS_AB_KNOBS
+  // (who stamps is decided in stamp_first, behind the first operand load: `dbg` and the grid's size are cold)
+  unsigned long long* dbg = nullptr;
   // lane 0 of EVERY wave of the two stamped workgroups: 0 = its K loop done, 1 = its partial tile written (slots 16..47)
-  unsigned long long* const wdbg = (g.dbg && lane == 0 && wave < 8 && (bid == 0 || bid == (int)gridDim.x - 1)) ? g.dbg + 16 + (bid == 0 ? 0 : 16) + 2 * wave : nullptr;
+  unsigned long long* wdbg = nullptr;
+  auto stamp = [&](int i) { if (dbg) dbg[i] = __builtin_amdgcn_s_memrealtime(); };
+  // slot 0 = the entry, slot 6 = the first operand load (the register unit's, or chunk 0's DMA) is out
+  auto stamp_first = [&] {
+    const bool mine = g.dbg && (bid == 0 || bid == (int)gridDim.x - 1);
+    dbg = (mine && tid == 0) ? g.dbg + (bid == 0 ? 0 : 8) : nullptr;
+    wdbg = (mine && lane == 0 && wave < 8) ? g.dbg + 16 + (bid == 0 ? 0 : 16) + 2 * wave : nullptr;
+    if (dbg) { dbg[0] = t_entry; dbg[6] = __builtin_amdgcn_s_memrealtime(); }
+  };
+#else
+  auto stamp = [](int) {};
+  auto stamp_first = [] {};
+#endif
+#ifdef TOPS_AB_KNOBS
 #define T32_WSTAMP(i) do { if (wdbg) wdbg[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define T32_WSTAMP(i) do { } while (0)
 #endif
   int tile_m, tile_n;
-  if (!t32_tile_of(g.tiles_m, g.tiles_n, g.gm, g.gn, bid, tile_m, tile_n)) return -1;
-  stamp(0);
+  if (!t32_tile_of(g, bid, tile_m, tile_n)) return -1;
   const int m0 = tile_m * 32, n0 = tile_n * 32;
 
   // the epilogue's operands do not depend on the product: their loads go out first
@@ -153,8 +191,8 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
 
   // this wave's run of k, in units of 16
   const int U = (g.K + 15) / 16;
-  const int k0 = (int)((long)U * wave / NW) * 16;
-  int k1 = (int)((long)U * (wave + 1) / NW) * 16;
+  const int k0 = (int)((unsigned)(U * wave) / (unsigned)NW) * 16;        // (U < 2^27, NW a power of two: a shift)
+  int k1 = (int)((unsigned)(U * (wave + 1)) / (unsigned)NW) * 16;
   if (k1 > g.K) k1 = g.K;
   // kd: where the DMA chunks of the run end -- k1, or (REGU, an odd run) the start of the unit that goes through registers
   int kd = k1;
@@ -263,7 +301,7 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   float asum = 0.f;                      // sum over k of this lane's A elements (row sums of A: bias gradients)
-  const bool want_rs = g.rowsum != nullptr && tile_n == 0;
+  bool want_rs;                          // (reads a cold member: set behind the first operand loads)
 
   const int PD = g.pd < NS ? g.pd : NS;
   const int pro = nC < PD ? nC : PD;
@@ -310,6 +348,8 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
   if constexpr (EARLY) {
     if (pro > 0) issue(0);
     __builtin_amdgcn_sched_barrier(0);
+    stamp_first();
+    want_rs = g.rowsum != nullptr && tile_n == 0;
     if constexpr (REGU) {
       if (ru) {
         // the unit has landed when at most chunk 0's DMA instructions are outstanding; the values are tied to the wait so
@@ -349,6 +389,8 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
     for (int c = 1; c < pro; ++c) issue(c);
   } else {
     for (int c = 0; c < pro; ++c) issue(c);
+    stamp_first();
+    want_rs = g.rowsum != nullptr && tile_n == 0;
   }
   stamp(1);
 
@@ -510,7 +552,7 @@ __global__ __launch_bounds__(256) void gemm_t32_head_kernel(T32Args g, T32HeadAr
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned long long t_entry = g.dbg ? __builtin_amdgcn_s_memrealtime() : 0ull;
   int tile_m, tile_n;
-  if (!t32_tile_of(g.tiles_m, g.tiles_n, g.gm, g.gn, (int)blockIdx.x, tile_m, tile_n)) return;
+  if (!t32_tile_of(g, (int)blockIdx.x, tile_m, tile_n)) return;
   // what the head needs besides H does not depend on this launch: W2's rows (this lane's four columns), the bias, the
   // target of lanes 0..N2-1 -- their loads go out ahead of everything
   const long grow = (long)tile_m * 32 + 4 * tile_n + wave;   // the row this wave finishes
@@ -644,6 +686,21 @@ __global__ __launch_bounds__(256) void gemm_t32_pair_kernel(T32Args g1, T32Args 
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
+// The tile map's constants (t32_tile_of), planned once for an XCD grid gm x gn (powers of two): the two shifts and the
+// reciprocals of the two widths a rectangle can have.  ceil(2^32 / w) gives the exact quotient by a multiply-high for every
+// dividend below 2^16 when w < 2^16; w = 1 needs none (its reciprocal does not fit 32 bits).  False: too many tiles for that.
+static bool t32_plan_map(T32Args& g) {
+  if ((long)g.tiles_m * g.tiles_n > 65535) return false;
+  auto lg = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
+  auto mag = [](int w) { return w >= 2 ? (unsigned)((0xFFFFFFFFull / (unsigned)w) + 1ull) : 0u; };
+  g.lgm = lg(g.gm);
+  g.lgn = lg(g.gn);
+  const int wlo = g.tiles_n >> g.lgn;
+  g.wmag0 = mag(wlo);
+  g.wmag1 = mag(wlo + 1);
+  return true;
+}
+
 // ragged_a: out: A is row-contiguous and needs the dword form (only looked for when allow_ragged_a)
 static bool t32_fill(const GemmProblem& p, T32Args& g, bool& akc, bool& bkc, bool allow_ragged_a = false, bool* ragged_a = nullptr) {
   if (p.dtype != TO_F32 || p.batch != 1 || p.reduce_batch) return false;
@@ -685,6 +742,7 @@ static bool t32_fill(const GemmProblem& p, T32Args& g, bool& akc, bool& bkc, boo
       if (cost < best) { best = cost; g.gm = gm; g.gn = gn; }
     }
   }
+  if (!t32_plan_map(g)) return false;
   g.alpha = (float)p.alpha; g.beta = (float)p.beta;
   g.bias = (const float*)p.bias; g.dact = (const float*)p.dact; g.act = p.act; g.dact_kind = p.dact_kind;
   g.rowsum = (float*)p.rowsum; g.rowsum_in = (const float*)p.rowsum_in; g.rowsum_alpha = (float)p.rowsum_alpha;
@@ -705,9 +763,9 @@ static bool t32_fill(const GemmProblem& p, T32Args& g, bool& akc, bool& bkc, boo
         }
         for (int w = 0; w < (keep[15] ? 1 : 2); ++w) {
           const unsigned long long* k = keep + 8 * w;
-          std::fprintf(stderr, "[t32] %s workgroup of the last launch, us since it began: prologue DMA issued %.2f, first chunk landed %.2f, K loop done %.2f, "
-                               "partials met %.2f, done %.2f; began %.2f us after workgroup 0\n", w ? "last" : "first",
-                       (k[1] - k[0]) * 0.01, (k[2] - k[0]) * 0.01, (k[3] - k[0]) * 0.01, (k[4] - k[0]) * 0.01, (k[5] - k[0]) * 0.01,
+          std::fprintf(stderr, "[t32] %s workgroup of the last launch, us since its first instruction: first operand load out %.2f, prologue DMA issued %.2f, "
+                               "first chunk landed %.2f, K loop done %.2f, partials met %.2f, done %.2f; began %.2f us after workgroup 0\n", w ? "last" : "first",
+                       (k[6] - k[0]) * 0.01, (k[1] - k[0]) * 0.01, (k[2] - k[0]) * 0.01, (k[3] - k[0]) * 0.01, (k[4] - k[0]) * 0.01, (k[5] - k[0]) * 0.01,
                        ((double)k[0] - (double)keep[0]) * 0.01);
           // every wave of that workgroup (the last one to write its partial closes the barrier)
           const unsigned long long* wv = keep + 16 + 16 * w;
@@ -863,6 +921,7 @@ bool launch_gemm_t32_head(const GemmProblem& pf, const GemmProblem& ph, hipStrea
     if (reinterpret_cast<uintptr_t>(ph.tail_out) & 15u) return false;
   }
   g.gm = 8; g.gn = 1;   // a row block's eight tiles on one XCD (for speed; the hand-over does not depend on it)
+  if (!t32_plan_map(g)) return false;
   if (g.tiles_m < 8) return false;
   // every workgroup must be resident from the start (they wait for each other): one round of the chip at most
   {

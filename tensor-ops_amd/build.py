@@ -13,13 +13,25 @@ MNIST_BIN = os.path.join(HERE, "tensor-ops-mnist-hip")
 SOURCES = ["runtime.cpp", "expr.cpp", "expr_jit.cpp", "rowprog.cpp", "api.cpp", "gemm_route.cpp", "stack_util.cpp", "stack_ff.cpp", "stack_rnn.cpp", "lazy.cpp", "lazy_plan.cpp", "lazy_cache.cpp", "lazy_exec.cpp", "comm.cpp", "gemm_f32_mfma.hip", "gemm_small.hip", "gemm_t32.hip", "gemm_skinnyk.hip", "gemm_kwave.hip", "gemm_kw16.hip", "gemm_kwave_f64.hip", "gemm_skinnyk_f64.hip", "gemm_f64.hip", "ewise.hip", "reduce_layout.hip", "gemv.hip", "fused_fflayer.hip", "p2p.hip", "online_sgd.hip", "infer_head.hip", "rnn_seq.hip", "induce_seq.hip", "minibatch_stage.hip", "recon_head.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function"]
+# Kernarg preload: the dispatcher puts a kernel's LEADING scalar and pointer parameters (up to 14 dwords beside the kernarg
+# pointer; never members of a struct) into user SGPRs, so the wave starts with them instead of fetching them.  The step's
+# kernels take their hot arguments that way (DESIGN.md 3.4 lists every kernel whose preload length is non-zero).  The flag
+# is build-wide on purpose: the schedule tests compile with FLAGS and must see the product's code.
+PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
+NOPRELOAD = bool(os.environ.get("TOPS_BUILD_NOPRELOAD"))   # the same sources without the flag, for measuring what it is worth
+if not NOPRELOAD:
+    FLAGS += PRELOAD
 AB = bool(os.environ.get("TOPS_BUILD_AB"))
+# each variant's objects and library in a directory of its own (build_ab/, build_nopreload/, build_ab_nopreload/)
+VARIANT = "build" + ("_ab" if AB else "") + ("_nopreload" if NOPRELOAD else "")
+if NOPRELOAD:   # load it with TOPS_HIP_LIB=.../build_nopreload/libtensorops_hip.so LD_LIBRARY_PATH=.../build_nopreload
+    LIB = os.path.join(HERE, VARIANT, "libtensorops_hip.so")
 if AB:   # development build: the A/B knobs and the extra tile-shape variants are compiled in.  Its objects and its library
     # live in build_ab/ (as tools/build_ab_lib.py's do): toggling the variable can never leave product and development
     # objects mixed in one directory or a development library under the product's name.  Load it with
     # TOPS_HIP_LIB=.../build_ab/libtensorops_hip.so LD_LIBRARY_PATH=.../build_ab
     FLAGS += ["-DTOPS_AB_KNOBS", "-DTOPS_GEMM_AB_VARIANTS"]
-    LIB = os.path.join(HERE, "build_ab", "libtensorops_hip.so")
+    LIB = os.path.join(HERE, VARIANT, "libtensorops_hip.so")
 # The kernel files whose hand-written waits, barriers and wait states tools/asm_inflight_check.py proves on the GENERATED
 # code (tests/test_pinned_asm.py): their device assembly -- the very text the object was assembled from -- is kept
 # beside the object (build/<stem>-hip-amdgcn-amd-amdhsa-gfx950.s; -save-temps, everything else it leaves is deleted).
@@ -44,7 +56,7 @@ def _walk(d):
 
 
 def needs_build():
-    arts = (LIB,) if AB else (LIB, HOST_LIB, DOTS_BIN, MNIST_BIN)
+    arts = (LIB,) if AB or NOPRELOAD else (LIB, HOST_LIB, DOTS_BIN, MNIST_BIN)
     if not all(os.path.exists(f) for f in arts):
         return True
     t = min(os.path.getmtime(f) for f in arts)
@@ -58,7 +70,7 @@ def build(force=False, verbose=True):
     name and renamed into place, so a process that has the library mapped never sees it change underneath."""
     if not force and not needs_build():
         return LIB
-    objdir = os.path.join(HERE, "build_ab" if AB else "build")
+    objdir = os.path.join(HERE, VARIANT)
     os.makedirs(objdir, exist_ok=True)
     import fcntl
     with open(os.path.join(objdir, ".lock"), "w") as lock:
@@ -111,7 +123,7 @@ def _build_locked(force, verbose, objdir):
             os.remove(os.path.join(objdir, f))
     _link([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs +
           ["-L/opt/rocm/lib", "-lhiprtc", "-ldl", "-Wl,-rpath,/opt/rocm/lib"], LIB)
-    if AB:   # (the host mirror and the apps belong to the product build: they resolve libtensorops_hip.so by LD_LIBRARY_PATH)
+    if AB or NOPRELOAD:   # (the host mirror and the apps belong to the product build: they resolve libtensorops_hip.so by LD_LIBRARY_PATH)
         return LIB
     _link(["g++", "-shared", "-fPIC", "-o", HOST_LIB, host_obj, "-L" + HERE, "-ltensorops_hip", "-Wl,-rpath,$ORIGIN"], HOST_LIB)
     # the Dots app on the HIP backend (host/apps/dots.cpp)

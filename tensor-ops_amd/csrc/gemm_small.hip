@@ -9,8 +9,10 @@
 // 4..16 K-slices over the chip cuts the per-wave chain to <= 128 MFMAs.
 //
 // Serves the batched ffLayer step (config 3): X.W1^T, dZ^T.X, H.W2^T, dZ2^T.H, dZ2.W2.
+#include "arg_fit.hpp"
 #include "common.hpp"
 
+#include <cstddef>
 #include <type_traits>
 
 namespace to {
@@ -20,8 +22,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 template <class S>
 struct SmallArgsT {
   // ---- the hot block: what stands in front of the first operand load -- the leading 64 bytes, and the strides behind
-  // them.  The step's kernels pin it (small_pin_hot) so that it is requested at the kernel's entry in one batch of scalar
-  // loads and waited for ONCE; everything further down is waited for where it is first used.
+  // them.  The step's kernels (loss head, weight-gradient pair) do not read theirs from here: they take it as leading scalar
+  // parameters, which the dispatcher preloads into registers, and fill it into their copy of this block.  Every other
+  // kernel reads a member where it is first used.  (small_ask_operands reads members of this block by OFFSET.)
   const S* A;
   const S* B;
   unsigned a_bytes, b_bytes;  // extents for the buffer descriptors (hardware bounds check)
@@ -31,8 +34,7 @@ struct SmallArgsT {
                      // contiguous run of the row-major (1) / column-major (2) tile sequence, so its private L2
                      // pulls a few A panels + all of B (1) or a few B panels + all of A (2) instead of everything
   unsigned map_d, map_mag, map_q, map_r;   // tile_of's constants, planned on the host (small_plan_map) from the tile grid and the order
-  int tiles_n;       // (the sixteenth dword, pinned with the rest: a dword of the block that nobody holds on to is a register the
-                     //  compiler may write ahead of the wait, which then has to come early)
+  int tiles_n;
   int a_sm, a_sk, b_sk, b_sn;   // element strides, low 32 bits: they only ever enter 32-bit byte offsets (gemm_small_can: an
   int a_sb, b_sb;               // operand spans < 2 GiB), and the low 32 bits of a sum of products need only the factors' low 32 bits
   // ---- the epilogue's operands (the weight-gradient pair's 32x32 body asks for them ahead of its operands) ----
@@ -63,31 +65,16 @@ struct SmallArgsT {
 #endif
 };
 
-// Every member of the hot block as an input of an empty asm statement at the kernel's entry: their scalar loads go out
-// together ahead of it and one s_waitcnt covers them.  Left alone, the compiler requests a member where it is first used --
-// the tile grid first, the pointers and strides behind tile_of's arithmetic, a serial round trip each time.  EPI: the
-// epilogue's operands too (a body whose first vector loads are the epilogue prefetches).
-template <bool EPI, class S>
-__device__ __forceinline__ void small_pin_hot(const SmallArgsT<S>& g) {
-  if constexpr (EPI) {
-    // what stands in front of the epilogue prefetches: the tile map, the extents, the epilogue's operands.  (The operands'
-    // own members are asked for right behind the branch on n1, under the tile map's arithmetic and the prefetches: pinning
-    // them here as well holds some forty scalar registers across a body that has none to spare.)
-    asm volatile("" ::"s"(g.M), "s"(g.N), "s"(g.tile_order), "s"(g.map_d), "s"(g.map_mag), "s"(g.map_q), "s"(g.map_r), "s"(g.Cin), "s"(g.bias),
-                 "s"(g.dact), "s"(g.c_sm));
-  } else {
-    asm volatile("" ::"s"(g.A), "s"(g.B), "s"(g.a_bytes), "s"(g.b_bytes), "s"(g.M), "s"(g.N), "s"(g.K), "s"(g.kper), "s"(g.tile_order),
-                 "s"(g.map_d), "s"(g.map_mag), "s"(g.map_q), "s"(g.map_r), "s"(g.tiles_n), "s"(g.a_sm), "s"(g.a_sk), "s"(g.b_sk), "s"(g.b_sn));
-  }
-}
-
 #ifdef TOPS_AB_KNOBS
 // (who stamps is worked out at the stamp, not at the entry: `dbg` is a cold member.  Slot 0, the entry, is the clock read by
 //  the body's first instruction; it is stored with the first stamp behind the operand loads -- SM_STAMP_ENTRY -- so that
 //  nothing in front of the first load waits for the clock or for `dbg`)
 #define SM_STAMP_ON stamp_on
 #define SM_STAMP(i) do { if (stamp_on) g.dbg[i] = wall_clock64(); } while (0)
-#define SM_STAMP_ENTRY() do { stamp_on = g.dbg && bid == 0 && tid == 0; if (stamp_on) g.dbg[0] = t_entry; } while (0)
+#define SM_STAMP_ENTRY() do { if (have_entry) asm volatile("" : "+v"(t_entry)); stamp_on = g.dbg && bid == 0 && tid == 0; if (stamp_on) g.dbg[0] = t_entry; } while (0)
+// (a clock handed in by a kernel whose hot arguments are preloaded: moved to a vector register pair -- the bodies have no
+//  scalar registers to spare -- at the first stamp and not at the entry, where the move would be a wait on the scalar
+//  counter in front of the first load that the product does not have)
 #define SM_ENTRY_CLOCK() wall_clock64()
 #else
 #define SM_STAMP_ENTRY() do { } while (0)
@@ -140,6 +127,39 @@ __device__ __forceinline__ float xor16(float x) {
 template <int OFF>
 __device__ __forceinline__ double xor16(double x) { return __shfl_xor(x, OFF, 64); }
 
+// The operands' own members of an argument block, asked for by the KERNEL itself at a point of its choosing
+// (small_ask_operands) and taken -- one wait -- where the body first needs them (gemm_small_body, LATE).  Why by hand: left
+// to the compiler, a member's scalar load is sunk to its first use; in the weight-gradient pair that is behind the epilogue
+// prefetches, a round trip of its own in front of the operand loads, and pinning the members instead (an empty asm) is a wait
+// where they are pinned.  Here the request leaves ahead of the tile map and the prefetches and its trip runs under them.
+// The words have NOT arrived until small_take_operands has waited: nothing may read or copy them in between
+// (tests/test_step_preload.py looks at the generated code for that).
+typedef unsigned int su32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int su32x2 __attribute__((ext_vector_type(2)));
+struct SmallEarly {
+  su32x4 ab;        // A, B
+  su32x2 bytes;     // a_bytes, b_bytes
+  su32x2 kk;        // K, kper
+  su32x4 strides;   // a_sm, a_sk, b_sk, b_sn
+  su32x4 rs;        // rowsum, rowsum_in (not needed early -- but the compiler asks for them right in front of the wait, which then
+                    // waits a whole trip for them)
+};
+// OFF: the argument block's byte offset in the kernel's argument segment
+template <int OFF, class S>
+__device__ __forceinline__ void small_ask_operands(SmallEarly& e) {
+  typedef SmallArgsT<S> G;
+  static_assert(offsetof(G, A) == 0 && offsetof(G, B) == 8 && offsetof(G, a_bytes) == 16 && offsetof(G, b_bytes) == 20 && offsetof(G, K) == 32 &&
+                offsetof(G, kper) == 36 && offsetof(G, a_sm) == 64 && offsetof(G, a_sk) == 68 && offsetof(G, b_sk) == 72 && offsetof(G, b_sn) == 76 &&
+                offsetof(G, rowsum) == 168 && offsetof(G, rowsum_in) == 176,
+                "the requests below read these members by offset");
+  asm volatile("s_load_dwordx4 %0, %5, %6\n\ts_load_dwordx2 %1, %5, %7\n\ts_load_dwordx2 %2, %5, %8\n\ts_load_dwordx4 %3, %5, %9\n\ts_load_dwordx4 %4, %5, %10"
+               : "=&s"(e.ab), "=&s"(e.bytes), "=&s"(e.kk), "=&s"(e.strides), "=&s"(e.rs)
+               : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(OFF), "n"(OFF + 16), "n"(OFF + 32), "n"(OFF + 64), "n"(OFF + 168));
+}
+__device__ __forceinline__ void small_take_operands(SmallEarly& e) {
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(e.ab), "+s"(e.bytes), "+s"(e.kk), "+s"(e.strides), "+s"(e.rs)::"memory");
+}
+
 // AMODE 0: A k-contiguous (a_sk == 1)   1: A m-contiguous / general strides
 // BMODE 0: B n-contiguous / general     1: B k-contiguous (b_sk == 1)
 // Within a chunk of 8 k the MFMA j of half-wave `half` consumes k = k0 + 4*half + j, for A and B alike.
@@ -171,14 +191,17 @@ __device__ __forceinline__ double xor16(double x) { return __shfl_xor(x, OFF, 64
 //      wave without one loaded zeros: 0 + 0 x 0, the same bits) -- so nothing but the K loop's MFMAs and the accumulator's
 //      LDS write lies between the loads and the reduction barrier.  Every other body: the epilogue prefetch first, the
 //      tail's loads behind the MFMAs, as before.
-template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0, bool EXT = false, int PARTS = 0, bool STAG = false, int TAILK = 0, bool HEAD = false, bool KMASK = false>   // ONESHOT: 0, or the chunks one batch holds; TAILK: GemmProblem::tail_kind
+// LATE (the weight-gradient pair's first body): the operands' own members are not g's but `early`'s, requested by the kernel
+//      (small_ask_operands); the epilogue prefetch goes out, THEN they are waited for -- the prefetches are that body's
+//      first vector loads either way.
+template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0, bool EXT = false, int PARTS = 0, bool STAG = false, int TAILK = 0, bool HEAD = false, bool KMASK = false, bool LATE = false>   // ONESHOT: 0, or the chunks one batch holds; TAILK: GemmProblem::tail_kind
 __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const int bid, const long bz, S* ext_lds = nullptr,
-                                                const int tid_in = -1, const long long t_entry_in = 0, const bool have_entry = false) {
+                                                const int tid_in = -1, const long long t_entry_in = 0, const bool have_entry = false,
+                                                SmallEarly* early = nullptr) {
 #ifdef TOPS_AB_KNOBS
-  // the clock at the kernel's first instruction (a kernel that pins its hot block reads it ahead of the pin and hands it in;
+  // the clock at the kernel's first instruction (a kernel whose hot arguments are preloaded reads it first thing and hands it in;
   // elsewhere: the body's first instruction)
   long long t_entry = have_entry ? t_entry_in : wall_clock64();
-  if (have_entry) asm volatile("" : "+v"(t_entry));   // (kept in a vector register pair: the bodies have no scalar registers to spare)
   bool stamp_on = false;   // (set by SM_STAMP_ENTRY, the first stamp of every path)
 #endif
   static_assert(!HEAD || (sizeof(S) == 4 && TS == 16 && ONESHOT && PARTS == 0), "HEAD: the fp32 16x16 one-shot in the compiler's order");
@@ -215,9 +238,52 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
   for (int r = 0; r < NR; ++r) acc[r] = S(0);
   S asum = S(0);  // sum over k of this lane's A elements (fused row sums of A = bias gradients)
 
-  const int kbeg = wave * g.kper;
-  int kend = kbeg + g.kper;
-  if (kend > g.K) kend = g.K;
+  // row of accumulator register r of this lane's k-group within the 16x16 tile (see the header comment)
+  auto row16 = [&](int kg, int r) { return ES == 8 ? kg + 4 * r : 4 * kg + r; };
+  // Epilogue operands (Cin, the activation derivative's h, the bias) do not depend on the product: their
+  // loads go out FIRST and are long back when the cross-wave reduction ends, instead of a dependent load there
+  // (measured neutral on config 3's in-place SGD epilogue, Cin = W: 26.5 us per step either way -- the
+  // reduction's barrier hides it -- kept because it never costs).
+  constexpr int NRW = (NR + NW - 1) / NW;  // registers r = wave, wave + NW, ... finished by this wave
+  S* Cb = g.C + bz * g.c_sb;
+  const S* Ci = g.Cin ? g.Cin + bz * g.c_sb : nullptr;
+  const S* Hd = g.dact ? g.dact + bz * g.c_sb : nullptr;
+  S pf_ci[NRW], pf_hd[NRW], pf_bias = S(0);
+  auto prefetch_epilogue = [&] {
+    const long col = (long)tile_n * TS + l31;
+    if (g.bias && col < g.N) pf_bias = g.bias[col];
+#pragma unroll
+    for (int i = 0; i < NRW; ++i) {
+      const int r = wave + i * NW;
+      const int lrow = (TS == 32) ? (r & 3) + 8 * (r >> 2) + 4 * half : row16(half, r);
+      const long row = (long)tile_m * TS + lrow;
+      const bool ok = r < NR && row < g.M && col < g.N;
+      pf_ci[i] = (Ci && ok) ? Ci[row * g.c_sm + col] : S(0);
+      pf_hd[i] = (Hd && ok) ? Hd[row * g.c_sm + col] : S(0);
+    }
+  };
+  // the operands' own members: g's, or (LATE) the words the kernel asked for at its entry -- behind the prefetch
+  const S* opA = g.A;
+  const S* opB = g.B;
+  unsigned op_a_bytes = g.a_bytes, op_b_bytes = g.b_bytes;
+  S* op_rowsum = g.rowsum;
+  const S* op_rowsum_in = g.rowsum_in;
+  int op_K = g.K, op_kper = g.kper, op_a_sm = g.a_sm, op_a_sk = g.a_sk, op_b_sk = g.b_sk, op_b_sn = g.b_sn;
+  if constexpr (LATE) {
+    static_assert(!HEAD, "LATE: a body whose first loads are the epilogue prefetches");
+    prefetch_epilogue();
+    small_take_operands(*early);
+    opA = reinterpret_cast<const S*>(((unsigned long)early->ab.y << 32) | early->ab.x);
+    opB = reinterpret_cast<const S*>(((unsigned long)early->ab.w << 32) | early->ab.z);
+    op_a_bytes = early->bytes.x; op_b_bytes = early->bytes.y;
+    op_K = (int)early->kk.x; op_kper = (int)early->kk.y;
+    op_a_sm = (int)early->strides.x; op_a_sk = (int)early->strides.y; op_b_sk = (int)early->strides.z; op_b_sn = (int)early->strides.w;
+    op_rowsum = reinterpret_cast<S*>(((unsigned long)early->rs.y << 32) | early->rs.x);
+    op_rowsum_in = reinterpret_cast<const S*>(((unsigned long)early->rs.w << 32) | early->rs.z);
+  }
+  const int kbeg = wave * op_kper;
+  int kend = kbeg + op_kper;
+  if (kend > op_K) kend = op_K;
 
   // Software pipeline, two register stages of ST chunks (8 k each): the loads of stage s+1
   // are in flight while the 4*ST MFMAs of stage s run -- one wave per SIMD has no other
@@ -229,12 +295,12 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
   // offset 0x7fffffff (>= num_records) and the hardware returns 0 -- no branch, no select on
   // the loaded value, so the compiler cannot turn the guard into a waited conditional load.
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<S*>(g.A), 0, g.a_bytes, 0x00020000);
+      const_cast<S*>(opA), 0, op_a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<S*>(g.B), 0, g.b_bytes, 0x00020000);
-  const int a_base = (int)(((unsigned)bz * (unsigned)g.a_sb + (unsigned)(mv ? m : 0) * (unsigned)g.a_sm) * (unsigned)ES);
-  const int b_base = (int)(((unsigned)bz * (unsigned)g.b_sb + (unsigned)(nv ? n : 0) * (unsigned)g.b_sn) * (unsigned)ES);
-  const int a_sk4 = (int)g.a_sk * ES, b_sk4 = (int)g.b_sk * ES;
+      const_cast<S*>(opB), 0, op_b_bytes, 0x00020000);
+  const int a_base = (int)(((unsigned)bz * (unsigned)g.a_sb + (unsigned)(mv ? m : 0) * (unsigned)op_a_sm) * (unsigned)ES);
+  const int b_base = (int)(((unsigned)bz * (unsigned)g.b_sb + (unsigned)(nv ? n : 0) * (unsigned)op_b_sn) * (unsigned)ES);
+  const int a_sk4 = op_a_sk * ES, b_sk4 = op_b_sk * ES;
   // arithmetic select (no short-circuit &&, no ?:) so that no control flow is generated
   auto sel = [](bool ok, int off) { const int msk = -(int)ok; return (off & msk) | (0x7fffffff & ~msk); };
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -347,31 +413,7 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  // row of accumulator register r of this lane's k-group within the 16x16 tile (see the header comment)
-  auto row16 = [&](int kg, int r) { return ES == 8 ? kg + 4 * r : 4 * kg + r; };
-  // Epilogue operands (Cin, the activation derivative's h, the bias) do not depend on the product: their
-  // loads go out FIRST and are long back when the cross-wave reduction ends, instead of a dependent load there
-  // (measured neutral on config 3's in-place SGD epilogue, Cin = W: 26.5 us per step either way -- the
-  // reduction's barrier hides it -- kept because it never costs).
-  constexpr int NRW = (NR + NW - 1) / NW;  // registers r = wave, wave + NW, ... finished by this wave
-  S* Cb = g.C + bz * g.c_sb;
-  const S* Ci = g.Cin ? g.Cin + bz * g.c_sb : nullptr;
-  const S* Hd = g.dact ? g.dact + bz * g.c_sb : nullptr;
-  S pf_ci[NRW], pf_hd[NRW], pf_bias = S(0);
-  auto prefetch_epilogue = [&] {
-    const long col = (long)tile_n * TS + l31;
-    if (g.bias && col < g.N) pf_bias = g.bias[col];
-#pragma unroll
-    for (int i = 0; i < NRW; ++i) {
-      const int r = wave + i * NW;
-      const int lrow = (TS == 32) ? (r & 3) + 8 * (r >> 2) + 4 * half : row16(half, r);
-      const long row = (long)tile_m * TS + lrow;
-      const bool ok = r < NR && row < g.M && col < g.N;
-      pf_ci[i] = (Ci && ok) ? Ci[row * g.c_sm + col] : S(0);
-      pf_hd[i] = (Hd && ok) ? Hd[row * g.c_sm + col] : S(0);
-    }
-  };
-  if constexpr (!HEAD) prefetch_epilogue();
+  if constexpr (!HEAD && !LATE) prefetch_epilogue();
   constexpr int SK = CK * ST;
   if constexpr (!HEAD) {
     SM_STAMP_ENTRY();
@@ -495,7 +537,7 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
   SM_STAMP(4);   // (MFMAs done, partial tile written to LDS)
   __syncthreads();
   SM_STAMP(5);   // (every wave's partial is there)
-  if (g.rowsum && tile_n == 0 && wave == 0 && lane < TS) {
+  if (op_rowsum && tile_n == 0 && wave == 0 && lane < TS) {
     // rowsum[m] = sum_k A[m,k]: add the k-groups (lanes l, l+TS, ...) of every wave
     S v = S(0);
 #pragma unroll
@@ -503,7 +545,7 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
 #pragma unroll
       for (int q = 0; q < KG; ++q) v += rsum[w][lane + q * TS];
     const long row = (long)tile_m * TS + lane;
-    if (row < g.M) g.rowsum[bz * g.M + row] = g.rowsum_acc ? g.rowsum_in[bz * g.M + row] + g.rowsum_alpha * v : v;
+    if (row < g.M) op_rowsum[bz * g.M + row] = g.rowsum_acc ? op_rowsum_in[bz * g.M + row] + g.rowsum_alpha * v : v;
   }
 #pragma unroll
   for (int i = 0; i < NRW; ++i) {
@@ -624,22 +666,35 @@ __global__ __launch_bounds__(NW * 64) void gemm_small_kernel(SmallArgsT<S> g) {
 // eight MFMAs on nothing and four more 16-byte loads a wave in front of the reduction barrier -- and carried the dword-load
 // path for operands that cannot take quads; here the launcher has checked that both can (a_vec, b_vec), so that path is
 // not in the instruction stream.  Same MFMAs on the same data in the same order: the same bits.
-__global__ __launch_bounds__(8 * 64) void gemm_small_head_kernel(SmallArgsT<float> g) {
+// Both kernels take what stands in front of the operand loads as LEADING SCALARS -- twelve dwords, which the build's kernarg
+// preload (build.py, FLAGS) has the dispatcher put in user SGPRs: the operand batch leaves without waiting for any scalar
+// load.  To fit, the instance is narrowed to what the step launches (launch_small_t checks it): one batch, k-contiguous
+// operands (the k strides are the constant 1) and the trivial tile map -- one column of tiles, workgroup b takes row block
+// b -- so no map constant needs a register.  With one column of tiles every A panel belongs to exactly one tile: which
+// workgroup takes which is of no consequence to any L2.  `cold` is the whole argument block; its hot members are not read.
+#define SMALL_HEAD_PARAMS const float* A, const float* B, unsigned a_bytes, unsigned b_bytes, int M, int N, int K, int kper, int a_sm, int b_sn, SmallArgsT<float> cold
+#define SMALL_HEAD_ARGS(g) (g).A, (g).B, (g).a_bytes, (g).b_bytes, (g).M, (g).N, (g).K, (g).kper, (g).a_sm, (g).b_sn, (g)
+#define SMALL_HEAD_FILL()                                                                                     \
+  SmallArgsT<float> g = cold;                                                                                 \
+  g.A = A; g.B = B; g.a_bytes = a_bytes; g.b_bytes = b_bytes; g.M = M; g.N = N; g.K = K; g.kper = kper;         \
+  g.a_sm = a_sm; g.b_sn = b_sn; g.a_sk = 1; g.b_sk = 1; g.a_sb = 0; g.b_sb = 0;                                 \
+  g.tile_order = 0; g.map_d = 1u; g.map_mag = 0u; g.map_q = 0u; g.map_r = 0u; g.tiles_n = 1;                    \
+  g.a_vec = 1; g.b_vec = 1;                                                                                   \
+  __builtin_amdgcn_sched_barrier(0)   /* the cold block's scalar loads stay up here, ahead of the operand loads' address arithmetic */
+__global__ __launch_bounds__(8 * 64) void gemm_small_head_kernel(SMALL_HEAD_PARAMS) {
   const long long t_entry = SM_ENTRY_CLOCK();
-  small_pin_hot<false>(g);
-  g.a_vec = 1;
-  g.b_vec = 1;
-  gemm_small_body<float, 0, 1, 8, 16, 2, false, 0, false, 0, true>(g, (int)blockIdx.x, (long)blockIdx.z, nullptr, -1, t_entry, true);
+  SMALL_HEAD_FILL();
+  gemm_small_body<float, 0, 1, 8, 16, 2, false, 0, false, 0, true>(g, (int)blockIdx.x, 0, nullptr, -1, t_entry, true);
 }
 // ... and the same launch behind a tanh hidden layer: the tail multiplies by 1 - h h (a kernel of its own, so that the
 // logistic step's kernel above is the code it was)
-__global__ __launch_bounds__(8 * 64) void gemm_small_head_tanh_kernel(SmallArgsT<float> g) {
+__global__ __launch_bounds__(8 * 64) void gemm_small_head_tanh_kernel(SMALL_HEAD_PARAMS) {
   const long long t_entry = SM_ENTRY_CLOCK();
-  small_pin_hot<false>(g);
-  g.a_vec = 1;
-  g.b_vec = 1;
-  gemm_small_body<float, 0, 1, 8, 16, 2, false, 0, false, ACT_KIND_TANH, true>(g, (int)blockIdx.x, (long)blockIdx.z, nullptr, -1, t_entry, true);
+  SMALL_HEAD_FILL();
+  gemm_small_body<float, 0, 1, 8, 16, 2, false, 0, false, ACT_KIND_TANH, true>(g, (int)blockIdx.x, 0, nullptr, -1, t_entry, true);
 }
+#undef SMALL_HEAD_FILL
+#undef SMALL_HEAD_PARAMS
 
 // Two independent latency-bound GEMMs in ONE launch (the weight gradients of two layers once both
 // cotangents exist): workgroups [0, n1) run the first problem, the rest the second.  Each launch costs
@@ -647,18 +702,33 @@ __global__ __launch_bounds__(8 * 64) void gemm_small_head_tanh_kernel(SmallArgsT
 // The block is sized for the larger configuration; the surplus waves of the smaller one exit at once
 // (a finished wave no longer counts at s_barrier).
 // P1 / STAG1: PARTS / STAG of the first problem's body (the second keeps the compiler's order).
+// n1 and what stands in front of the first problem's epilogue prefetches -- the large problem, whose tiles the launch waits
+// for -- are LEADING SCALARS, fourteen dwords, which the build's kernarg preload (build.py, FLAGS) has the dispatcher put in
+// user SGPRs: the tile map and the three prefetches wait for no scalar load, and the operands' own members (`first`, the
+// whole argument block; its members named here are not read) are one trip that runs under them.  To fit the fourteen: the
+// tile order rides in n1's upper byte (small_pair_word: n1 < 2^16 workgroups) and the output's row stride is 32-bit
+// (launch_gemm_small_pair refuses a pair whose stride does not fit).  The second problem's few workgroups fetch their
+// block from memory behind the branch, as before.
+__host__ __device__ __forceinline__ int small_pair_word(int n1, int tile_order) { return n1 | (tile_order << 24); }
+#define SMALL_PAIR_ARGS(g1, g2, n1) (g1).Cin, (g1).bias, (g1).dact, small_pair_word(n1, (g1).tile_order), (g1).M, (g1).N, (g1).map_d, (g1).map_mag, (g1).map_q, (g1).map_r, (int)(g1).c_sm, (g1), (g2)
 template <class S, int A1, int B1, int NW1, int TS1, int OS1, int A2, int B2, int NW2, int TS2, int OS2, int P1 = 0, bool STAG1 = false>
-__global__ __launch_bounds__((NW1 > NW2 ? NW1 : NW2) * 64) void gemm_small_pair_kernel(SmallArgsT<S> g1,
-                                                                                         SmallArgsT<S> g2, int n1) {
-  // n1 and the first problem's hot block in ONE batch of scalar loads, one wait: the workgroups of the first problem -- the
-  // large one, whose tiles the launch waits for -- no longer pay n1's round trip ahead of their own arguments'.  (The second
-  // problem's few workgroups fetch theirs behind the branch, as before: pinning both blocks spills scalar registers.)
+__global__ __launch_bounds__((NW1 > NW2 ? NW1 : NW2) * 64) void gemm_small_pair_kernel(const S* Cin, const S* bias, const S* dact, int word, int M, int N,
+                                                                                         unsigned map_d, unsigned map_mag, unsigned map_q, unsigned map_r,
+                                                                                         int c_sm, SmallArgsT<S> first, SmallArgsT<S> g2) {
   const long long t_entry = SM_ENTRY_CLOCK();
-  asm volatile("" ::"s"(n1));
-  small_pin_hot<true>(g1);
+  const int n1 = word & 0xFFFFFF;
   if (__builtin_expect((int)blockIdx.x < n1, 1)) {
     if (NW1 < NW2 && (int)(threadIdx.x >> 6) >= NW1) return;
-    gemm_small_body<S, A1, B1, NW1, TS1, OS1, false, P1, STAG1>(g1, (int)blockIdx.x, 0, nullptr, -1, t_entry, true);
+    SmallArgsT<S> g1 = first;
+    g1.Cin = Cin; g1.bias = bias; g1.dact = dact; g1.tile_order = word >> 24; g1.M = M; g1.N = N;
+    g1.map_d = map_d; g1.map_mag = map_mag; g1.map_q = map_q; g1.map_r = map_r; g1.c_sm = c_sm;
+    // `first` lies behind the fourteen leading dwords: byte 56 of the argument segment.  Whoever adds, removes or resizes a
+    // leading parameter of this kernel changes this 56 with it (tests/test_step_preload.py reads the block's offset from the
+    // generated metadata and fails otherwise; the static_assert in small_ask_operands covers only the members' offsets INSIDE
+    // the block).
+    SmallEarly early;
+    small_ask_operands<56, S>(early);
+    gemm_small_body<S, A1, B1, NW1, TS1, OS1, false, P1, STAG1, 0, false, false, true>(g1, (int)blockIdx.x, 0, nullptr, -1, t_entry, true, &early);
   } else {
     if (NW2 < NW1 && (int)(threadIdx.x >> 6) >= NW2) return;
     gemm_small_body<S, A2, B2, NW2, TS2, OS2, false, 0, false, 0, false, true>(g2, (int)blockIdx.x - n1, 0, nullptr, -1, t_entry, true);
@@ -1108,7 +1178,7 @@ static long long* small_stamps(int which) {
       // (a staged body -- PARTS >= 1 -- stamps 2 and 3 without a wait: the loads ahead of the first MFMA are out; the first part's MFMAs are issued)
       static const char* names[9] = {"entry", "set-up done", "operand batch issued", "operand batch landed", "MFMAs done, partial in LDS",
                                      "all partials there (barrier)", "reduced + epilogue / loss head, stores issued", "tail done", "stores acknowledged"};
-      std::fprintf(stderr, "[small stamps %d] tile 0, thread 0, us since the first instruction of its kernel (a kernel that pins its argument block) or body:", want);
+      std::fprintf(stderr, "[small stamps %d] tile 0, thread 0, us since the first instruction of its kernel (a kernel whose hot arguments are preloaded) or body:", want);
       for (int i = 1; i < 9; ++i)
         if (keep[i]) std::fprintf(stderr, "\n  %6.2f  %s", (keep[i] - keep[0]) * 0.01, names[i]);
       std::fprintf(stderr, "\n");
@@ -1259,12 +1329,14 @@ static void launch_small_t(const GemmProblem& p, hipStream_t s) {
   bool lean = false;
   if constexpr (!F64)
     lean = head_lean && g.loss_rows && c.ts == 16 && c.nw == 8 && c.os == 0 && amode == 0 && bmode == 1 && g.a_vec && g.b_vec &&
-           p.K <= 8 * 2 * 16;
+           p.K <= 8 * 2 * 16 && g.tiles_n == 1 && p.batch == 1;   // (one column of tiles, one batch: the kernels' leading scalars carry no more)
   if (lean) {
     if constexpr (!F64) {   // (plan_small's kper is already the slice of at most two chunks)
-      const dim3 grid((unsigned)(g.tiles_m * g.tiles_n), 1, (unsigned)p.batch), block(8 * 64);
-      if (tanh_tail) launch_k(gemm_small_head_tanh_kernel, grid, block, 0, s, g);
-      else launch_k(gemm_small_head_kernel, grid, block, 0, s, g);
+      g.tile_order = 0;     // the trivial map: workgroup b takes row block b (the kernels assume it)
+      small_plan_map(g);
+      const dim3 grid((unsigned)g.tiles_m), block(8 * 64);
+      if (tanh_tail) launch_k(gemm_small_head_tanh_kernel, grid, block, 0, s, SMALL_HEAD_ARGS(g));
+      else launch_k(gemm_small_head_kernel, grid, block, 0, s, SMALL_HEAD_ARGS(g));
     }
   } else if (tanh_tail) {   // (a fused tail is always eight waves on 16x16 tiles, two-stage: plan_small)
     TO_CHECK(c.ts == 16 && c.nw == 8 && c.os == 0, TO_ERR_STATE, "internal: fused tail outside its configuration");
@@ -1514,6 +1586,7 @@ bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStr
     count_launch();
     return true;
   }
+  if (!fits_i32(p1.c_sm)) return false;   // (the pair kernel takes the first problem's output stride as a 32-bit leading scalar)
   SmallArgsT<float> g1, g2;
   const SmallPlan c1 = plan_small<float>(p1, g1), c2 = plan_small<float>(p2, g2);
 #ifdef TOPS_AB_KNOBS
@@ -1528,7 +1601,7 @@ bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStr
     const long t1 = (long)g1.tiles_m * g1.tiles_n, t2 = (long)g2.tiles_m * g2.tiles_n;
     if (t1 + t2 > 65535) return false;
     if (dry) return true;
-    launch_k((gemm_small_pair_kernel<float, 1, 0, 1, 16, 0, 1, 0, 1, 16, 0>), dim3((unsigned)(t1 + t2)), dim3(64), 0, s, g1, g2, (int)t1);
+    launch_k((gemm_small_pair_kernel<float, 1, 0, 1, 16, 0, 1, 0, 1, 16, 0>), dim3((unsigned)(t1 + t2)), dim3(64), 0, s, SMALL_PAIR_ARGS(g1, g2, (int)t1));
     TO_HIP(hipGetLastError());
     count_launch();
     return true;
@@ -1543,7 +1616,7 @@ bool launch_gemm_small_pair(const GemmProblem& p1, const GemmProblem& p2, hipStr
   //  workgroup; the same K -- the batch -- puts both problems in the one-shot range together anyway)
   // who orders the big problem's 64 loads against its 32 MFMAs (gemm_small_body, PARTS / STAG; DESIGN.md 3.4 has the
   // measurement): SMALL_PAIR_PARTS parts, staggered or not, is what ships; a development build can run every form.
-#define TOPS_PAIR(P, ST) launch_k((gemm_small_pair_kernel<float, 1, 0, 16, 32, 8, 1, 0, 8, 16, 8, P, ST>), grid, block, 0, s, g1, g2, n1)
+#define TOPS_PAIR(P, ST) launch_k((gemm_small_pair_kernel<float, 1, 0, 16, 32, 8, 1, 0, 8, 16, 8, P, ST>), grid, block, 0, s, SMALL_PAIR_ARGS(g1, g2, n1))
 #ifdef TOPS_AB_KNOBS
   static const int parts = [] { const char* e = ab_getenv("TOPS_SMALL_PARTS"); return e ? atoi(e) : SMALL_PAIR_PARTS; }();
   static const int stag = [] { const char* e = ab_getenv("TOPS_SMALL_STAGGER"); return e ? atoi(e) : (int)SMALL_PAIR_STAG; }();

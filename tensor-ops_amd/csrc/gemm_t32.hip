@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "arg_fit.hpp"
 
 namespace to {
 
@@ -38,9 +39,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct T32Args {
-  // ---- the hot block: everything in front of the first operand load, in the leading 80 bytes.  The kernels pin it
-  // (t32_pin_hot) so that it is requested at the entry in one batch of scalar loads and waited for ONCE; the members behind
-  // it are waited for where they are first used, with the operand loads in flight.
+  // ---- the hot block: everything in front of the first operand load, in the leading 80 bytes.  The forward kernel
+  // (gemm_t32_kernel) does not read it from here: it takes it as leading scalar parameters, which the dispatcher preloads into
+  // registers, and fills it into its copy of this block.  The development forms (gemm_t32_head_kernel, gemm_t32_pair_kernel)
+  // pin it (t32_pin_hot) so that it is requested at the entry in one batch of scalar loads and waited for ONCE.  The members
+  // behind it are waited for where they are first used, with the operand loads in flight.
   const float* A;
   const float* B;
   long a_sx, b_sx;   // element stride between consecutive rows of the operand's IMAGE: KC: between x; XC: between k
@@ -68,7 +71,7 @@ struct T32Args {
   float rowsum_alpha;
 };
 
-// Every member of the hot block as an input of ONE empty asm statement at the kernel's entry: their scalar loads are
+// (The development forms; gemm_t32_body, PIN.)  Every member of the hot block as an input of ONE empty asm statement at the kernel's entry: their scalar loads are
 // issued together, ahead of it, and one s_waitcnt covers them -- left alone, the compiler requests a member where it is
 // first used (A and B behind the tile map's arithmetic and behind the branch that sends surplus workgroups home), a serial
 // round trip each time.
@@ -134,7 +137,8 @@ __device__ __forceinline__ int t32_key(int x) { return (x >> 1) & 7; }
 // outstanding], the unit's MFMAs, the epilogue prefetch, and from there as without REGU (every later wait is for all).
 // The unit's loads are inline assembly like the DMA: the compiler does not count the DMA instructions, so a wait of its
 // own making would be vmcnt(0) and hold the MFMAs until chunk 0 is there.
-template <bool AKC, bool BKC, bool ARAG = false, bool WT = false, int NW = T32_NW, int NS = T32_NS, bool EARLY = false, bool REGU = false>
+// PIN: the hot block comes from memory and is pinned at the entry (false: the caller holds it in registers already)
+template <bool AKC, bool BKC, bool ARAG = false, bool WT = false, int NW = T32_NW, int NS = T32_NS, bool EARLY = false, bool REGU = false, bool PIN = true>
 __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, float* smem) {
   static_assert(!REGU || (NW == 8 && NS == 1 && EARLY && !ARAG), "the register unit belongs to the eight-wave, one-stage, early-DMA form");
   constexpr int WAVE_F = NS * T32_STAGE;   // floats of LDS per wave
@@ -145,7 +149,7 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
   // the body's first instruction (the clock's value is only stored behind the first operand load: no wait of its own here)
   const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
 #endif
-  t32_pin_hot(g);
+  if constexpr (PIN) t32_pin_hot(g);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, half = lane >> 5;
@@ -670,10 +674,28 @@ __global__ __launch_bounds__(256) void gemm_t32_head_kernel(T32Args g, T32HeadAr
   }
 }
 
+// The forward kernel takes the hot block as LEADING SCALARS -- twelve dwords: the build's kernarg preload (build.py, FLAGS)
+// has the dispatcher put them in user SGPRs, so a wave starts with everything in front of its first operand load and the
+// body waits for no scalar load before it.  (Only leading scalar and pointer parameters preload, never members of a struct;
+// fourteen dwords fit beside the kernarg pointer.)  To fit: the strides are 32-bit (t32_fill admits spans below 2 GiB only,
+// and the body forms 32-bit byte offsets from them anyway), lgm, lgn and pd share one word (t32_pack_map), and the tile
+// grid is derived from M and N exactly as t32_fill derives it (t32_tiles).  `cold` is the whole argument block as every
+// other kernel of this file takes it; its hot members are not read here.
+__host__ __device__ __forceinline__ int t32_tiles(int extent) { return (extent + 31) >> 5; }
+__host__ __device__ __forceinline__ unsigned t32_pack_map(int lgm, int lgn, int pd) { return (unsigned)lgm | ((unsigned)lgn << 8) | ((unsigned)pd << 16); }
+
 template <bool AKC, bool BKC, int NW = T32_NW, int NS = T32_NS, bool EARLY = false, bool REGU = false>
-__global__ __launch_bounds__(NW * 64) void gemm_t32_kernel(T32Args g) {
+__global__ __launch_bounds__(NW * 64) void gemm_t32_kernel(const float* A, const float* B, int a_sx, int b_sx, int M, int N, int K,
+                                                           unsigned map, unsigned wmag0, unsigned wmag1, T32Args cold) {
   extern __shared__ __attribute__((aligned(1024))) float t32_smem[];
-  gemm_t32_body<AKC, BKC, false, false, NW, NS, EARLY, REGU>(g, (int)blockIdx.x, t32_smem);
+  T32Args g = cold;
+  g.A = A; g.B = B;
+  g.a_sx = a_sx; g.b_sx = b_sx;
+  g.M = M; g.N = N; g.K = K;
+  g.tiles_m = t32_tiles(M); g.tiles_n = t32_tiles(N);
+  g.lgm = (int)(map & 255u); g.lgn = (int)((map >> 8) & 255u); g.pd = (int)(map >> 16);
+  g.wmag0 = wmag0; g.wmag1 = wmag1;
+  gemm_t32_body<AKC, BKC, false, false, NW, NS, EARLY, REGU, false>(g, (int)blockIdx.x, t32_smem);
 }
 
 // Two weight-gradient contractions (dZ^T . A: both operands row-contiguous, K = the batch) in ONE launch: the first
@@ -724,16 +746,15 @@ static bool t32_fill(const GemmProblem& p, T32Args& g, bool& akc, bool& bkc, boo
   if (p.bias && (reinterpret_cast<uintptr_t>(p.bias) & 15u)) return false;
   if (p.beta != 0.0 && !p.Cin) return false;
   if (p.act > 2) return false;
-  // byte offsets are 32-bit
-  if ((p.M + 32) * std::max<int64_t>(p.a_sm, 1) * 4 + p.K * std::max<int64_t>(p.a_sk, 1) * 4 >= (1LL << 31)) return false;
-  if ((p.N + 32) * std::max<int64_t>(p.b_sn, 1) * 4 + p.K * std::max<int64_t>(p.b_sk, 1) * 4 >= (1LL << 31)) return false;
+  // byte offsets are 32-bit, and so are the strides the forward kernel takes as leading scalars
+  if (!t32_spans_fit(p.M, p.N, p.K, p.a_sm, p.a_sk, p.b_sn, p.b_sk)) return false;
   g.A = (const float*)p.A; g.B = (const float*)p.B; g.C = (float*)p.C;
   g.Cin = p.beta != 0.0 ? (const float*)p.Cin : nullptr;
   g.M = (int)p.M; g.N = (int)p.N; g.K = (int)p.K;
   g.a_sx = akc ? p.a_sm : p.a_sk;
   g.b_sx = bkc ? p.b_sn : p.b_sk;
   g.c_sm = p.c_sm;
-  g.tiles_m = (int)((p.M + 31) / 32); g.tiles_n = (int)((p.N + 31) / 32);
+  g.tiles_m = t32_tiles((int)p.M); g.tiles_n = t32_tiles((int)p.N);   // (the forward kernel derives them from M and N by the same function)
   {   // the XCD grid that pulls the fewest panels into each L2
     int best = 1 << 30;
     for (int gm : {8, 4, 2, 1}) {
@@ -826,10 +847,13 @@ static void t32_launch_nw(const T32Args& g, bool akc, bool bkc, hipStream_t s) {
     attr = true;
   }
   const dim3 grid((unsigned)t32_grid(g)), block(NW * 64);
-  if (akc && bkc) launch_k((gemm_t32_kernel<true, true, NW, NS, EARLY, REGU>), grid, block, lds, s, g);
-  else if (akc) launch_k((gemm_t32_kernel<true, false, NW, NS, EARLY, REGU>), grid, block, lds, s, g);
-  else if (bkc) launch_k((gemm_t32_kernel<false, true, NW, NS, EARLY, REGU>), grid, block, lds, s, g);
-  else launch_k((gemm_t32_kernel<false, false, NW, NS, EARLY, REGU>), grid, block, lds, s, g);
+  // the leading scalars (gemm_t32_kernel): t32_fill has checked that the strides fit
+#define T32_HOT g.A, g.B, (int)g.a_sx, (int)g.b_sx, g.M, g.N, g.K, t32_pack_map(g.lgm, g.lgn, g.pd), g.wmag0, g.wmag1
+  if (akc && bkc) launch_k((gemm_t32_kernel<true, true, NW, NS, EARLY, REGU>), grid, block, lds, s, T32_HOT, g);
+  else if (akc) launch_k((gemm_t32_kernel<true, false, NW, NS, EARLY, REGU>), grid, block, lds, s, T32_HOT, g);
+  else if (bkc) launch_k((gemm_t32_kernel<false, true, NW, NS, EARLY, REGU>), grid, block, lds, s, T32_HOT, g);
+  else launch_k((gemm_t32_kernel<false, false, NW, NS, EARLY, REGU>), grid, block, lds, s, T32_HOT, g);
+#undef T32_HOT
 }
 
 void launch_gemm_t32(const GemmProblem& p, hipStream_t s) {

@@ -194,7 +194,12 @@ __device__ __forceinline__ void small_take_operands(SmallEarly& e) {
 // LATE (the weight-gradient pair's first body): the operands' own members are not g's but `early`'s, requested by the kernel
 //      (small_ask_operands); the epilogue prefetch goes out, THEN they are waited for -- the prefetches are that body's
 //      first vector loads either way.
-template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0, bool EXT = false, int PARTS = 0, bool STAG = false, int TAILK = 0, bool HEAD = false, bool KMASK = false, bool LATE = false>   // ONESHOT: 0, or the chunks one batch holds; TAILK: GemmProblem::tail_kind
+// EPI (16x16 bodies: the loss head and its fused tail; without effect on a 32x32 body): nothing behind the reduction barrier
+//      waits for memory it could have asked for earlier -- see pf_t below, the stores of the loss head and of the fused tail.
+//      False: the forms before it -- in the weight-gradient pair, whose kernel is left as it was (it has no loss head; its row
+//      sums' old value fetched ahead of the barrier showed no gain and read slower in its job), and in the loss-head kernels a
+//      development build can be switched to (TOPS_SMALL_EPI=0).
+template <class S, int AMODE, int BMODE, int NW, int TS, int ONESHOT = 0, bool EXT = false, int PARTS = 0, bool STAG = false, int TAILK = 0, bool HEAD = false, bool KMASK = false, bool LATE = false, bool EPI = true>   // ONESHOT: 0, or the chunks one batch holds; TAILK: GemmProblem::tail_kind
 __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const int bid, const long bz, S* ext_lds = nullptr,
                                                 const int tid_in = -1, const long long t_entry_in = 0, const bool have_entry = false,
                                                 SmallEarly* early = nullptr) {
@@ -248,18 +253,27 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
   S* Cb = g.C + bz * g.c_sb;
   const S* Ci = g.Cin ? g.Cin + bz * g.c_sb : nullptr;
   const S* Hd = g.dact ? g.dact + bz * g.c_sb : nullptr;
-  S pf_ci[NRW], pf_hd[NRW], pf_bias = S(0);
-  auto prefetch_epilogue = [&] {
-    const long col = (long)tile_n * TS + l31;
-    if (g.bias && col < g.N) pf_bias = g.bias[col];
-#pragma unroll
-    for (int i = 0; i < NRW; ++i) {
-      const int r = wave + i * NW;
-      const int lrow = (TS == 32) ? (r & 3) + 8 * (r >> 2) + 4 * half : row16(half, r);
-      const long row = (long)tile_m * TS + lrow;
-      const bool ok = r < NR && row < g.M && col < g.N;
-      pf_ci[i] = (Ci && ok) ? Ci[row * g.c_sm + col] : S(0);
-      pf_hd[i] = (Hd && ok) ? Hd[row * g.c_sm + col] : S(0);
+  // arithmetic select (no short-circuit &&, no ?:) so that no control flow is generated
+  auto sel = [](bool ok, int off) { const int msk = -(int)ok; return (off & msk) | (0x7fffffff & ~msk); };
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  // one element through a bounds-checked descriptor: a lane whose offset `sel` turned into 0x7fffffff (>= num_records) loads 0 /
+  // stores nothing -- no branch around the access, no select on a loaded value
+  auto ld1 = [&](__amdgpu_buffer_rsrc_t r, int off) -> S {
+    if constexpr (ES == 4) {
+      return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
+    } else {
+      const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0);
+      return __hiloint2double((int)v.y, (int)v.x);
+    }
+  };
+  auto st1 = [&](S v, __amdgpu_buffer_rsrc_t r, int off) {
+    if constexpr (ES == 4) {
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((float)v), r, off, 0, 0);
+    } else {
+      u32x2 w;
+      w.x = (unsigned)__double2loint((double)v); w.y = (unsigned)__double2hiint((double)v);
+      __builtin_amdgcn_raw_buffer_store_b64(w, r, off, 0, 0);
     }
   };
   // the operands' own members: g's, or (LATE) the words the kernel asked for at its entry -- behind the prefetch
@@ -269,6 +283,32 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
   S* op_rowsum = g.rowsum;
   const S* op_rowsum_in = g.rowsum_in;
   int op_K = g.K, op_kper = g.kper, op_a_sm = g.a_sm, op_a_sk = g.a_sk, op_b_sk = g.b_sk, op_b_sn = g.b_sn;
+  // The loss head's target element of this lane's rows (TS == 16) does not depend on the product either and is asked for
+  // AHEAD of the reduction barrier (EPI; every workgroup is on the stretch behind that barrier just before the kernel can end,
+  // and a dependent load there is a memory round trip nothing hides): pf_t, through a descriptor that is empty without a
+  // loss head and with `sel` for the lanes outside the tile's extents -- such a lane gets 0, never a stray value.
+  S pf_ci[NRW], pf_hd[NRW], pf_bias = S(0), pf_t[NRW];
+  auto prefetch_epilogue = [&] {
+    const long col = (long)tile_n * TS + l31;
+    if (g.bias && col < g.N) pf_bias = g.bias[col];
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<S*>(g.target), 0, (TS == 16 && EPI && g.loss_rows) ? (unsigned)(((g.M - 1) * g.c_sm + g.N) * ES) : 0u, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < NRW; ++i) {
+      const int r = wave + i * NW;
+      const int lrow = (TS == 32) ? (r & 3) + 8 * (r >> 2) + 4 * half : row16(half, r);
+      const long row = (long)tile_m * TS + lrow;
+      const bool ok = r < NR && row < g.M && col < g.N;
+      pf_ci[i] = (Ci && ok) ? Ci[row * g.c_sm + col] : S(0);
+      pf_hd[i] = (Hd && ok) ? Hd[row * g.c_sm + col] : S(0);
+      // (HEAD: branch-free, the kernels always have a loss head.  Elsewhere behind the uniform g.loss_rows: a launch without a
+      //  loss head -- most launches of the generic 16x16 instances -- issues no load for it)
+      if constexpr (TS == 16 && EPI) {
+        pf_t[i] = S(0);
+        if (HEAD || g.loss_rows) pf_t[i] = ld1(rt, sel((r < NR) & (row < g.M) & (col < g.N), (int)((row * g.c_sm + col) * ES)));
+      }
+    }
+  };
   if constexpr (LATE) {
     static_assert(!HEAD, "LATE: a body whose first loads are the epilogue prefetches");
     prefetch_epilogue();
@@ -301,19 +341,7 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
   const int a_base = (int)(((unsigned)bz * (unsigned)g.a_sb + (unsigned)(mv ? m : 0) * (unsigned)op_a_sm) * (unsigned)ES);
   const int b_base = (int)(((unsigned)bz * (unsigned)g.b_sb + (unsigned)(nv ? n : 0) * (unsigned)op_b_sn) * (unsigned)ES);
   const int a_sk4 = op_a_sk * ES, b_sk4 = op_b_sk * ES;
-  // arithmetic select (no short-circuit &&, no ?:) so that no control flow is generated
-  auto sel = [](bool ok, int off) { const int msk = -(int)ok; return (off & msk) | (0x7fffffff & ~msk); };
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  // one element / one quad of 4 consecutive k through the bounds-checked descriptor
-  auto ld1 = [&](__amdgpu_buffer_rsrc_t r, int off) -> S {
-    if constexpr (ES == 4) {
-      return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
-    } else {
-      const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0);
-      return __hiloint2double((int)v.y, (int)v.x);
-    }
-  };
+  // one quad of 4 consecutive k through the bounds-checked descriptor (one element: ld1 above)
   auto ld4 = [&](__amdgpu_buffer_rsrc_t r, bool ok, int off, S (&d)[4]) {
     if constexpr (ES == 4) {
       const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, sel(ok, off), 0, 0);
@@ -535,9 +563,19 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
   for (int r = 0; r < NR; ++r) red[wave][r][lane] = acc[r];
   rsum[wave][lane] = asum;
   SM_STAMP(4);   // (MFMAs done, partial tile written to LDS)
+  // the loss-head kernels: the argument block's members that only the epilogue reads are in registers when the barrier opens
+  // (the barrier waits for the scalar counter anyway: the LDS writes above), instead of a scalar load behind it.
+  // NOT in the weight-gradient pair (LATE): pinned there, the compiler requests the members right in front of
+  // small_take_operands' wait, which then waits a whole trip for them with the operand loads behind it (the pair's average
+  // rose, profiles/README.md), and its short-K development form ran out of scalar registers.
+  if constexpr (EPI && HEAD)
+    asm volatile("" ::"s"(g.alpha), "s"(g.beta), "s"(g.act), "s"(g.dact_kind), "s"(g.c_sm), "s"(g.C), "s"(g.loss_rows), "s"(g.loss_out),
+                 "s"(g.tail_out), "s"(g.tail_n));
   __syncthreads();
   SM_STAMP(5);   // (every wave's partial is there)
-  if (op_rowsum && tile_n == 0 && wave == 0 && lane < TS) {
+  // (HEAD: a loss-head launch with row sums takes the generic kernel, launch_small_t -- their load of the old value would be
+  //  a vector load behind the barrier in the instruction stream of a kernel that never runs it)
+  if (!HEAD && op_rowsum && tile_n == 0 && wave == 0 && lane < TS) {
     // rowsum[m] = sum_k A[m,k]: add the k-groups (lanes l, l+TS, ...) of every wave
     S v = S(0);
 #pragma unroll
@@ -562,7 +600,9 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
         // loss head on the finished row: the 16 lanes of a k-group hold columns 0..15 of one row
         const bool valid = row < g.M && col < g.N;
         v = v * g.alpha + pf_bias;
-        const S t = valid ? g.target[row * g.c_sm + col] : S(0);
+        S t;   // the row's target element, 0 for a lane outside the extents (EPI: fetched ahead of the barrier)
+        if constexpr (EPI) t = pf_t[i];
+        else t = valid ? g.target[row * g.c_sm + col] : S(0);
         // (the same pairs in the same order as the shuffles they replace -- xor 8, 4, 2, 1 -- so the same bits)
         auto sum16 = [](S x) {
           x += xor16<8>(x); x += xor16<4>(x); x += xor16<2>(x); x += xor16<1>(x);
@@ -584,11 +624,21 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
           out = S(-2) * e * sg * (S(1) - sg);
           l = valid ? e * e : S(0);
         }
-        if (valid) Cb[row * g.c_sm + col] = out;
+        if constexpr (EPI) {   // (stores through descriptors: a masked lane's is dropped by the hardware, no branch around it)
+          const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(Cb, 0, (unsigned)(((g.M - 1) * g.c_sm + g.N) * ES), 0x00020000);
+          st1(out, rc, sel(valid, (int)((row * g.c_sm + col) * ES)));
+        } else {
+          if (valid) Cb[row * g.c_sm + col] = out;
+        }
         if (g.tail_out) dzs[lrow * 17 + l31] = valid ? out : S(0);
         if (g.loss_out) {
           l = sum16(l);
-          if (l31 == 0 && row < g.M) g.loss_out[row] = l;
+          if constexpr (EPI) {
+            const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(g.loss_out, 0, (unsigned)(g.M * ES), 0x00020000);
+            st1(l, rl, sel((l31 == 0) & (row < g.M), (int)(row * ES)));
+          } else {
+            if (l31 == 0 && row < g.M) g.loss_out[row] = l;
+          }
         }
         continue;
       }
@@ -634,16 +684,41 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
           }
         }
       }
+      if constexpr (EPI) {
+        // all eight values first -- ONE wait for h, with nothing but loads outstanding -- then the eight stores back to back
+        // through a descriptor on the output: no branch per store, and no store waits for the acknowledgement of another
+        S tv[2][4];
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int t = wave + u * NW;
-        const long col = (long)t * 16 + l15;
+        for (int u = 0; u < 2; ++u)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const long row = (long)tile_m * 16 + row16(kg, r);
-          if (t < ntiles && row < g.M && col < g.tail_n) {
-            if constexpr (TAILK == ACT_KIND_TANH) g.tail_out[row * g.tail_n + col] = acc2[u][r] * tanh_dact(tl_hv[u][r]);
-            else g.tail_out[row * g.tail_n + col] = acc2[u][r] * tl_hv[u][r] * (S(1) - tl_hv[u][r]);
+          for (int r = 0; r < 4; ++r) {
+            if constexpr (TAILK == ACT_KIND_TANH) tv[u][r] = acc2[u][r] * tanh_dact(tl_hv[u][r]);
+            else tv[u][r] = acc2[u][r] * tl_hv[u][r] * (S(1) - tl_hv[u][r]);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+        const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(g.tail_out, 0, (unsigned)(g.M * g.tail_n * ES), 0x00020000);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int t = wave + u * NW, col = t * 16 + l15;
+          const bool cv = (t < ntiles) & (col < g.tail_n);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = tile_m * 16 + row16(kg, r);
+            st1(tv[u][r], ro, sel(cv & (row < g.M), (row * g.tail_n + col) * ES));
+          }
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int t = wave + u * NW;
+          const long col = (long)t * 16 + l15;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const long row = (long)tile_m * 16 + row16(kg, r);
+            if (t < ntiles && row < g.M && col < g.tail_n) {
+              if constexpr (TAILK == ACT_KIND_TANH) g.tail_out[row * g.tail_n + col] = acc2[u][r] * tanh_dact(tl_hv[u][r]);
+              else g.tail_out[row * g.tail_n + col] = acc2[u][r] * tl_hv[u][r] * (S(1) - tl_hv[u][r]);
+            }
           }
         }
       }
@@ -693,6 +768,24 @@ __global__ __launch_bounds__(8 * 64) void gemm_small_head_tanh_kernel(SMALL_HEAD
   SMALL_HEAD_FILL();
   gemm_small_body<float, 0, 1, 8, 16, 2, false, 0, false, ACT_KIND_TANH, true>(g, (int)blockIdx.x, 0, nullptr, -1, t_entry, true);
 }
+#ifdef TOPS_AB_KNOBS
+// TOPS_SMALL_EPI=0: the two kernels with the epilogues as they were (gemm_small_body, EPI = false), so that ONE development
+// library can be switched between the forms.  Under names of their own: the product kernels' names stay unique.
+__global__ __launch_bounds__(8 * 64) void gemm_small_oldepi_head_kernel(SMALL_HEAD_PARAMS) {
+  const long long t_entry = SM_ENTRY_CLOCK();
+  SMALL_HEAD_FILL();
+  gemm_small_body<float, 0, 1, 8, 16, 2, false, 0, false, 0, true, false, false, false>(g, (int)blockIdx.x, 0, nullptr, -1, t_entry, true);
+}
+__global__ __launch_bounds__(8 * 64) void gemm_small_oldepi_head_tanh_kernel(SMALL_HEAD_PARAMS) {
+  const long long t_entry = SM_ENTRY_CLOCK();
+  SMALL_HEAD_FILL();
+  gemm_small_body<float, 0, 1, 8, 16, 2, false, 0, false, ACT_KIND_TANH, true, false, false, false>(g, (int)blockIdx.x, 0, nullptr, -1, t_entry, true);
+}
+static bool small_epi() {
+  static const int on = [] { const char* e = ab_getenv("TOPS_SMALL_EPI"); return e ? atoi(e) : 1; }();
+  return on != 0;
+}
+#endif
 #undef SMALL_HEAD_FILL
 #undef SMALL_HEAD_PARAMS
 
@@ -728,10 +821,10 @@ __global__ __launch_bounds__((NW1 > NW2 ? NW1 : NW2) * 64) void gemm_small_pair_
     // the block).
     SmallEarly early;
     small_ask_operands<56, S>(early);
-    gemm_small_body<S, A1, B1, NW1, TS1, OS1, false, P1, STAG1, 0, false, false, true>(g1, (int)blockIdx.x, 0, nullptr, -1, t_entry, true, &early);
+    gemm_small_body<S, A1, B1, NW1, TS1, OS1, false, P1, STAG1, 0, false, false, true, false>(g1, (int)blockIdx.x, 0, nullptr, -1, t_entry, true, &early);
   } else {
     if (NW2 < NW1 && (int)(threadIdx.x >> 6) >= NW2) return;
-    gemm_small_body<S, A2, B2, NW2, TS2, OS2, false, 0, false, 0, false, true>(g2, (int)blockIdx.x - n1, 0, nullptr, -1, t_entry, true);
+    gemm_small_body<S, A2, B2, NW2, TS2, OS2, false, 0, false, 0, false, true, false, false>(g2, (int)blockIdx.x - n1, 0, nullptr, -1, t_entry, true);
   }
 }
 
@@ -1216,6 +1309,10 @@ static SmallPlan plan_small(const GemmProblem& p, SmallArgsT<S>& g) {
   g.tail_w = (const S*)p.tail_w; g.tail_h = (const S*)p.tail_h;
   g.tail_out = p.loss_rows ? (S*)p.tail_out : nullptr; g.tail_n = p.tail_n;
   TO_CHECK(!g.tail_out || p.tail_n <= 256, TO_ERR_ARG, "fused tail: at most 256 columns (gemm_small_fuses_tail)");
+  // the loss head reads its targets and writes dz, the losses and the tail through descriptors with 32-bit byte offsets
+  // (gemm_small_fuses_loss bounds M at 12,800 rows of at most 16 columns: only an absurd row stride could get here)
+  TO_CHECK(!g.loss_rows || (((p.M - 1) * p.c_sm + p.N) * (int64_t)sizeof(S) < (1LL << 31) && p.M * (int64_t)p.tail_n * (int64_t)sizeof(S) < (1LL << 31)),
+           TO_ERR_ARG, "loss head: the output spans 2 GiB or more");
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
   auto eff = [](int64_t stride, int64_t extent) { return extent == 1 ? (int64_t)0 : stride; };
   SmallPlan c{};
@@ -1329,12 +1426,18 @@ static void launch_small_t(const GemmProblem& p, hipStream_t s) {
   bool lean = false;
   if constexpr (!F64)
     lean = head_lean && g.loss_rows && c.ts == 16 && c.nw == 8 && c.os == 0 && amode == 0 && bmode == 1 && g.a_vec && g.b_vec &&
-           p.K <= 8 * 2 * 16 && g.tiles_n == 1 && p.batch == 1;   // (one column of tiles, one batch: the kernels' leading scalars carry no more)
+           p.K <= 8 * 2 * 16 && g.tiles_n == 1 && p.batch == 1 && !g.rowsum;   // (one column of tiles, one batch: the kernels' leading scalars carry no more)
   if (lean) {
     if constexpr (!F64) {   // (plan_small's kper is already the slice of at most two chunks)
       g.tile_order = 0;     // the trivial map: workgroup b takes row block b (the kernels assume it)
       small_plan_map(g);
       const dim3 grid((unsigned)g.tiles_m), block(8 * 64);
+#ifdef TOPS_AB_KNOBS
+      if (!small_epi()) {
+        if (tanh_tail) launch_k(gemm_small_oldepi_head_tanh_kernel, grid, block, 0, s, SMALL_HEAD_ARGS(g));
+        else launch_k(gemm_small_oldepi_head_kernel, grid, block, 0, s, SMALL_HEAD_ARGS(g));
+      } else
+#endif
       if (tanh_tail) launch_k(gemm_small_head_tanh_kernel, grid, block, 0, s, SMALL_HEAD_ARGS(g));
       else launch_k(gemm_small_head_kernel, grid, block, 0, s, SMALL_HEAD_ARGS(g));
     }

@@ -540,6 +540,56 @@ to_status to_rnn_stack_sgd(int n_layers, const int* state_act, const to_tensor* 
 to_status to_set_rnn_persistent(int on, int* previous_or_null);
 to_status to_rnn_stats(int64_t* persistent_runs, int64_t* stepwise_runs);
 
+/* Closed-loop generation of the same stacks in ONE call: `runNetworkSt` under `iterate` -- prime the stack with a few steps,
+ * then feed every output back as the next input.  The stack, state_act, hidden_act, out_act (TO_ACT_SOFTMAX or
+ * TO_ACT_LOGISTIC; anything else TO_ERR_UNSUPPORTED), the dtypes, the batching of s (unbatched or [B; n_l]) and the s_out
+ * rules are to_rnn_stack_run's.  One STEP is what to_rnn_stack_run does for one time step: z = W a + W' s + b, new state
+ * state_act(z), layer output hidden_act(z), out_act(z) for the last layer.
+ *   prime     X [B; Tp, i] (or [Tp, i]), Tp >= 1: steps 0 .. Tp-1 consume X as to_rnn_stack_run would; their outputs go to
+ *             prime_out_or_null, a contiguous [B; Tp, n_L].
+ *   generate  for k = 0 .. G-1: x_k = feed(prev_k), prev_0 the last prime output and prev_k = g_{k-1} after that;
+ *             g_k = step(x_k) into out, a contiguous [B; G, n_L].  n_L == i is required (TO_ERR_SHAPE), G >= 1 (TO_ERR_ARG).
+ *   feed      TO_FEED_OUTPUT  x_k is prev_k as stored;
+ *             TO_FEED_ARGMAX  x_k = oneHot(c), c bit for bit what to_arg_max returns for the stored row prev_k (earliest
+ *                             index on ties);
+ *             TO_FEED_SAMPLE  inverse CDF with the caller's uniforms U, a contiguous [B; G] of X's dtype and batch (to_rand
+ *                             makes one).  In the row's dtype and sequentially: c_0 = p_0, c_j = c_{j-1} + p_j,
+ *                             thr = U[b, k] * c_{n-1}; the symbol is the number of j with c_j <= thr, at most n - 1.  The
+ *                             order and the dtype of these operations are part of the contract: a sequential restatement
+ *                             (numpy's cumsum) gives the same symbol from the same stored row.
+ *             U is required for TO_FEED_SAMPLE and must be null otherwise (TO_ERR_ARG both ways).
+ *   symbols_or_null  host int64[B * G]: symbols[b * G + k] is the index fed at generated step k; the one-hot modes only (with
+ *             TO_FEED_OUTPUT it must be null, TO_ERR_ARG).
+ *   s_out_or_null[l]  the state after Tp + G steps, a contiguous [B; n_l]: valid as s of a following call.
+ * An output that overlaps an input, a parameter or another output is TO_ERR_ARG.  fp32 or fp64, any B, Tp, G and widths:
+ * never TO_ERR_UNSUPPORTED for a valid stack.  Pending operands are produced first; refused during graph capture
+ * (TO_ERR_STATE); every refusal is decided before the first launch and leaves all outputs untouched; blocks before
+ * returning; keeps no handle.
+ * Routes.  The generated steps are a dependent chain.  Per step (A): the prime is to_rnn_stack_run's forward on X (its
+ * routes, to_set_rnn_persistent), then per generated step one feed launch (csrc/rnn_generate.hip) and that forward with
+ * T = 1 on the carried states -- a generated step's values are bit for bit those of to_rnn_stack_run with T = 1 on the fed
+ * rows and the carried (batched) states; takes every stack, launches grow with G.  Persistent (B, rnn_gen_kernel): the
+ * prime and all G steps of all rows in ONE launch, every layer's W, W' and b in LDS, a workgroup owning whole sequences and
+ * the whole stack; the launch count depends neither on Tp nor on G.  The prime runs in the kernel too, so that on either
+ * route cutting a generation into two calls (G = a, then one prime row fed from g_{a-1} with the first call's s_out and
+ * G = b - 1) gives the bits of the one call with G = a + b.  Its range: 1..8 layers, fp32 and fp64, and the parameters plus
+ * one sequence's rows within 160 KiB of LDS -- fp32 64 -> 128 (stateful) -> 64 (129 KiB of parameters) fits, 64 -> 160
+ * (stateful) -> 64 (181 KiB) and fp64 64 -> 128 -> 64 (258 KiB) do not and take route A.  Both routes use one definition of
+ * the feed rule; on either a row's bits depend neither on B nor on the row's place in the batch; the two routes agree to
+ * rounding, not bit for bit.  to_set_rnn_generate_persistent: 0 route A; 1 automatic (default): route B where its plan fits
+ * AND the batch fits 256 workgroups with at most four (row, column) items of the widest layer a thread -- B <= 2048 for
+ * fp32 64 -> 128 -> 64, every B up to 4096 for 5 -> 7 -> 5 --, route A beyond: measured by tools/rnn_generate_scan.py
+ * (profiles/rnn_generate_scan.txt; logistic states and a stateless output layer only); 2 route B
+ * wherever its plan fits.  Process-wide.  to_rnn_generate_stats counts calls by the route that ran the generated steps. */
+enum { TO_FEED_OUTPUT = 0, TO_FEED_ARGMAX = 1, TO_FEED_SAMPLE = 2 };
+to_status to_rnn_stack_generate(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
+                                const to_tensor* b, int hidden_act, int out_act, int feed,
+                                to_tensor X, to_tensor U_or_null, int64_t G,
+                                to_tensor prime_out_or_null, to_tensor out, int64_t* symbols_or_null,
+                                const to_tensor* s_out_or_null);
+to_status to_set_rnn_generate_persistent(int on, int* previous_or_null);   /* 0 per step, 1 automatic, 2 wherever in range */
+to_status to_rnn_generate_stats(int64_t* persistent_runs, int64_t* per_step_runs);
+
 /* `induceNetwork` (FeedForward.hs:150-164) of the same ffLayer stacks, iterated: gradient descent on the INPUT with the
  * parameters fixed (app/MNIST.hs:357-365 runs 5000 such steps in a row), for every row of the hidden batch, in ONE call:
  *   x_0 = x[r];   g_k = d/dx loss(net(x_k), y[r]);   x_{k+1} = x_k - rate * g_k,   k = 0 .. iters-1

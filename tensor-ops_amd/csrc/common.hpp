@@ -488,6 +488,41 @@ struct RnnSeqPlan {
 bool rnn_seq_plan(int dtype, int64_t H, int64_t B, RnnSeqPlan* p);
 void launch_rnn_seq(int dtype, bool reverse, const RnnSeqPlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T,
                     int64_t H, int act_kind, hipStream_t s);
+// rnn_generate.hip: closed-loop generation (to_rnn_stack_generate).  The feed rule -- the next input row from the stored
+// previous output row -- has ONE definition there, used by both routes: feed_kernel (route A, one launch a generated step:
+// x [B][n] from prev [B][n], the symbol of row r into sym[r * G + k]) and rnn_gen_kernel (route B: the prime and all G steps of all
+// rows and the whole stack in one launch, the parameters in LDS).  feed: TO_FEED_* of the public header.
+constexpr int RNN_GEN_MAX_LAYERS = 8;
+struct RnnGenPlan {
+  int R = 1;          // sequences per workgroup
+  int wpad = 0;       // row stride of the activation buffers in LDS (elements; odd)
+  int64_t grid = 0;   // workgroups
+  size_t lds = 0;     // dynamic LDS bytes
+  bool few_items = false;  // at most 256 workgroups, and no thread with more than four items of the widest layer a step
+};
+struct RnnGenOperands {
+  int L = 0;
+  int64_t widths[RNN_GEN_MAX_LAYERS + 1] = {};  // i, n_1 .. n_L
+  int state_kind[RNN_GEN_MAX_LAYERS] = {};      // ACT_KIND_* of a stateful layer's state, -1: stateless
+  const void *W[RNN_GEN_MAX_LAYERS] = {}, *WS[RNN_GEN_MAX_LAYERS] = {}, *b[RNN_GEN_MAX_LAYERS] = {};
+  const void* s_in[RNN_GEN_MAX_LAYERS] = {};    // the initial states: element (b, j) at b * s_sb[l] + j * s_ss[l]
+  int64_t s_sb[RNN_GEN_MAX_LAYERS] = {}, s_ss[RNN_GEN_MAX_LAYERS] = {};
+  void* s_out[RNN_GEN_MAX_LAYERS] = {};         // [B][n_l] contiguous (optional): the states after the last step
+  const void* X = nullptr;                      // the prime: element (b, t, j) at b * x_sb + t * x_st + j * x_sj
+  int64_t x_sb = 0, x_st = 0, x_sj = 1;
+  void* prime_out = nullptr;                    // [B][Tp][n_L] (optional)
+  const void* U = nullptr;                      // [B][G] (TO_FEED_SAMPLE)
+  void* out = nullptr;                          // [B][G][n_L]
+  long long* sym = nullptr;                     // [B][G] (the one-hot modes)
+  int64_t B = 0, Tp = 0, G = 0;
+  int hidden_kind = 0, feed = 0;
+  bool softmax = true;
+};
+// widths: i, n_1 .. n_L; stateful[l] != 0: layer l carries a state.  False: no plan with R >= 1 fits the LDS (or L is too large)
+bool rnn_gen_plan(int dtype, int L, const int64_t* widths, const int* stateful, int64_t B, RnnGenPlan* p);
+void launch_rnn_gen(int dtype, const RnnGenPlan& p, const RnnGenOperands& o, hipStream_t s);
+void launch_rnn_feed(int dtype, const void* prev, int64_t B, int64_t n, int feed, const void* U, int64_t G, int64_t k, void* x,
+                     long long* sym, hipStream_t s);
 // induce_seq.hip: every iteration of `induceNetwork` on every row in one launch (to_fflayer_stack_induce, route B).
 // X [B][i0] contiguous: x_0 on entry, x_iters on exit; gx [B][i0] (optional) the last iteration's gradient; losses
 // [B][iters] (optional).  A plan with G > 1 may only be launched where online_sgd_placement_ok() holds.

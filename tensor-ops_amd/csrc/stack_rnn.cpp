@@ -7,6 +7,8 @@
 // S are the two offset views St[0..T) and St[1..T] of one buffer.  What is left is each stateful layer's recurrence:
 // persistent (rnn_seq.hip, one launch per layer and direction for all T steps) or per step (one GEMM with the addend,
 // plus one elementwise launch).  The caller's [B; T, .] rows are moved to and from time-major by one strided copy each.
+#include <memory>
+
 #include "api_util.hpp"
 #include "stack_util.hpp"
 
@@ -39,6 +41,104 @@ struct RnnStackArgs {  // what the three entries hand to rnn_stack_impl; each fi
   const to_tensor *s_out = nullptr, *gs = nullptr, *gws = nullptr, *gw = nullptr, *gb = nullptr;
   double rate_state = 0.0, rate_params = 0.0;
 };
+
+// The forward of a stack over T time-major steps of B sequences, shared by rnn_stack_impl (all T steps of X) and
+// to_rnn_stack_generate (the prime; on its per-step route each generated step with T = 1).
+struct RnnStateSrc {  // where a stateful layer's initial states are: one [n] for every sequence, or [B][n] (bstride apart)
+  const void* ptr = nullptr;
+  bool batched = false;
+  int64_t bstride = 0, stride = 1;
+};
+struct RnnForward {  // what the forward leaves behind
+  std::vector<Holder> Z, St, WT, Ah;   // per layer: z [T*B][n]; states [(T+1)*B][n], block 0 the initial ones; W'^T; hidden_act(z)
+  std::vector<const void*> outp;       // what the layer above reads: hidden_act(z_l), all rows
+  std::vector<RnnSeqPlan> plan;
+  std::vector<char> persist;
+  bool any_state = false, all_persistent = true;
+  const void* no_bias_for_head = nullptr;  // stateless last layer of a run: the head launch adds b_L
+  explicit RnnForward(int n) : Z(n), St(n), WT(n), Ah(n), outp(n, nullptr), plan(n), persist(n, 0) {}
+};
+
+static void rnn_forward(int dt, int n_layers, const int* state_act, const RnnStateSrc* init, const to_tensor* ws,
+                        const to_tensor* w, const to_tensor* b, int hk, bool run, const void* Xt, int64_t in_n, int64_t T,
+                        int64_t B, RnnForward& f) {
+  const int64_t rows = T * B, es = dt == TO_F64 ? 8 : 4;
+  auto state_kind = [&](int l) { return state_act[l] == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC; };
+  std::vector<Holder>&Z = f.Z, &St = f.St, &WT = f.WT, &Ah = f.Ah;
+  const void* prev = Xt;
+  int64_t prev_n = in_n;
+  for (int l = 0; l < n_layers; ++l) {
+    const int64_t n = w[l]->dims[0];
+    const bool last = l + 1 == n_layers, stateful = state_act[l] != TO_RNN_STATELESS;
+    const int64_t d2[2] = {rows, n};
+    Z[l].t = new_tensor(2, d2, 0, dt);
+    // the input projection (stateless hidden layer: its activation) over all rows
+    GemmProblem p = row_gemm(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, Z[l].t->ptr, rows, n, prev_n);
+    p.bias = b[l]->ptr;
+    if (!stateful && !last) p.act = hk + 1;
+    if (last && !stateful && run) { p.bias = nullptr; f.no_bias_for_head = b[l]->ptr; }
+    gemm_with_epilogue(p);
+    if (stateful) {
+      f.any_state = true;
+      const int64_t d3[2] = {(T + 1) * B, n};
+      St[l].t = new_tensor(2, d3, 0, dt);
+      void* st = St[l].t->ptr;
+      if (!init[l].batched) {
+        launch_bcast_axis(dt, init[l].ptr, st, 1, B, n, 0, S());
+      } else {
+        const int64_t dd[2] = {B, n}, ss[2] = {init[l].bstride, init[l].stride};
+        launch_copy_strided(dt, init[l].ptr, st, 2, dd, ss, S());
+      }
+      f.persist[l] = rnn_persistent_for(dt, n, B, &f.plan[l]);
+      f.all_persistent = f.all_persistent && f.persist[l];
+      void* z = Z[l].t->ptr;
+      if (f.persist[l]) {
+        const int64_t dd[2] = {n, n}, ss[2] = {1, n};  // W'^T: M[k][j] = W'[j][k]
+        WT[l].t = new_tensor(2, dd, 0, dt);
+        launch_copy_strided(dt, ws[l]->ptr, WT[l].t->ptr, 2, dd, ss, S());
+        launch_rnn_seq(dt, false, f.plan[l], WT[l].t->ptr, z, st, B, T, n, state_kind(l), S());
+      } else {
+        for (int64_t t = 0; t < T; ++t) {  // z_t = P_t + s_{t-1} W'^T (in place), s_t = state_act(z_t)
+          GemmProblem q = row_gemm(dt, at(st, t * B * n, es), n, 1, ws[l]->ptr, 1, n, at(z, t * B * n, es), B, n, n);
+          q.beta = 1.0;
+          q.Cin = q.C;
+          gemm_with_epilogue(q);
+          ew2(dt, state_kind(l) == ACT_KIND_TANH ? EW_TANH : EW_LOGISTIC, at(st, (t + 1) * B * n, es), at(z, t * B * n, es), nullptr,
+              B * n);
+        }
+      }
+    }
+    // what the layer above reads: a hidden stateful layer's output hidden_act(z) IS its state when the two activations
+    // are the same function; otherwise it is one more elementwise pass over all rows of z
+    if (stateful && !last && state_kind(l) == hk) {
+      prev = at(St[l].t->ptr, B * n, es);
+    } else if (stateful && !last) {
+      Ah[l].t = new_tensor(2, d2, 0, dt);
+      ew2(dt, hk == ACT_KIND_TANH ? EW_TANH : EW_LOGISTIC, Ah[l].t->ptr, Z[l].t->ptr, nullptr, rows * n);
+      prev = Ah[l].t->ptr;
+    } else {
+      prev = Z[l].t->ptr;
+    }
+    f.outp[l] = prev;
+    prev_n = n;
+  }
+}
+
+// out_act(z_L (+ b_L where the forward left it to the head)) of all `rows` rows into ot [rows][n_L]
+// (zb holds the zero bias: the caller keeps it until the stream has run)
+static void rnn_head_rows(int dt, const RnnForward& f, int n_layers, int64_t nL, int64_t rows, int out_act, void* ot,
+                          Holder& zb) {
+  const void* bias = f.no_bias_for_head;
+  if (!bias) {
+    if (!zb.t) {
+      zb.t = new_tensor(1, &nL, 0, dt);
+      launch_fill(dt, zb.t->ptr, nL, 0.0, S());
+    }
+    bias = zb.t->ptr;
+  }
+  launch_infer_rows(dt, f.Z[n_layers - 1].t->ptr, rows, bias, (int)nL, out_act == TO_ACT_SOFTMAX, ot, nullptr, 0, nullptr,
+                    nullptr, S());
+}
 
 static void rnn_stack_impl(const RnnStackArgs& a) {
   const bool run = a.mode == RnnMode::Run, grad = a.mode == RnnMode::Grad, sgd = a.mode == RnnMode::Sgd;
@@ -170,69 +270,16 @@ static void rnn_stack_impl(const RnnStackArgs& a) {
   const void* Yt = !run ? to_time_major(Y, yh) : nullptr;
 
   // ---- forward -------------------------------------------------------------------------------------------------------
-  std::vector<Holder> Z(n_layers), St(n_layers), WT(n_layers), Ah(n_layers);
-  std::vector<const void*> outp(n_layers, nullptr);   // what the layer above reads: hidden_act(z_l), all rows
-  std::vector<RnnSeqPlan> plan(n_layers);
-  std::vector<char> persist(n_layers, 0);
-  bool any_state = false, all_persistent = true;
-  const void* prev = Xt;
-  int64_t prev_n = X->dims[1];
-  const void* no_bias_for_head = nullptr;  // run, stateless last layer: the head launch adds b_L
-  for (int l = 0; l < n_layers; ++l) {
-    const int64_t n = w[l]->dims[0];
-    const bool last = l + 1 == n_layers, stateful = state_act[l] != TO_RNN_STATELESS;
-    const int64_t d2[2] = {rows, n};
-    Z[l].t = new_tensor(2, d2, 0, dt);
-    // the input projection (stateless hidden layer: its activation) over all rows
-    GemmProblem p = row_gemm(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, Z[l].t->ptr, rows, n, prev_n);
-    p.bias = b[l]->ptr;
-    if (!stateful && !last) p.act = hk + 1;
-    if (last && !stateful && run) { p.bias = nullptr; no_bias_for_head = b[l]->ptr; }
-    gemm_with_epilogue(p);
-    if (stateful) {
-      any_state = true;
-      const int64_t d3[2] = {(T + 1) * B, n};
-      St[l].t = new_tensor(2, d3, 0, dt);
-      void* st = St[l].t->ptr;
-      if (s[l]->batch == 0) {
-        launch_bcast_axis(dt, s[l]->ptr, st, 1, B, n, 0, S());
-      } else {
-        const int64_t dd[2] = {B, n}, ss[2] = {s[l]->bstride, s[l]->strides[0]};
-        launch_copy_strided(dt, s[l]->ptr, st, 2, dd, ss, S());
-      }
-      persist[l] = rnn_persistent_for(dt, n, B, &plan[l]);
-      all_persistent = all_persistent && persist[l];
-      void* z = Z[l].t->ptr;
-      if (persist[l]) {
-        const int64_t dd[2] = {n, n}, ss[2] = {1, n};  // W'^T: M[k][j] = W'[j][k]
-        WT[l].t = new_tensor(2, dd, 0, dt);
-        launch_copy_strided(dt, ws[l]->ptr, WT[l].t->ptr, 2, dd, ss, S());
-        launch_rnn_seq(dt, false, plan[l], WT[l].t->ptr, z, st, B, T, n, state_kind(l), S());
-      } else {
-        for (int64_t t = 0; t < T; ++t) {  // z_t = P_t + s_{t-1} W'^T (in place), s_t = state_act(z_t)
-          GemmProblem q = row_gemm(dt, at(st, t * B * n, es), n, 1, ws[l]->ptr, 1, n, at(z, t * B * n, es), B, n, n);
-          q.beta = 1.0;
-          q.Cin = q.C;
-          gemm_with_epilogue(q);
-          ew2(dt, state_kind(l) == ACT_KIND_TANH ? EW_TANH : EW_LOGISTIC, at(st, (t + 1) * B * n, es), at(z, t * B * n, es), nullptr,
-              B * n);
-        }
-      }
-    }
-    // what the layer above reads: a hidden stateful layer's output hidden_act(z) IS its state when the two activations
-    // are the same function; otherwise it is one more elementwise pass over all rows of z
-    if (stateful && !last && state_kind(l) == hk) {
-      prev = at(St[l].t->ptr, B * n, es);
-    } else if (stateful && !last) {
-      Ah[l].t = new_tensor(2, d2, 0, dt);
-      ew2(dt, hk == ACT_KIND_TANH ? EW_TANH : EW_LOGISTIC, Ah[l].t->ptr, Z[l].t->ptr, nullptr, rows * n);
-      prev = Ah[l].t->ptr;
-    } else {
-      prev = Z[l].t->ptr;
-    }
-    outp[l] = prev;
-    prev_n = n;
-  }
+  std::vector<RnnStateSrc> init(n_layers);
+  for (int l = 0; l < n_layers; ++l)
+    if (s[l]) init[l] = {s[l]->ptr, s[l]->batch != 0, s[l]->bstride, s[l]->strides[0]};
+  RnnForward f(n_layers);
+  rnn_forward(dt, n_layers, state_act, init.data(), ws, w, b, hk, run, Xt, X->dims[1], T, B, f);
+  std::vector<Holder>&Z = f.Z, &St = f.St;
+  const std::vector<const void*>& outp = f.outp;
+  const std::vector<RnnSeqPlan>& plan = f.plan;
+  const std::vector<char>& persist = f.persist;
+  const bool any_state = f.any_state, all_persistent = f.all_persistent;
   if (any_state) (all_persistent ? g_rnn_persistent_runs : g_rnn_stepwise_runs)++;
   const int L = n_layers - 1;
   if (run) {
@@ -242,16 +289,9 @@ static void rnn_stack_impl(const RnnStackArgs& a) {
           TO_HIP(hipMemcpyAsync(s_out[l]->ptr, at(St[l].t->ptr, T * B * w[l]->dims[0], es), (size_t)(B * w[l]->dims[0] * es),
                                 hipMemcpyDeviceToDevice, S()));
     Holder oh, zb;
-    const void* bias = no_bias_for_head;
-    if (!bias) {
-      zb.t = new_tensor(1, &nL, 0, dt);
-      launch_fill(dt, zb.t->ptr, nL, 0.0, S());
-      bias = zb.t->ptr;
-    }
     TO_CHECK(nL <= 2147483647LL, TO_ERR_SHAPE, F + "output layer too wide");
     void* ot = scratch_or(out, nL, oh);
-    launch_infer_rows(dt, Z[L].t->ptr, rows, bias, (int)nL, out_act == TO_ACT_SOFTMAX, ot, nullptr, 0, nullptr, nullptr,
-                      S());
+    rnn_head_rows(dt, f, n_layers, nL, rows, out_act, ot, zb);
     from_time_major(ot, out, nL);
     TO_HIP(hipStreamSynchronize(S()));
     return;
@@ -387,6 +427,240 @@ to_status to_rnn_stack_sgd(int n_layers, const int* state_act, const to_tensor* 
   RnnStackArgs a{RnnMode::Sgd, n_layers, state_act, s, ws, w, b, hidden_act, out_act, X, loss, Y};
   a.losses = losses_or_null; a.rate_state = rate_state; a.rate_params = rate_params;
   rnn_stack_impl(a);
+  API_END
+}
+
+// ---- closed-loop generation: `runNetworkSt` under `iterate` as one call ---------------------------------------------------
+// A generated step's input does not exist before the step before has finished, so the generated steps are a chain.  Per
+// step (route A): the prime is the forward above on X, then per generated step one feed launch and that forward with T = 1
+// on the carried states.  Persistent (route B, rnn_generate.hip): the prime and all G steps of all rows in ONE launch, the
+// whole stack in LDS -- the prime too, so that a call's values do not depend on where a sequence is cut into calls.
+static int g_rnn_generate_persistent = 1;   // to_set_rnn_generate_persistent: 0 per step, 1 auto, 2 wherever in range
+static int64_t g_rnn_generate_persistent_runs = 0, g_rnn_generate_step_runs = 0;
+
+static bool gen_overlap(to_tensor s, to_tensor t) {
+  if (!s || !t || !s->ptr || !t->ptr) return false;   // (a handle without storage yet shares none)
+  auto end = [](to_tensor u) {
+    int64_t last = u->batch > 1 ? (u->batch - 1) * u->bstride : 0;
+    for (int d = 0; d < u->rank; ++d) last += (u->dims[d] - 1) * u->strides[d];
+    return static_cast<const char*>(u->ptr) + (last + 1) * (int64_t)u->esize();
+  };
+  return static_cast<const char*>(s->ptr) < end(t) && static_cast<const char*>(t->ptr) < end(s);
+}
+
+to_status to_rnn_stack_generate(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
+                                const to_tensor* b, int hidden_act, int out_act, int feed, to_tensor X, to_tensor U_or_null,
+                                int64_t G, to_tensor prime_out_or_null, to_tensor out, int64_t* symbols_or_null,
+                                const to_tensor* s_out_or_null) {
+  API_BEGIN
+  const char* fn = "to_rnn_stack_generate";
+  const std::string F = std::string(fn) + ": ";
+  const to_tensor U = U_or_null, prime_out = prime_out_or_null;
+  const to_tensor* s_out = s_out_or_null;
+  require_init();
+  no_capture(fn);
+  NONNULL(state_act); NONNULL(s); NONNULL(ws); NONNULL(w); NONNULL(b); NONNULL(X); NONNULL(out);
+  TO_CHECK(n_layers >= 1, TO_ERR_ARG, F + "need at least one layer");
+  for (int l = 0; l < n_layers; ++l)
+    TO_CHECK(state_act[l] == TO_ACT_LOGISTIC || state_act[l] == TO_ACT_TANH || state_act[l] == TO_RNN_STATELESS,
+             TO_ERR_UNSUPPORTED,
+             F + "layer " + std::to_string(l) + ": the state activation must be logistic or tanh (or TO_RNN_STATELESS)");
+  const int hk = stack_hidden_act_check(hidden_act);
+  TO_CHECK(out_act == TO_ACT_SOFTMAX || out_act == TO_ACT_LOGISTIC, TO_ERR_UNSUPPORTED,
+           F + "the output activation must be softmax or logistic");
+  TO_CHECK(feed == TO_FEED_OUTPUT || feed == TO_FEED_ARGMAX || feed == TO_FEED_SAMPLE, TO_ERR_ARG,
+           F + "feed must be TO_FEED_OUTPUT, TO_FEED_ARGMAX or TO_FEED_SAMPLE");
+  TO_CHECK(G >= 1, TO_ERR_ARG, F + "G must be at least 1");
+  TO_CHECK((feed == TO_FEED_SAMPLE) == (U != nullptr), TO_ERR_ARG,
+           F + "U is required for TO_FEED_SAMPLE and must be null otherwise");
+  TO_CHECK(feed != TO_FEED_OUTPUT || !symbols_or_null, TO_ERR_ARG, F + "TO_FEED_OUTPUT feeds no symbol: symbols must be null");
+  const int dt = X->dtype;
+  TO_CHECK(X->rank == 2 && X->dims[0] >= 1 && X->dims[1] >= 1, TO_ERR_SHAPE,
+           F + "X must be [B; Tp, i] (or [Tp, i]), got " + shape_str(X));
+  const int64_t Tp = X->dims[0], B = X->batch > 0 ? X->batch : 1, in_n = X->dims[1];
+  const int64_t nL = stack_params_check(n_layers, w, b, nullptr, nullptr, dt, in_n);
+  TO_CHECK(nL == in_n, TO_ERR_SHAPE,
+           F + "the output is fed back as the input: n_L = " + std::to_string(nL) + " but i = " + std::to_string(in_n));
+  TO_CHECK(nL <= 2147483647LL, TO_ERR_SHAPE, F + "output layer too wide");
+  for (int l = 0; l < n_layers; ++l) {
+    const int64_t n = w[l]->dims[0];
+    const std::string L = F + "layer " + std::to_string(l) + ": ";
+    if (state_act[l] == TO_RNN_STATELESS) {
+      TO_CHECK(!s[l] && !ws[l], TO_ERR_ARG, L + "a stateless layer has no state and no W'");
+      if (s_out) TO_CHECK(!s_out[l], TO_ERR_ARG, L + "a stateless layer has no final state");
+      continue;
+    }
+    NONNULL(s[l]); NONNULL(ws[l]);
+    TO_CHECK(s[l]->dtype == dt && ws[l]->dtype == dt, TO_ERR_ARG, L + "states, parameters and data must share one dtype");
+    TO_CHECK(ws[l]->rank == 2 && ws[l]->batch == 0 && ws[l]->dims[0] == n && ws[l]->dims[1] == n && ws[l]->contiguous(),
+             TO_ERR_SHAPE, L + "W' has shape " + shape_str(ws[l]));
+    TO_CHECK(s[l]->rank == 1 && s[l]->dims[0] == n, TO_ERR_SHAPE, L + "s has shape " + shape_str(s[l]));
+    TO_CHECK(s[l]->batch == 0 || s[l]->batch == X->batch, TO_ERR_SHAPE,
+             L + "s must be unbatched or of X's batch, got " + shape_str(s[l]));
+    if (s_out && s_out[l]) {
+      TO_CHECK(s_out[l]->dtype == dt, TO_ERR_ARG, L + "s_out and X have different dtypes");
+      TO_CHECK(s_out[l]->rank == 1 && s_out[l]->dims[0] == n && s_out[l]->batch == X->batch && s_out[l]->contiguous(),
+               TO_ERR_SHAPE, L + "s_out must be a contiguous [B; n] of X's batch, got " + shape_str(s_out[l]));
+    }
+  }
+  auto seq_like = [&](to_tensor t, int64_t len, const char* what) {  // a contiguous [B; len, n_L] of X's batch and dtype
+    TO_CHECK(t->dtype == dt, TO_ERR_ARG, F + what + " and X have different dtypes");
+    TO_CHECK(t->rank == 2 && t->dims[0] == len && t->dims[1] == nL && t->batch == X->batch, TO_ERR_SHAPE,
+             F + what + " must be [B; " + std::to_string(len) + ", " + std::to_string(nL) + "] of X's batch, got " + shape_str(t));
+    TO_CHECK(t->contiguous(), TO_ERR_ARG, F + what + " must be contiguous");
+  };
+  seq_like(out, G, "out");
+  if (prime_out) seq_like(prime_out, Tp, "prime_out");
+  if (U) {
+    TO_CHECK(U->dtype == dt, TO_ERR_ARG, F + "U and X have different dtypes");
+    TO_CHECK(U->rank == 1 && U->dims[0] == G && U->batch == X->batch, TO_ERR_SHAPE,
+             F + "U must be [B; " + std::to_string(G) + "] of X's batch, got " + shape_str(U));
+    TO_CHECK(U->contiguous(), TO_ERR_ARG, F + "U must be contiguous");
+  }
+  TO_CHECK(Tp * B <= 2147483647LL && G * B <= 2147483647LL, TO_ERR_SHAPE, F + "more than 2^31-1 rows");
+  {  // an output may overlap neither an input, nor a parameter, nor another output
+    std::vector<to_tensor> outs{out, prime_out}, ins{X, U};
+    for (int l = 0; l < n_layers; ++l) {
+      if (s_out) outs.push_back(s_out[l]);
+      ins.push_back(s[l]); ins.push_back(ws[l]); ins.push_back(w[l]); ins.push_back(b[l]);
+    }
+    for (size_t o = 0; o < outs.size(); ++o) {
+      bool bad = false;
+      for (to_tensor in : ins) bad = bad || gen_overlap(outs[o], in);
+      for (size_t q = 0; q < o; ++q) bad = bad || gen_overlap(outs[o], outs[q]);
+      TO_CHECK(!bad, TO_ERR_ARG, F + "an output overlaps an input, a parameter or another output");
+    }
+  }
+  // The route.  The automatic rule is set from tools/rnn_generate_scan.py's table (profiles/rnn_generate_scan.txt, DESIGN.md
+  // section 3.3): the persistent kernel is ahead of route A -- 1.6x to 5x -- wherever the batch fits 256 workgroups with at
+  // most four (row, column) items of the widest layer a thread (fp32 64 -> 128 -> 64: up to B = 2048), and 1.5x behind it at
+  // eight items a thread (B = 4096): plain FMAs from LDS then lose to the per-step route's GEMMs.  Five to seven items: not
+  // measured, route A.
+  RnnGenPlan gplan;
+  bool persistent = false;
+  if (g_rnn_generate_persistent != 0 && n_layers <= RNN_GEN_MAX_LAYERS) {
+    int64_t widths[RNN_GEN_MAX_LAYERS + 1] = {in_n};
+    int stateful[RNN_GEN_MAX_LAYERS] = {};
+    for (int l = 0; l < n_layers; ++l) {
+      widths[l + 1] = w[l]->dims[0];
+      stateful[l] = state_act[l] != TO_RNN_STATELESS;
+    }
+    persistent = rnn_gen_plan(dt, n_layers, widths, stateful, B, &gplan) && (g_rnn_generate_persistent == 2 || gplan.few_items);
+  }
+
+  // ---- operands produced; destinations claimed -------------------------------------------------------------------
+  ensure(X);
+  if (U) ensure(U);
+  for (int l = 0; l < n_layers; ++l) {
+    ensure(w[l]); ensure(b[l]);
+    if (s[l]) { ensure(s[l]); ensure(ws[l]); }
+  }
+  claim(out);
+  if (prime_out) claim(prime_out);
+  if (s_out) for (int l = 0; l < n_layers; ++l) if (s_out[l]) claim(s_out[l]);
+
+  const int64_t es = dt == TO_F64 ? 8 : 4;
+  auto scratch = [&](int64_t rows, int64_t n, Holder& h) -> void* {
+    const int64_t d2[2] = {rows, n};
+    h.t = new_tensor(2, d2, 0, dt);
+    return h.t->ptr;
+  };
+  // time-major [T][B][n] -> the caller's contiguous [B; T, n]
+  auto from_time_major = [&](const void* src, to_tensor dst, int64_t T) {
+    if (src == dst->ptr) return;
+    const int64_t d3[3] = {B, T, nL}, s3[3] = {nL, B * nL, 1};
+    launch_copy_strided(dt, src, dst->ptr, 3, d3, s3, S());
+  };
+  Holder symh;
+  long long* sym = nullptr;
+  if (feed != TO_FEED_OUTPUT) {
+    const int64_t nl = (B * G * 8 + 3) / 4;  // B * G int64 in a float-typed pool buffer
+    symh.t = new_tensor(1, &nl, 0);
+    sym = reinterpret_cast<long long*>(symh.t->ptr);
+  }
+  Holder xh, ph, zb, xg, og;
+  std::unique_ptr<RnnForward> cur;
+  if (persistent) {
+    // ---- route B: the prime and every generated step in one launch; the states, X and the outputs where the caller has them --
+    RnnGenOperands o;
+    o.L = n_layers;
+    o.widths[0] = in_n;
+    for (int l = 0; l < n_layers; ++l) {
+      o.widths[l + 1] = w[l]->dims[0];
+      o.state_kind[l] = !s[l] ? -1 : state_act[l] == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC;
+      o.W[l] = w[l]->ptr; o.b[l] = b[l]->ptr;
+      if (s[l]) {
+        o.WS[l] = ws[l]->ptr;
+        o.s_in[l] = s[l]->ptr;
+        o.s_sb[l] = s[l]->batch > 0 ? s[l]->bstride : 0;
+        o.s_ss[l] = s[l]->strides[0];
+        o.s_out[l] = s_out && s_out[l] ? s_out[l]->ptr : nullptr;
+      }
+    }
+    o.X = X->ptr; o.x_sb = X->batch > 0 ? X->bstride : 0; o.x_st = X->strides[0]; o.x_sj = X->strides[1];
+    o.prime_out = prime_out ? prime_out->ptr : nullptr;
+    o.U = U ? U->ptr : nullptr; o.out = out->ptr; o.sym = sym;
+    o.B = B; o.Tp = Tp; o.G = G; o.hidden_kind = hk; o.feed = feed; o.softmax = out_act == TO_ACT_SOFTMAX;
+    launch_rnn_gen(dt, gplan, o, S());
+    g_rnn_generate_persistent_runs++;
+  } else {
+    // ---- route A.  The prime: X [B; Tp, i] time-major, the forward, the head -------------------------------------------
+    const void* Xt = X->ptr;
+    if (!(B == 1 && X->contiguous())) {
+      const int64_t d3[3] = {Tp, B, in_n}, s3[3] = {X->strides[0], X->batch > 0 ? X->bstride : 0, X->strides[1]};
+      Xt = scratch(Tp * B, in_n, xh);
+      launch_copy_strided(dt, X->ptr, xh.t->ptr, 3, d3, s3, S());
+    }
+    std::vector<RnnStateSrc> init(n_layers);
+    for (int l = 0; l < n_layers; ++l)
+      if (s[l]) init[l] = {s[l]->ptr, s[l]->batch != 0, s[l]->bstride, s[l]->strides[0]};
+    cur.reset(new RnnForward(n_layers));
+    rnn_forward(dt, n_layers, state_act, init.data(), ws, w, b, hk, true, Xt, in_n, Tp, B, *cur);
+    void* pt = prime_out && B == 1 ? prime_out->ptr : scratch(Tp * B, nL, ph);
+    rnn_head_rows(dt, *cur, n_layers, nL, Tp * B, out_act, pt, zb);
+    if (prime_out) from_time_major(pt, prime_out, Tp);
+    const void* prev = at(pt, (Tp - 1) * B * nL, es);   // the last prime step's rows [B][n_L]
+    for (int l = 0; l < n_layers; ++l)   // the carried states: block Tp of the prime's St, [B][n_l]
+      if (s[l]) init[l] = {at(cur->St[l].t->ptr, Tp * B * w[l]->dims[0], es), true, w[l]->dims[0], 1};
+    // per generated step one feed launch, then the forward with T = 1 on the carried states
+    void* x = scratch(B, in_n, xg);
+    void* ot = B == 1 ? out->ptr : scratch(G * B, nL, og);   // time-major [G][B][n_L]
+    for (int64_t k = 0; k < G; ++k) {
+      launch_rnn_feed(dt, prev, B, nL, feed, U ? U->ptr : nullptr, G, k, x, sym, S());
+      std::unique_ptr<RnnForward> nxt(new RnnForward(n_layers));
+      rnn_forward(dt, n_layers, state_act, init.data(), ws, w, b, hk, true, x, in_n, 1, B, *nxt);
+      void* row = at(ot, k * B * nL, es);
+      rnn_head_rows(dt, *nxt, n_layers, nL, B, out_act, row, zb);
+      prev = row;
+      for (int l = 0; l < n_layers; ++l)
+        if (s[l]) init[l].ptr = at(nxt->St[l].t->ptr, B * w[l]->dims[0], es);
+      cur = std::move(nxt);   // (the step before's buffers go back to the pool; the stream runs in order)
+    }
+    from_time_major(ot, out, G);
+    if (s_out)
+      for (int l = 0; l < n_layers; ++l)
+        if (s_out[l])
+          TO_HIP(hipMemcpyAsync(s_out[l]->ptr, init[l].ptr, (size_t)(B * w[l]->dims[0] * es), hipMemcpyDeviceToDevice, S()));
+    g_rnn_generate_step_runs++;
+  }
+  if (symbols_or_null) device_to_host(symbols_or_null, sym, (size_t)(B * G) * sizeof(int64_t), S());
+  TO_HIP(hipStreamSynchronize(S()));
+  API_END
+}
+
+to_status to_set_rnn_generate_persistent(int on, int* previous_or_null) {
+  API_BEGIN
+  TO_CHECK(on >= 0 && on <= 2, TO_ERR_ARG,
+           "to_set_rnn_generate_persistent: 0 (per step), 1 (automatic) or 2 (wherever in range)");
+  if (previous_or_null) *previous_or_null = g_rnn_generate_persistent;
+  g_rnn_generate_persistent = on;
+  API_END
+}
+
+to_status to_rnn_generate_stats(int64_t* persistent_runs, int64_t* per_step_runs) {
+  API_BEGIN
+  if (persistent_runs) *persistent_runs = g_rnn_generate_persistent_runs;
+  if (per_step_runs) *per_step_runs = g_rnn_generate_step_runs;
   API_END
 }
 

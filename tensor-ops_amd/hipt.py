@@ -657,6 +657,45 @@ class HipT:
         check(lib().to_rnn_stats(C.byref(p), C.byref(q)))
         return p.value, q.value
 
+    _RNN_FEED = {"output": 0, "argmax": 1, "sample": 2}
+
+    def rnn_stack_generate(self, layers, X, G, feed="output", U=None, out_act="softmax", hidden_act="logistic",
+                           want_prime_out=False, want_states=False):
+        """Closed-loop generation (to_rnn_stack_generate): prime the stack with X [B; Tp, i], then G steps each fed from
+        the step before's output -- as stored ("output"), its argMax one-hot ("argmax") or a symbol drawn by inverse CDF
+        with the uniforms U [B; G] ("sample").  Returns (out [B; G, n_L], symbols int64 [B, G] or None, prime_out
+        [B; Tp, n_L] or None, final states -- one per layer, None for a stateless one -- or None)"""
+        n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
+        Tp, _ = X.shape
+        batch = X.batch
+        nL = layers[-1][2].shape[0]
+        G = int(G)
+        out = self._alloc((max(G, 1), nL), batch)
+        prime = self._alloc((Tp, nL), batch) if want_prime_out else None
+        finals = [self._alloc((lay[2].shape[0],), batch) if (want_states and lay[0] is not None) else None for lay in layers]
+        s_out = (capi.c_tensor * n)(*[(f.h if f is not None else None) for f in finals]) if want_states else None
+        symbols = np.empty((max(batch, 1), max(G, 0)), dtype=np.int64) if feed != "output" else None
+        check(lib().to_rnn_stack_generate(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
+                                          self._RNN_FEED[feed], X.h, U.h if U is not None else None, G,
+                                          prime.h if prime is not None else None, out.h,
+                                          symbols.ctypes.data_as(C.POINTER(C.c_int64)) if symbols is not None else None,
+                                          s_out))
+        return out, symbols, prime, (finals if want_states else None)
+
+    @staticmethod
+    def rnn_generate_persistent(on):
+        """to_set_rnn_generate_persistent: 0 per step, 1 automatic, 2 wherever in range; returns the previous setting"""
+        prev = C.c_int()
+        check(lib().to_set_rnn_generate_persistent(int(on), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
+    def rnn_generate_stats():
+        """(persistent runs, per-step runs)"""
+        p, q = C.c_int64(), C.c_int64()
+        check(lib().to_rnn_generate_stats(C.byref(p), C.byref(q)))
+        return p.value, q.value
+
     # -- induceNetwork iterated (to_fflayer_stack_induce) ----------------------------------------
     def induce_stack(self, ws, bs, x, y, rate, iters, out_act="softmax", loss="crossEntropy", want_gx=False,
                      want_losses=False, in_place=False, hidden_act="logistic"):

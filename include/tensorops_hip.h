@@ -590,6 +590,49 @@ to_status to_rnn_stack_generate(int n_layers, const int* state_act, const to_ten
 to_status to_set_rnn_generate_persistent(int on, int* previous_or_null);   /* 0 per step, 1 automatic, 2 wherever in range */
 to_status to_rnn_generate_stats(int64_t* persistent_runs, int64_t* per_step_runs);
 
+/* Per-sequence training of the same stacks in ONE call: `trainNetwork'` (Recurrent.hs:356-371 takes ONE sequence [(x, y)]
+ * and returns the updated network) folded over a set of sequences.  For j = 0 .. n_idx-1, in order, with q = idx[j] (q = j
+ * when idx is null): one to_rnn_stack_sgd step on sequence q alone -- forward over T steps from the current initial states,
+ * BPTT of sum_t loss(out_t, Y_t), s -= rate_state gs and every parameter -= rate_params g, in place.  Step j + 1 sees step
+ * j's parameters and initial states; as in the reference the final state of a sequence is not carried, the learned initial
+ * state is.  The stack (state_act, s, ws, w, b), hidden_act, the (out_act, loss) pairs, the dtypes and the rule that initial
+ * states are unbatched and contiguous are to_rnn_stack_sgd's, with its statuses.
+ *   X               [N; T, i], batched and contiguous;  Y [N; T, n_L], same batch and dtype, contiguous (TO_ERR_SHAPE);
+ *   idx_or_null     host int64[n_idx], entries in [0, N), repeats allowed (TO_ERR_SHAPE out of range); null: sequences
+ *                   0 .. n_idx-1, n_idx <= N (TO_ERR_SHAPE).  n_idx >= 1 (TO_ERR_ARG).  The array may be reused on return;
+ *   losses_or_null  contiguous [n_idx; T] of X's dtype: losses[j][t] is the loss of sequence idx[j] at step t under the
+ *                   parameters step j started from.  It may overlap neither X, Y nor a parameter (TO_ERR_ARG).
+ * fp32 or fp64, any N, T >= 1 and widths: never TO_ERR_UNSUPPORTED for a valid stack.  Pending operands are produced first;
+ * refused during graph capture (TO_ERR_STATE); every refusal is decided before the first launch and leaves parameters,
+ * states and losses untouched; blocks before returning; keeps no handle.
+ * Routes.  Per sequence (A): per j, to_rnn_stack_sgd's own launches on the B = 1 views to_batch_select would give -- the
+ * parameters, states and losses are BIT FOR BIT those of the caller's loop of to_rnn_stack_sgd over to_batch_select views;
+ * takes every stack; launches, pool allocations and one synchronise per sequence.  Persistent (B, csrc/rnn_online.hip,
+ * rnn_online_kernel): all n_idx sequences in ONE launch by ONE workgroup (nothing crosses workgroups, the kernel waits on
+ * its own barriers only).  Every layer's W, W' and b and the initial states stay in LDS for the whole call -- matrices
+ * k-major with an odd leading dimension, read conflict-free by the forward (a thread a column) and by the backward's W^T dz
+ * and W'^T dz (a thread a k).  Only a stateful layer's own recurrence is serial in t (one barrier a step, forward and
+ * backward); input projections, hidden activations, the head, the cotangents between layers and the update are spread over
+ * all threads for all T steps at once.  Every sum has a fixed order (z: input part by ascending k, state part by ascending
+ * k, the bias; a gradient element: ascending t; no gradient buffer exists), so the result is deterministic and n_idx = a
+ * followed by n_idx = b from the first call's parameters gives the bits of the one call with a + b.  What the backward needs
+ * of the forward (the tape) is in LDS where it fits beside the parameters, else in a pool buffer; the launch count depends
+ * neither on n_idx nor on T and the range does not depend on T: 1..8 layers, fp32 and fp64, and the parameters, the states
+ * and a few rows within 160 KiB of LDS -- fp32 64 -> 128 (stateful) -> 64 (133 KiB) and 70 -> 130 (stateful) -> 3 (107 KiB)
+ * fit, fp64 70 -> 130 -> 3 (209 KiB of parameters) and fp32 64 -> 160 (stateful) -> 64 (182 KiB) do not and take route A.
+ * The two routes agree to rounding, not bit for bit.  to_set_rnn_online_persistent: 0 route A; 1 automatic (default): route B
+ * where its plan fits AND no layer (the input not counted) is wider than H* = 128, the largest width scanned: measured by
+ * tools/rnn_online_scan.py on fp32 64 -> H (stateful) -> 10 over 256 sequences, route B was ahead of route A at H = 32, 64,
+ * 96 and 128 at both T = 8 and T = 64 (profiles/rnn_online_scan.txt; logistic states, one tanh row at
+ * H = 64); wider layers that still fit have NOT been measured and take route A; 2 route B wherever its plan fits.
+ * Process-wide.  to_rnn_online_stats counts calls by the route that ran them. */
+to_status to_rnn_stack_online_sgd(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
+                                  const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
+                                  int64_t n_idx, const int64_t* idx_or_null, double rate_state, double rate_params,
+                                  to_tensor losses_or_null);
+to_status to_set_rnn_online_persistent(int on, int* previous_or_null);   /* 0 per sequence, 1 automatic, 2 wherever in range */
+to_status to_rnn_online_stats(int64_t* persistent_runs, int64_t* per_sequence_runs);
+
 /* `induceNetwork` (FeedForward.hs:150-164) of the same ffLayer stacks, iterated: gradient descent on the INPUT with the
  * parameters fixed (app/MNIST.hs:357-365 runs 5000 such steps in a row), for every row of the hidden batch, in ONE call:
  *   x_0 = x[r];   g_k = d/dx loss(net(x_k), y[r]);   x_{k+1} = x_k - rate * g_k,   k = 0 .. iters-1

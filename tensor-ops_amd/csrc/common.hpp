@@ -523,6 +523,39 @@ bool rnn_gen_plan(int dtype, int L, const int64_t* widths, const int* stateful, 
 void launch_rnn_gen(int dtype, const RnnGenPlan& p, const RnnGenOperands& o, hipStream_t s);
 void launch_rnn_feed(int dtype, const void* prev, int64_t B, int64_t n, int feed, const void* U, int64_t G, int64_t k, void* x,
                      long long* sym, hipStream_t s);
+constexpr size_t GEN_LDS_MAX = 160 * 1024;   // what a workgroup of rnn_gen_kernel / rnn_online_kernel may hold: the limit rnn_seq.hip and induce_seq.hip use
+// rnn_online.hip: per-sequence training (to_rnn_stack_online_sgd, route B) -- forward, BPTT and the update of n_idx
+// sequences, one after the other, in ONE launch by ONE workgroup that keeps the parameters and the learned initial states in
+// LDS.  The plan is the workgroup's LDS map (offsets in elements) and the layout of one step's tape record.
+struct RnnOnlinePlan {
+  int w_off[RNN_GEN_MAX_LAYERS] = {}, ws_off[RNN_GEN_MAX_LAYERS] = {}, b_off[RNN_GEN_MAX_LAYERS] = {};
+  int s_off[RNN_GEN_MAX_LAYERS] = {}, sc_off[RNN_GEN_MAX_LAYERS] = {};   // the initial state; the current state, twice
+  int t_in[RNN_GEN_MAX_LAYERS] = {}, t_s[RNN_GEN_MAX_LAYERS] = {}, t_dz[RNN_GEN_MAX_LAYERS] = {};   // within a tape record
+  int wpad = 0, vec_off = 0, tape_off = 0;   // the backward recurrence's dz: two rows of wpad elements at vec_off; the tape, if in LDS
+  int64_t rec = 0;          // elements of one step's tape record (every row in it padded to four elements)
+  int64_t tape_elems = 0;   // T * rec
+  int64_t nmax = 0;         // the widest layer (the input not counted)
+  bool tape_lds = false;    // the tape fits the LDS beside everything else (else: operands.tape, tape_elems elements)
+  size_t lds = 0;           // dynamic LDS bytes
+};
+struct RnnOnlineOperands {
+  int L = 0;
+  int64_t widths[RNN_GEN_MAX_LAYERS + 1] = {};  // i, n_1 .. n_L
+  int state_kind[RNN_GEN_MAX_LAYERS] = {};      // ACT_KIND_* of a stateful layer's state, -1: stateless
+  void *W[RNN_GEN_MAX_LAYERS] = {}, *WS[RNN_GEN_MAX_LAYERS] = {}, *b[RNN_GEN_MAX_LAYERS] = {}, *s[RNN_GEN_MAX_LAYERS] = {};
+  const void *X = nullptr, *Y = nullptr;        // contiguous [N][T][i] and [N][T][n_L]
+  void* losses = nullptr;                       // contiguous [n_idx][T] (optional)
+  const long long* idx = nullptr;               // device [n_idx] (null: sequences 0 .. n_idx-1)
+  void* tape = nullptr;                         // tape_elems elements of global memory unless plan.tape_lds
+  int64_t n_idx = 0, T = 0;
+  int hidden_kind = 0;
+  bool softmax = true;
+  double rate_state = 0.0, rate_params = 0.0;
+};
+// widths: i, n_1 .. n_L.  False: more than 8 layers, or the parameters, states and the recurrences' vectors exceed
+// GEN_LDS_MAX; T decides only where the tape lives
+bool rnn_online_plan(int dtype, int L, const int64_t* widths, const int* stateful, int64_t T, RnnOnlinePlan* p);
+void launch_rnn_online(int dtype, const RnnOnlinePlan& p, const RnnOnlineOperands& o, hipStream_t s);
 // induce_seq.hip: every iteration of `induceNetwork` on every row in one launch (to_fflayer_stack_induce, route B).
 // X [B][i0] contiguous: x_0 on entry, x_iters on exit; gx [B][i0] (optional) the last iteration's gradient; losses
 // [B][iters] (optional).  A plan with G > 1 may only be launched where online_sgd_placement_ok() holds.

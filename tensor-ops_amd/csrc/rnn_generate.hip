@@ -28,7 +28,6 @@ namespace to {
 namespace {
 
 constexpr int GEN_THREADS = 256;
-constexpr size_t GEN_LDS_MAX = 160 * 1024;   // the limit rnn_seq.hip and induce_seq.hip use
 constexpr int64_t GEN_MAX_ITEMS = 4096;      // (row, column) items of the widest layer per workgroup
 
 __device__ __forceinline__ float exp_g(float x) { return expf(x); }

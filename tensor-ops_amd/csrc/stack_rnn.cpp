@@ -40,6 +40,8 @@ struct RnnStackArgs {  // what the three entries hand to rnn_stack_impl; each fi
   to_tensor Y = nullptr, out = nullptr, gx = nullptr, losses = nullptr;
   const to_tensor *s_out = nullptr, *gs = nullptr, *gws = nullptr, *gw = nullptr, *gb = nullptr;
   double rate_state = 0.0, rate_params = 0.0;
+  const char* fn = nullptr;   // the entry's name in messages when it is none of the three (to_rnn_stack_online_sgd)
+  bool check_only = false;    // validate and return: nothing is produced, claimed or launched
 };
 
 // The forward of a stack over T time-major steps of B sequences, shared by rnn_stack_impl (all T steps of X) and
@@ -146,7 +148,7 @@ static void rnn_stack_impl(const RnnStackArgs& a) {
   const int* state_act = a.state_act;
   const to_tensor *s = a.s, *ws = a.ws, *w = a.w, *b = a.b, *s_out = a.s_out, *gs = a.gs, *gws = a.gws, *gw = a.gw, *gb = a.gb;
   const to_tensor X = a.X, Y = a.Y, out = a.out, gx = a.gx, losses = a.losses;
-  const char* fn = run ? "to_rnn_stack_run" : grad ? "to_rnn_stack_grad" : "to_rnn_stack_sgd";
+  const char* fn = a.fn ? a.fn : run ? "to_rnn_stack_run" : grad ? "to_rnn_stack_grad" : "to_rnn_stack_sgd";
   const std::string F = std::string(fn) + ": ";
   require_init();
   no_capture(fn);
@@ -222,6 +224,7 @@ static void rnn_stack_impl(const RnnStackArgs& a) {
     }
   }
   TO_CHECK(T * B <= 2147483647LL, TO_ERR_SHAPE, F + "more than 2^31-1 rows");
+  if (a.check_only) return;
 
   // ---- operands produced; destinations claimed -------------------------------------------------------------------
   ensure(X);
@@ -661,6 +664,157 @@ to_status to_rnn_generate_stats(int64_t* persistent_runs, int64_t* per_step_runs
   API_BEGIN
   if (persistent_runs) *persistent_runs = g_rnn_generate_persistent_runs;
   if (per_step_runs) *per_step_runs = g_rnn_generate_step_runs;
+  API_END
+}
+
+// ---- per-sequence training: `trainNetwork'` folded over a set of sequences as one call --------------------------------------
+// Step j trains on sequence idx[j] alone, from the parameters and learned initial states step j - 1 left: a dependent chain
+// of single sequences.  Per sequence (route A): rnn_stack_impl in Sgd mode on the B = 1 views to_batch_select would give --
+// bit for bit the caller's own loop of to_rnn_stack_sgd.  Persistent (route B, rnn_online.hip): all n_idx sequences in ONE
+// launch by one workgroup, the whole stack in LDS.
+static int g_rnn_online_persistent = 1;   // to_set_rnn_online_persistent: 0 per sequence, 1 auto, 2 wherever in range
+static int64_t g_rnn_online_persistent_runs = 0, g_rnn_online_sequence_runs = 0;
+// The automatic rule: route B where its plan fits AND no layer (the input not counted) is wider than H*.  H* = 128 is the
+// largest width tools/rnn_online_scan.py scanned, and route B was ahead of route A at every scanned width at both T
+// (profiles/rnn_online_scan.txt, fp32 64 -> H (stateful) -> 10: A / B = 4.8 / 1.7 at H = 32, 3.6 / 1.5 at 64, 3.2 / 1.4 at 96,
+// 2.9 / 1.2 at 128, for T = 8 / 64).  Wider layers that still fit the LDS (up to about 200 columns in
+// fp32) have not been measured and take route A.
+constexpr int64_t RNN_ONLINE_AUTO_MAX_WIDTH = 128;
+
+to_status to_rnn_stack_online_sgd(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
+                                  const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
+                                  int64_t n_idx, const int64_t* idx_or_null, double rate_state, double rate_params,
+                                  to_tensor losses_or_null) {
+  API_BEGIN
+  const char* fn = "to_rnn_stack_online_sgd";
+  const std::string F = std::string(fn) + ": ";
+  const to_tensor losses = losses_or_null;
+  const int64_t* idx = idx_or_null;
+  require_init();
+  no_capture(fn);
+  NONNULL(state_act); NONNULL(s); NONNULL(ws); NONNULL(w); NONNULL(b); NONNULL(X); NONNULL(Y);
+  TO_CHECK(n_idx >= 1, TO_ERR_ARG, F + "n_idx must be at least 1");
+  auto set_like = [&](to_tensor t, const char* what) {
+    TO_CHECK(t->rank == 2 && t->batch > 0 && t->contiguous(), TO_ERR_SHAPE,
+             F + what + " must be a batched, contiguous [N; T, n], got " + shape_str(t));
+  };
+  set_like(X, "X");
+  set_like(Y, "Y");
+  const int64_t N = X->batch, T = X->dims[0];
+  const int dt = X->dtype;
+  TO_CHECK(Y->batch == N, TO_ERR_SHAPE, F + "X and Y have different batches");
+  // the stack, the pair and one sequence's shapes: to_rnn_stack_sgd's checks on what to_batch_select would hand it
+  to_tensor_s xv, yv, lv;
+  auto one_of = [](to_tensor_s& v, to_tensor t) {
+    v.dtype = t->dtype;
+    v.rank = t->rank;
+    for (int d = 0; d < t->rank; ++d) { v.dims[d] = t->dims[d]; v.strides[d] = t->strides[d]; }
+  };
+  one_of(xv, X);
+  one_of(yv, Y);
+  RnnStackArgs chk{RnnMode::Sgd, n_layers, state_act, s, ws, w, b, hidden_act, out_act, &xv, loss, &yv};
+  chk.fn = fn;
+  chk.check_only = true;
+  if (losses) {
+    TO_CHECK(losses->dtype == dt, TO_ERR_ARG, F + "losses and X have different dtypes");
+    TO_CHECK(losses->rank == 1 && losses->dims[0] == T && losses->batch == n_idx && losses->contiguous(), TO_ERR_SHAPE,
+             F + "losses must be a contiguous [" + std::to_string(n_idx) + "; " + std::to_string(T) + "], got " + shape_str(losses));
+    one_of(lv, losses);
+    chk.losses = &lv;
+  }
+  rnn_stack_impl(chk);
+  TO_CHECK(idx || n_idx <= N, TO_ERR_SHAPE, F + "more sequences asked for than X holds");
+  for (int64_t j = 0; idx && j < n_idx; ++j)
+    TO_CHECK(idx[j] >= 0 && idx[j] < N, TO_ERR_SHAPE, F + "sequence index out of range");
+  if (losses) {
+    bool bad = gen_overlap(losses, X) || gen_overlap(losses, Y);
+    for (int l = 0; l < n_layers; ++l)
+      bad = bad || gen_overlap(losses, s[l]) || gen_overlap(losses, ws[l]) || gen_overlap(losses, w[l]) || gen_overlap(losses, b[l]);
+    TO_CHECK(!bad, TO_ERR_ARG, F + "losses overlaps X, Y or a parameter");
+  }
+  // The route (RNN_ONLINE_AUTO_MAX_WIDTH above).
+  RnnOnlinePlan plan;
+  bool persistent = false;
+  if (g_rnn_online_persistent != 0 && n_layers <= RNN_GEN_MAX_LAYERS) {
+    int64_t widths[RNN_GEN_MAX_LAYERS + 1] = {X->dims[1]};
+    int stateful[RNN_GEN_MAX_LAYERS] = {};
+    for (int l = 0; l < n_layers; ++l) {
+      widths[l + 1] = w[l]->dims[0];
+      stateful[l] = state_act[l] != TO_RNN_STATELESS;
+    }
+    persistent = rnn_online_plan(dt, n_layers, widths, stateful, T, &plan) &&
+                 (g_rnn_online_persistent == 2 || plan.nmax <= RNN_ONLINE_AUTO_MAX_WIDTH);
+  }
+
+  // ---- operands produced; destinations claimed -------------------------------------------------------------------
+  ensure(X);
+  ensure(Y);
+  for (int l = 0; l < n_layers; ++l) {
+    ensure(w[l]); ensure(b[l]);
+    if (s[l]) { ensure(s[l]); ensure(ws[l]); }
+  }
+  if (losses) claim(losses);
+  if (persistent) {
+    RnnOnlineOperands o;
+    o.L = n_layers;
+    o.widths[0] = X->dims[1];
+    for (int l = 0; l < n_layers; ++l) {   // in-place writes: recorded readers of the old values first, new identities after
+      claim(w[l]); claim(b[l]);
+      o.widths[l + 1] = w[l]->dims[0];
+      o.state_kind[l] = !s[l] ? -1 : state_act[l] == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC;
+      o.W[l] = w[l]->ptr; o.b[l] = b[l]->ptr;
+      if (s[l]) {
+        claim(s[l]); claim(ws[l]);
+        o.WS[l] = ws[l]->ptr; o.s[l] = s[l]->ptr;
+      }
+    }
+    Holder order, tape;
+    if (idx) {
+      const int64_t nl = (n_idx * 8 + 3) / 4;   // n_idx int64 in a float-typed pool buffer
+      order.t = new_tensor(1, &nl, 0);
+      host_to_device(order.t->ptr, idx, (size_t)n_idx * sizeof(int64_t), S());
+      o.idx = static_cast<const long long*>(order.t->ptr);
+    }
+    if (!plan.tape_lds) {
+      tape.t = new_tensor(1, &plan.tape_elems, 0, dt);
+      o.tape = tape.t->ptr;
+    }
+    o.X = X->ptr; o.Y = Y->ptr; o.losses = losses ? losses->ptr : nullptr;
+    o.n_idx = n_idx; o.T = T;
+    o.hidden_kind = hidden_act == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC;
+    o.softmax = out_act == TO_ACT_SOFTMAX;
+    o.rate_state = rate_state; o.rate_params = rate_params;
+    launch_rnn_online(dt, plan, o, S());
+    TO_HIP(hipStreamSynchronize(S()));   // the order and the tape go back to the pool
+    g_rnn_online_persistent_runs++;
+  } else {
+    for (int64_t j = 0; j < n_idx; ++j) {
+      const int64_t q = idx ? idx[j] : j;
+      Holder xq(new_view(X, X->rank, X->dims, X->strides, 0, X->numel(), q * X->bstride));
+      Holder yq(new_view(Y, Y->rank, Y->dims, Y->strides, 0, Y->numel(), q * Y->bstride));
+      Holder lq(losses ? new_view(losses, 1, losses->dims, losses->strides, 0, losses->numel(), j * losses->numel()) : nullptr);
+      RnnStackArgs a{RnnMode::Sgd, n_layers, state_act, s, ws, w, b, hidden_act, out_act, xq.t, loss, yq.t};
+      a.losses = lq.t; a.rate_state = rate_state; a.rate_params = rate_params; a.fn = fn;
+      rnn_stack_impl(a);
+    }
+    g_rnn_online_sequence_runs++;
+  }
+  API_END
+}
+
+to_status to_set_rnn_online_persistent(int on, int* previous_or_null) {
+  API_BEGIN
+  TO_CHECK(on >= 0 && on <= 2, TO_ERR_ARG,
+           "to_set_rnn_online_persistent: 0 (per sequence), 1 (automatic) or 2 (wherever in range)");
+  if (previous_or_null) *previous_or_null = g_rnn_online_persistent;
+  g_rnn_online_persistent = on;
+  API_END
+}
+
+to_status to_rnn_online_stats(int64_t* persistent_runs, int64_t* per_sequence_runs) {
+  API_BEGIN
+  if (persistent_runs) *persistent_runs = g_rnn_online_persistent_runs;
+  if (per_sequence_runs) *per_sequence_runs = g_rnn_online_sequence_runs;
   API_END
 }
 

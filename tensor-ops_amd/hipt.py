@@ -696,6 +696,40 @@ class HipT:
         check(lib().to_rnn_generate_stats(C.byref(p), C.byref(q)))
         return p.value, q.value
 
+    def rnn_stack_online_sgd(self, layers, X, Y, rate_state, rate_params, idx=None, n_idx=None, out_act="softmax",
+                             loss="crossEntropy", hidden_act="logistic", want_losses=False):
+        """`trainNetwork'` folded over the sequences idx[0 .. n_idx) (None: sequences 0 .. n_idx-1, all of them when n_idx is
+        None too) of X [N; T, i] / Y [N; T, n_L], one sequence an update, parameters and initial states updated in place
+        (to_rnn_stack_online_sgd); the losses [n_idx; T] if asked for"""
+        n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
+        arr = None
+        if idx is not None:
+            arr = np.ascontiguousarray(idx, dtype=np.int64)
+            n_idx = len(arr) if n_idx is None else n_idx
+        elif n_idx is None:
+            n_idx = X.batch
+        n_idx = int(n_idx)
+        losses = self._alloc((X.shape[0],), n_idx) if want_losses and n_idx >= 1 else None
+        check(lib().to_rnn_stack_online_sgd(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
+                                            self._RNN_LOSS[loss], X.h, Y.h, n_idx,
+                                            arr.ctypes.data_as(C.POINTER(C.c_int64)) if arr is not None else None,
+                                            float(rate_state), float(rate_params), losses.h if losses is not None else None))
+        return losses
+
+    @staticmethod
+    def rnn_online_persistent(on):
+        """to_set_rnn_online_persistent: 0 per sequence, 1 automatic, 2 wherever in range; returns the previous setting"""
+        prev = C.c_int()
+        check(lib().to_set_rnn_online_persistent(int(on), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
+    def rnn_online_stats():
+        """(persistent runs, per-sequence runs)"""
+        p, q = C.c_int64(), C.c_int64()
+        check(lib().to_rnn_online_stats(C.byref(p), C.byref(q)))
+        return p.value, q.value
+
     # -- induceNetwork iterated (to_fflayer_stack_induce) ----------------------------------------
     def induce_stack(self, ws, bs, x, y, rate, iters, out_act="softmax", loss="crossEntropy", want_gx=False,
                      want_losses=False, in_place=False, hidden_act="logistic"):

@@ -540,6 +540,51 @@ to_status to_rnn_stack_sgd(int n_layers, const int* state_act, const to_tensor* 
 to_status to_set_rnn_persistent(int on, int* previous_or_null);
 to_status to_rnn_stats(int64_t* persistent_runs, int64_t* stepwise_runs);
 
+/* The same three entries for a batch whose sequences have DIFFERENT lengths (`trainNetwork` of Recurrent.hs takes a list
+ * [(x, y)] of any length): the argument list of the dense sibling with `lens` directly after the data tensors.  lens is a
+ * host array of B entries (one for X [T, i]) and may be reused on return.  Sequence b is steps 0 .. lens[b]-1 of X[b]; the
+ * steps t >= lens[b] are PADDING.  1 <= lens[b] <= T, otherwise TO_ERR_SHAPE; lens null is TO_ERR_ARG.
+ *   Padding is never read: padding rows of X and Y may hold anything, NaN and Inf included, and influence no output bit.
+ *   run   out[b, t] is the stack's output for t < lens[b] and exactly +0.0 at padding; s_out[l][b] is the state after step
+ *         lens[b]-1 -- valid as s of a following dense or ragged call (a ragged batch fed in chunks).
+ *   grad  objective sum_b sum_{t < lens[b]} loss(out_{b,t}, Y_{b,t}); gs / gws / gw / gb its cotangents; gx and losses are
+ *         exactly +0.0 at padding.
+ *   sgd   `trainNetwork'` on that objective, in place.
+ * Every other rule is the dense sibling's, with its statuses: the stack, state_act, hidden_act, the (out_act, loss) pairs,
+ * the dtypes, the batching of s, the unbatched initial states of grad / sgd, contiguity, refusal during graph capture; every
+ * refusal leaves every destination untouched.  fp32 and fp64, any B, T and widths: never TO_ERR_UNSUPPORTED for a valid
+ * stack.
+ * Routes.  The sequences are sorted by length (descending, stable) and their steps packed time-major: at step t the active
+ * sequences own consecutive packed rows, N = sum lens rows in all (csrc/rnn_ragged.hip: one pack launch per data tensor,
+ * one unpack launch per [B; T, .] destination, device tables of O(B + T)).  The time-independent work is the dense entries'
+ * contractions over exactly N rows, so the work follows sum lens, not B T, and padding enters no contraction.  A stateful
+ * layer's recurrence is one persistent launch per direction (rnn_ragged_seq_kernel: a workgroup of short sequences ends
+ * early; the launch count depends on neither T nor lens) or per step on the rows still active (launches grow with max lens,
+ * not with T).  to_set_rnn_persistent and its threshold (W' in LDS) decide exactly as for the dense entries; that threshold
+ * was measured on equal-length batches and HAS NOT BEEN MEASURED for ragged ones.  With every length equal to T the results
+ * are the dense entries', bit for bit.  The dense entries, their launches and to_rnn_stats are untouched by these calls;
+ * to_rnn_ragged_stats counts the ragged calls with a stateful layer by route.
+ * Measured (tools/rnn_ragged_scan.py, profiles/rnn_ragged_scan.txt; fp32, T = 64, lengths uniform in 1..T, grad and sgd
+ * alike, persistent route): against the caller's loop of one dense call per distinct length on to_batch_gather'ed groups the
+ * ragged call is 2.6x to 21x ahead (5 -> 7 -> 5: 14x at B = 64, 2.7x at B = 1024; 64 -> 128 -> 64: 21x and 13x); against the
+ * dense entry on the padded batch (B T rows of work, not the ragged objective) 1.35x / 1.8x ahead on the narrow stack and
+ * 0.97x (B = 64: behind) / 1.27x on the wide one -- 2.6x and 1.6x of padded x sum lens / (B T), which it does NOT reach
+ * there: the longest sequences' workgroups still walk all their steps.  Where it LOSES: with every length equal to T it is
+ * 5 to 12 % behind the dense entry (the table upload, pack and unpack buy nothing then) -- call the dense entry for such a
+ * batch.  NOT measured: fp64, tanh states, the per-step route, the persistent / per-step threshold under ragged batches. */
+to_status to_rnn_stack_run_ragged(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                                  const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, to_tensor X,
+                                  const int64_t* lens, to_tensor out, const to_tensor* s_out_or_null);
+to_status to_rnn_stack_grad_ragged(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                                   const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X,
+                                   to_tensor Y, const int64_t* lens, const to_tensor* gs, const to_tensor* gws,
+                                   const to_tensor* gw, const to_tensor* gb, to_tensor gx_or_null, to_tensor losses_or_null);
+to_status to_rnn_stack_sgd_ragged(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                                  const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X,
+                                  to_tensor Y, const int64_t* lens, double rate_state, double rate_params,
+                                  to_tensor losses_or_null);
+to_status to_rnn_ragged_stats(int64_t* persistent_runs, int64_t* stepwise_runs);
+
 /* Closed-loop generation of the same stacks in ONE call: `runNetworkSt` under `iterate` -- prime the stack with a few steps,
  * then feed every output back as the next input.  The stack, state_act, hidden_act, out_act (TO_ACT_SOFTMAX or
  * TO_ACT_LOGISTIC; anything else TO_ERR_UNSUPPORTED), the dtypes, the batching of s (unbatched or [B; n_l]) and the s_out

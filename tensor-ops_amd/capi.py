@@ -147,6 +147,16 @@ SIGNATURES = {
                          c_tensor],
     "to_set_rnn_persistent": [C.c_int, C.POINTER(C.c_int)],
     "to_rnn_stats": [i64p, i64p],
+    "to_rnn_stack_run_ragged": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor),
+                                C.POINTER(c_tensor), C.c_int, C.c_int, c_tensor, i64p, c_tensor, C.POINTER(c_tensor)],
+    "to_rnn_stack_grad_ragged": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor),
+                                 C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int, c_tensor, c_tensor, i64p,
+                                 C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor), c_tensor,
+                                 c_tensor],
+    "to_rnn_stack_sgd_ragged": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor),
+                                C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int, c_tensor, c_tensor, i64p, C.c_double,
+                                C.c_double, c_tensor],
+    "to_rnn_ragged_stats": [i64p, i64p],
     "to_rnn_stack_generate": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor),
                               C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int, c_tensor, c_tensor, C.c_int64, c_tensor,
                               c_tensor, i64p, C.POINTER(c_tensor)],

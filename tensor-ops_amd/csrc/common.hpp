@@ -488,6 +488,31 @@ struct RnnSeqPlan {
 bool rnn_seq_plan(int dtype, int64_t H, int64_t B, RnnSeqPlan* p);
 void launch_rnn_seq(int dtype, bool reverse, const RnnSeqPlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T,
                     int64_t H, int act_kind, hipStream_t s);
+// rnn_ragged.hip: sequences of different lengths (to_rnn_stack_*_ragged).  The row schedule: the sequences sorted by length,
+// descending and stable; at step t the active ones are the first cnt[t] sorted positions and their packed rows are
+// off[t] .. off[t] + cnt[t] - 1, N = off[Tmax] rows in all.  The tables live on the device, O(B + T) int32.
+struct RaggedTables {
+  const int* perm;   // [B]: sorted position -> sequence
+  const int* inv;    // [B]: sequence -> sorted position
+  const int* lens;   // [B]: the length of each sequence (the caller's order)
+  const int* off;    // [Tmax + 1]: the first packed row of each step; off[Tmax] = N
+  int B, Tmax, N;
+};
+// dst [N][n] packed <- element (b, t, j) of src at b * sb + t * st + j * sj (elements); padding is not read
+void launch_ragged_pack(int dtype, const RaggedTables& tb, const void* src, int64_t sb, int64_t st, int64_t sj, void* dst,
+                        int64_t n, hipStream_t s);
+// dst contiguous [B][T][n] <- packed src [N][n]; +0.0 at (b, t >= lens[b])
+void launch_ragged_unpack(int dtype, const RaggedTables& tb, const void* src, void* dst, int64_t T, int64_t n, hipStream_t s);
+// mode 0: dst [B][n] (Sp block 0) <- the batched initial states src (b * sb + j * ss) of the sorted sequences; mode 1: dst
+// [B][n] (s_out, the caller's order) <- row (lens[b] - 1, b) of Sa = src; mode 2: dst = Sp rows B .. N-1 <- Sa = src, the
+// state before step t >= 1 being the state after step t - 1
+void launch_ragged_states(int dtype, int mode, const RaggedTables& tb, const void* src, void* dst, int64_t n, int64_t sb,
+                          int64_t ss, hipStream_t s);
+// rnn_seq.hip's recurrence on packed rows, a workgroup per p.R consecutive sorted sequences (p: rnn_seq_plan's).  Z, Sa, Sp
+// [N][H]: forward Z = P -> z in place, Sa(t, p) = act(z), Sp(t + 1, p) the same where the sequence goes on (Sp block 0: the
+// initial states, read); reverse Z = G -> dz in place, reading Sa.
+void launch_rnn_ragged_seq(int dtype, bool reverse, const RnnSeqPlan& p, const RaggedTables& tb, const void* M, void* Z,
+                           void* Sa, void* Sp, int64_t H, int act_kind, hipStream_t s);
 // rnn_generate.hip: closed-loop generation (to_rnn_stack_generate).  The feed rule -- the next input row from the stored
 // previous output row -- has ONE definition there, used by both routes: feed_kernel (route A, one launch a generated step:
 // x [B][n] from prev [B][n], the symbol of row r into sym[r * G + k]) and rnn_gen_kernel (route B: the prime and all G steps of all

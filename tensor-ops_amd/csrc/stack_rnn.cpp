@@ -7,6 +7,7 @@
 // S are the two offset views St[0..T) and St[1..T] of one buffer.  What is left is each stateful layer's recurrence:
 // persistent (rnn_seq.hip, one launch per layer and direction for all T steps) or per step (one GEMM with the addend,
 // plus one elementwise launch).  The caller's [B; T, .] rows are moved to and from time-major by one strided copy each.
+#include <algorithm>
 #include <memory>
 
 #include "api_util.hpp"
@@ -430,6 +431,290 @@ to_status to_rnn_stack_sgd(int n_layers, const int* state_act, const to_tensor* 
   RnnStackArgs a{RnnMode::Sgd, n_layers, state_act, s, ws, w, b, hidden_act, out_act, X, loss, Y};
   a.losses = losses_or_null; a.rate_state = rate_state; a.rate_params = rate_params;
   rnn_stack_impl(a);
+  API_END
+}
+
+// ---- sequences of different lengths: to_rnn_stack_*_ragged ---------------------------------------------------------------
+// Sequence b is steps 0 .. lens[b]-1 of X[b]; the rest of its rows is padding, never read.  The sequences are sorted by
+// length (descending, stable) and their steps packed time-major (rnn_ragged.hip: at step t the first cnt[t] sorted positions
+// are active and own the packed rows off[t] ..), N = sum lens rows in all.  Every time-independent piece is the dense path's
+// own call with rows = N; block 0 holds all B sequences, so gs is the dense expression too.  A stateful layer keeps Sa (the
+// state after each step) and Sp (the state before it, block 0 the initial states), both aligned row for row with Z.  The
+// recurrence: rnn_ragged_seq_kernel (one launch per layer and direction) or per step on the prefix of cnt[t] rows at off[t],
+// by rnn_persistent_for -- the dense rule, measured on equal lengths only.  With every length equal to T the schedule IS the
+// dense layout and every contraction the dense one.
+static int64_t g_rnn_ragged_persistent_runs = 0, g_rnn_ragged_stepwise_runs = 0;
+
+static void rnn_ragged_impl(RnnStackArgs a, const int64_t* lens) {
+  const bool run = a.mode == RnnMode::Run, grad = a.mode == RnnMode::Grad, sgd = a.mode == RnnMode::Sgd;
+  const int n_layers = a.n_layers;
+  const int* state_act = a.state_act;
+  const to_tensor *s = a.s, *ws = a.ws, *w = a.w, *b = a.b, *s_out = a.s_out, *gs = a.gs, *gws = a.gws, *gw = a.gw, *gb = a.gb;
+  const to_tensor X = a.X, Y = a.Y, out = a.out, gx = a.gx, losses = a.losses;
+  const std::string F = std::string(a.fn) + ": ";
+  // the stack, the pair, the shapes, the dtypes, graph capture: the dense sibling's checks with its statuses
+  a.check_only = true;
+  rnn_stack_impl(a);
+  NONNULL(lens);
+  const int dt = X->dtype;
+  const int64_t T = X->dims[0], B = X->batch > 0 ? X->batch : 1, in_n = X->dims[1], nL = w[n_layers - 1]->dims[0];
+  int64_t Tmax = 0, N = 0;
+  for (int64_t q = 0; q < B; ++q) {
+    TO_CHECK(lens[q] >= 1 && lens[q] <= T, TO_ERR_SHAPE,
+             F + "lens[" + std::to_string(q) + "] = " + std::to_string(lens[q]) + " is outside 1 .. T = " + std::to_string(T));
+    Tmax = std::max(Tmax, lens[q]);
+    N += lens[q];
+  }
+  TO_CHECK(nL <= 2147483647LL, TO_ERR_SHAPE, F + "output layer too wide");
+  const auto state_kind = [&](int l) { return state_act[l] == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC; };
+  const int hk = a.hidden_act == TO_ACT_TANH ? ACT_KIND_TANH : ACT_KIND_LOGISTIC;
+  const int head = run ? 0 : stack_loss_head(a.out_act, a.loss, F);
+
+  // ---- the row schedule: perm, its inverse, the lengths, off -- one table, one upload -------------------------------------
+  std::vector<int> tab((size_t)(3 * B + Tmax + 1));
+  int *perm = tab.data(), *inv = perm + B, *len32 = inv + B, *off = len32 + B;
+  for (int64_t q = 0; q < B; ++q) { perm[q] = (int)q; len32[q] = (int)lens[q]; }
+  std::stable_sort(perm, perm + B, [&](int x, int y) { return lens[x] > lens[y]; });
+  for (int64_t p = 0; p < B; ++p) inv[perm[p]] = (int)p;
+  std::vector<int64_t> cnt((size_t)Tmax + 1, 0);   // cnt[t]: sequences longer than t (cnt[Tmax] = 0)
+  for (int64_t q = 0; q < B; ++q) cnt[lens[q] - 1]++;
+  for (int64_t t = Tmax - 1; t >= 0; --t) cnt[t] += cnt[t + 1];
+  off[0] = 0;
+  for (int64_t t = 0; t < Tmax; ++t) off[t + 1] = off[t] + (int)cnt[t];
+
+  // ---- operands produced; destinations claimed -------------------------------------------------------------------
+  ensure(X);
+  if (Y) ensure(Y);
+  for (int l = 0; l < n_layers; ++l) {
+    ensure(w[l]); ensure(b[l]);
+    if (s[l]) { ensure(s[l]); ensure(ws[l]); }
+  }
+  if (out) claim(out);
+  if (s_out) for (int l = 0; l < n_layers; ++l) if (s_out[l]) claim(s_out[l]);
+  if (gx) claim(gx);
+  if (losses) claim(losses);
+  if (grad)
+    for (int l = 0; l < n_layers; ++l) {
+      claim(gw[l]); claim(gb[l]);
+      if (gs[l]) { claim(gs[l]); claim(gws[l]); }
+    }
+
+  const int64_t es = dt == TO_F64 ? 8 : 4;
+  Holder tabh;
+  {
+    const int64_t nw = (int64_t)tab.size();   // int32 in a float-typed pool buffer
+    tabh.t = new_tensor(1, &nw, 0);
+    host_to_device(tabh.t->ptr, tab.data(), tab.size() * sizeof(int), S());
+  }
+  const int* dtab = static_cast<const int*>(tabh.t->ptr);
+  const RaggedTables tb{dtab, dtab + B, dtab + 2 * B, dtab + 3 * B, (int)B, (int)Tmax, (int)N};
+  auto rows_of = [&](int64_t rows, int64_t n, Holder& h) -> void* {
+    const int64_t d2[2] = {rows, n};
+    h.t = new_tensor(2, d2, 0, dt);
+    return h.t->ptr;
+  };
+  auto pack = [&](to_tensor t, Holder& h) -> const void* {
+    void* d = rows_of(N, t->dims[1], h);
+    launch_ragged_pack(dt, tb, t->ptr, t->batch > 0 ? t->bstride : 0, t->strides[0], t->strides[1], d, t->dims[1], S());
+    return d;
+  };
+  Holder xh, yh;
+  const void* Xt = pack(X, xh);
+  const void* Yt = !run ? pack(Y, yh) : nullptr;
+
+  // ---- forward: rnn_forward's launches with rows = N -------------------------------------------------------------------
+  RnnForward f(n_layers);   // (St holds Sa here)
+  std::vector<Holder> Sp(n_layers);
+  std::vector<Holder>&Z = f.Z, &Sa = f.St, &WT = f.WT, &Ah = f.Ah;
+  {
+    const void* prev = Xt;
+    int64_t prev_n = in_n;
+    for (int l = 0; l < n_layers; ++l) {
+      const int64_t n = w[l]->dims[0];
+      const bool last = l + 1 == n_layers, stateful = state_act[l] != TO_RNN_STATELESS;
+      void* z = rows_of(N, n, Z[l]);
+      GemmProblem p = row_gemm(dt, prev, prev_n, 1, w[l]->ptr, 1, prev_n, z, N, n, prev_n);
+      p.bias = b[l]->ptr;
+      if (!stateful && !last) p.act = hk + 1;
+      if (last && !stateful && run) { p.bias = nullptr; f.no_bias_for_head = b[l]->ptr; }
+      gemm_with_epilogue(p);
+      if (stateful) {
+        f.any_state = true;
+        void* sa = rows_of(N, n, Sa[l]);
+        void* sp = rows_of(N, n, Sp[l]);
+        if (s[l]->batch == 0) launch_bcast_axis(dt, s[l]->ptr, sp, 1, B, n, 0, S());
+        else launch_ragged_states(dt, 0, tb, s[l]->ptr, sp, n, s[l]->bstride, s[l]->strides[0], S());
+        f.persist[l] = rnn_persistent_for(dt, n, B, &f.plan[l]);
+        f.all_persistent = f.all_persistent && f.persist[l];
+        if (f.persist[l]) {
+          const int64_t dd[2] = {n, n}, ss[2] = {1, n};  // W'^T: M[k][j] = W'[j][k]
+          WT[l].t = new_tensor(2, dd, 0, dt);
+          launch_copy_strided(dt, ws[l]->ptr, WT[l].t->ptr, 2, dd, ss, S());
+          launch_rnn_ragged_seq(dt, false, f.plan[l], tb, WT[l].t->ptr, z, sa, sp, n, state_kind(l), S());
+        } else {
+          // z_t = P_t + s_{t-1} W'^T (in place), s_t = state_act(z_t), on the cnt[t] active rows; the states before step
+          // t >= 1 are the first cnt[t] rows of Sa's block t - 1
+          for (int64_t t = 0; t < Tmax; ++t) {
+            const void* before = t == 0 ? sp : at(sa, (int64_t)off[t - 1] * n, es);
+            GemmProblem q = row_gemm(dt, before, n, 1, ws[l]->ptr, 1, n, at(z, (int64_t)off[t] * n, es), cnt[t], n, n);
+            q.beta = 1.0;
+            q.Cin = q.C;
+            gemm_with_epilogue(q);
+            ew2(dt, state_kind(l) == ACT_KIND_TANH ? EW_TANH : EW_LOGISTIC, at(sa, (int64_t)off[t] * n, es),
+                at(z, (int64_t)off[t] * n, es), nullptr, cnt[t] * n);
+          }
+          if (!run) launch_ragged_states(dt, 2, tb, sa, sp, n, 0, 0, S());   // Sp blocks 1..: the left operand of gW'
+        }
+      }
+      if (stateful && !last && state_kind(l) == hk) {
+        prev = Sa[l].t->ptr;
+      } else if (stateful && !last) {
+        void* ah = rows_of(N, n, Ah[l]);
+        ew2(dt, hk == ACT_KIND_TANH ? EW_TANH : EW_LOGISTIC, ah, z, nullptr, N * n);
+        prev = ah;
+      } else {
+        prev = z;
+      }
+      f.outp[l] = prev;
+      prev_n = n;
+    }
+  }
+  if (f.any_state) (f.all_persistent ? g_rnn_ragged_persistent_runs : g_rnn_ragged_stepwise_runs)++;
+  const int L = n_layers - 1;
+  if (run) {
+    if (s_out)
+      for (int l = 0; l < n_layers; ++l)
+        if (s_out[l]) launch_ragged_states(dt, 1, tb, Sa[l].t->ptr, s_out[l]->ptr, w[l]->dims[0], 0, 0, S());
+    Holder oh, zb;
+    void* ot = rows_of(N, nL, oh);
+    rnn_head_rows(dt, f, n_layers, nL, N, a.out_act, ot, zb);
+    launch_ragged_unpack(dt, tb, ot, out->ptr, T, nL, S());
+    TO_HIP(hipStreamSynchronize(S()));
+    return;
+  }
+
+  // ---- backward: rnn_stack_impl's with rows = N, Sa under act' and Sp as S_prev ----------------------------------------
+  std::vector<Holder> tg(4 * n_layers);
+  std::vector<void*> g_s(n_layers, nullptr), g_ws(n_layers, nullptr), g_w(n_layers), g_b(n_layers);
+  for (int l = 0; l < n_layers; ++l) {
+    auto dest = [&](const to_tensor* given, to_tensor like, Holder& h) -> void* {
+      if (grad) return given[l]->ptr;
+      h.t = new_tensor(like->rank, like->dims, 0, dt);
+      return h.t->ptr;
+    };
+    g_w[l] = dest(gw, w[l], tg[4 * l]);
+    g_b[l] = dest(gb, b[l], tg[4 * l + 1]);
+    if (state_act[l] != TO_RNN_STATELESS) {
+      g_s[l] = dest(gs, s[l], tg[4 * l + 2]);
+      g_ws[l] = dest(gws, ws[l], tg[4 * l + 3]);
+    }
+  }
+  Holder dzL, lh;
+  rows_of(N, nL, dzL);
+  void* lt = nullptr;
+  if (losses) { lh.t = new_tensor(1, &N, 0, dt); lt = lh.t->ptr; }
+  launch_loss_grad_rows(dt, Z[L].t->ptr, Yt, dzL.t->ptr, lt, N, nL, loss_grad_rows_kind(head), S());
+  if (losses) launch_ragged_unpack(dt, tb, lt, losses->ptr, T, 1, S());
+  Holder dz_cur(dzL.take()), gxh;
+  for (int l = L; l >= 0; --l) {
+    const int64_t n = w[l]->dims[0], m = w[l]->dims[1];
+    const bool stateful = state_act[l] != TO_RNN_STATELESS;
+    void* dz = dz_cur.t->ptr;
+    if (stateful) {  // dz_t = G_t + (dz_{t+1} W') (.) state_act'(s_t) where the sequence has a step t + 1, in place over G
+      void *sa = Sa[l].t->ptr, *sp = Sp[l].t->ptr;
+      if (f.persist[l]) {
+        launch_rnn_ragged_seq(dt, true, f.plan[l], tb, ws[l]->ptr, dz, sa, sp, n, state_kind(l), S());
+      } else {
+        const int64_t d2[2] = {B, n};
+        Holder dtmp(new_tensor(2, d2, 0, dt));
+        for (int64_t t = Tmax - 2; t >= 0; --t) {   // the first cnt[t+1] rows of block t go on to step t + 1
+          GemmProblem q = row_gemm(dt, at(dz, (int64_t)off[t + 1] * n, es), n, 1, ws[l]->ptr, n, 1, dtmp.t->ptr, cnt[t + 1], n, n);
+          q.dact = at(sa, (int64_t)off[t] * n, es);
+          q.dact_kind = state_kind(l);
+          gemm_with_epilogue(q);
+          ew2(dt, EW_AFFINE, at(dz, (int64_t)off[t] * n, es), at(dz, (int64_t)off[t] * n, es), dtmp.t->ptr, cnt[t + 1] * n);
+        }
+      }
+      // gW' = dZ^T S_prev ; gs = (sum_p dz_0[p]) W' (block 0 holds all B sequences)
+      run_gemm(row_gemm(dt, dz, 1, n, sp, n, 1, g_ws[l], n, n, N));
+      Holder dsum(new_tensor(1, &n, 0, dt));
+      launch_sum_axis(dt, dz, dsum.t->ptr, 1, B, n, 0, n, 1, S());
+      run_gemm(row_gemm(dt, dsum.t->ptr, n, 1, ws[l]->ptr, n, 1, g_s[l], 1, n, n));
+    }
+    const void* a_in = l > 0 ? f.outp[l - 1] : Xt;
+    GemmProblem p = row_gemm(dt, dz, 1, n, a_in, m, 1, g_w[l], n, m, N);
+    p.rowsum = g_b[l];
+    if (gemm_small_route(p)) {
+      launch_gemm_small(p, S());
+    } else {
+      p.rowsum = nullptr;
+      run_gemm(p);
+      launch_sum_axis(dt, dz, g_b[l], 1, N, n, 0, n, 1, S());
+    }
+    if (l > 0 || gx) {
+      Holder next;
+      void* dst = rows_of(N, m, l > 0 ? next : gxh);
+      GemmProblem q = row_gemm(dt, dz, n, 1, w[l]->ptr, m, 1, dst, N, m, n);
+      if (l > 0) { q.dact = a_in; q.dact_kind = hk; }
+      gemm_with_epilogue(q);
+      if (l == 0) launch_ragged_unpack(dt, tb, dst, gx->ptr, T, m, S());
+      else { Holder drop(dz_cur.take()); dz_cur.t = next.take(); }
+    }
+  }
+  if (sgd) {  // trainNetwork': s -= rate_state gs, every parameter -= rate_params g
+    for (int l = 0; l < n_layers; ++l) {
+      before_write(w[l]); before_write(b[l]);
+      w[l]->id = fresh_id(); b[l]->id = fresh_id();
+      launch_sgd(dt, w[l]->ptr, g_w[l], a.rate_params, w[l]->total(), S());
+      launch_sgd(dt, b[l]->ptr, g_b[l], a.rate_params, b[l]->total(), S());
+      if (state_act[l] != TO_RNN_STATELESS) {
+        before_write(s[l]); before_write(ws[l]);
+        s[l]->id = fresh_id(); ws[l]->id = fresh_id();
+        launch_sgd(dt, s[l]->ptr, g_s[l], a.rate_state, s[l]->total(), S());
+        launch_sgd(dt, ws[l]->ptr, g_ws[l], a.rate_params, ws[l]->total(), S());
+      }
+    }
+  }
+  TO_HIP(hipStreamSynchronize(S()));
+}
+
+to_status to_rnn_stack_run_ragged(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                                  const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, to_tensor X,
+                                  const int64_t* lens, to_tensor out, const to_tensor* s_out_or_null) {
+  API_BEGIN
+  RnnStackArgs a{RnnMode::Run, n_layers, state_act, s, ws, w, b, hidden_act, out_act, X};
+  a.out = out; a.s_out = s_out_or_null; a.fn = "to_rnn_stack_run_ragged";
+  rnn_ragged_impl(a, lens);
+  API_END
+}
+
+to_status to_rnn_stack_grad_ragged(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                                   const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X,
+                                   to_tensor Y, const int64_t* lens, const to_tensor* gs, const to_tensor* gws,
+                                   const to_tensor* gw, const to_tensor* gb, to_tensor gx_or_null, to_tensor losses_or_null) {
+  API_BEGIN
+  RnnStackArgs a{RnnMode::Grad, n_layers, state_act, s, ws, w, b, hidden_act, out_act, X, loss, Y};
+  a.gs = gs; a.gws = gws; a.gw = gw; a.gb = gb; a.gx = gx_or_null; a.losses = losses_or_null;
+  a.fn = "to_rnn_stack_grad_ragged";
+  rnn_ragged_impl(a, lens);
+  API_END
+}
+
+to_status to_rnn_stack_sgd_ragged(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                                  const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X,
+                                  to_tensor Y, const int64_t* lens, double rate_state, double rate_params,
+                                  to_tensor losses_or_null) {
+  API_BEGIN
+  RnnStackArgs a{RnnMode::Sgd, n_layers, state_act, s, ws, w, b, hidden_act, out_act, X, loss, Y};
+  a.losses = losses_or_null; a.rate_state = rate_state; a.rate_params = rate_params; a.fn = "to_rnn_stack_sgd_ragged";
+  rnn_ragged_impl(a, lens);
+  API_END
+}
+
+to_status to_rnn_ragged_stats(int64_t* persistent_runs, int64_t* stepwise_runs) {
+  API_BEGIN
+  if (persistent_runs) *persistent_runs = g_rnn_ragged_persistent_runs;
+  if (stepwise_runs) *stepwise_runs = g_rnn_ragged_stepwise_runs;
   API_END
 }
 

@@ -603,22 +603,37 @@ class HipT:
         col = [(capi.c_tensor * n)(*[(t.h if t is not None else None) for t in ts]) for ts in zip(*[lay[:4] for lay in layers])]
         return n, sact, col
 
-    def rnn_stack_run(self, layers, X, out_act="softmax", want_states=False, hidden_act="logistic"):
+    @staticmethod
+    def _rnn_lens(lens, X):
+        """lens (one length per sequence of X) as the int64 host array the ragged entries read"""
+        arr = np.ascontiguousarray(lens, dtype=np.int64).reshape(-1)
+        if len(arr) != max(X.batch, 1):
+            raise ValueError("lens needs one entry per sequence of X")
+        return arr
+
+    def rnn_stack_run(self, layers, X, out_act="softmax", want_states=False, hidden_act="logistic", lens=None):
         """`runNetwork` threaded over the T steps of X [B; T, i] (to_rnn_stack_run): (out [B; T, n_L], final states --
-        one per layer, None for a stateless one -- or None)"""
+        one per layer, None for a stateless one -- or None).  lens: sequence b is steps 0 .. lens[b]-1 of X[b], the rest
+        padding (to_rnn_stack_run_ragged): out is zero there and the final states are those after step lens[b]-1."""
         n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
         T, _ = X.shape
         batch = X.batch
         out = self._alloc((T, layers[-1][2].shape[0]), batch)
         finals = [self._alloc((lay[2].shape[0],), batch) if (want_states and lay[0] is not None) else None for lay in layers]
         s_out = (capi.c_tensor * n)(*[(f.h if f is not None else None) for f in finals]) if want_states else None
+        if lens is not None:
+            arr = self._rnn_lens(lens, X)
+            check(lib().to_rnn_stack_run_ragged(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act], X.h,
+                                                arr.ctypes.data_as(C.POINTER(C.c_int64)), out.h, s_out))
+            return out, (finals if want_states else None)
         check(lib().to_rnn_stack_run(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act], X.h, out.h, s_out))
         return out, (finals if want_states else None)
 
     def rnn_stack_grad(self, layers, X, Y, out_act="softmax", loss="crossEntropy", want_gx=False, want_losses=False,
-                       hidden_act="logistic"):
+                       hidden_act="logistic", lens=None):
         """BPTT of the stack summed over the sequences of X (to_rnn_stack_grad): (gs, gws, gw, gb -- lists per layer, None
-        for a stateless layer's state entries --, gx [B; T, i] or None, losses [B; T] or None)"""
+        for a stateless layer's state entries --, gx [B; T, i] or None, losses [B; T] or None).  lens: the objective
+        covers steps t < lens[b] only (to_rnn_stack_grad_ragged); gx and losses are zero at padding."""
         n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
         gS = [self._alloc(lay[0].shape, 0) if lay[0] is not None else None for lay in layers]
         gWS = [self._alloc(lay[1].shape, 0) if lay[1] is not None else None for lay in layers]
@@ -628,6 +643,13 @@ class HipT:
         gx = self._alloc((T, i), X.batch) if want_gx else None
         losses = self._alloc((T,), X.batch) if want_losses else None
         arr = lambda ts: (capi.c_tensor * n)(*[(t.h if t is not None else None) for t in ts])  # noqa: E731
+        if lens is not None:
+            la = self._rnn_lens(lens, X)
+            check(lib().to_rnn_stack_grad_ragged(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
+                                                 self._RNN_LOSS[loss], X.h, Y.h, la.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 arr(gS), arr(gWS), arr(gW), arr(gB), gx.h if gx is not None else None,
+                                                 losses.h if losses is not None else None))
+            return gS, gWS, gW, gB, gx, losses
         check(lib().to_rnn_stack_grad(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
                                       self._RNN_LOSS[loss], X.h, Y.h,
                                       arr(gS), arr(gWS), arr(gW), arr(gB), gx.h if gx is not None else None,
@@ -635,10 +657,18 @@ class HipT:
         return gS, gWS, gW, gB, gx, losses
 
     def rnn_stack_sgd(self, layers, X, Y, rate_state, rate_params, out_act="softmax", loss="crossEntropy",
-                      want_losses=False, hidden_act="logistic"):
-        """`trainNetwork'` in place (to_rnn_stack_sgd); the per-(sequence, step) losses if asked for"""
+                      want_losses=False, hidden_act="logistic", lens=None):
+        """`trainNetwork'` in place (to_rnn_stack_sgd); the per-(sequence, step) losses if asked for.  lens: on the steps
+        t < lens[b] only (to_rnn_stack_sgd_ragged)."""
         n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
         losses = self._alloc((X.shape[0],), X.batch) if want_losses else None
+        if lens is not None:
+            la = self._rnn_lens(lens, X)
+            check(lib().to_rnn_stack_sgd_ragged(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
+                                                self._RNN_LOSS[loss], X.h, Y.h, la.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                float(rate_state), float(rate_params),
+                                                losses.h if losses is not None else None))
+            return losses
         check(lib().to_rnn_stack_sgd(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
                                      self._RNN_LOSS[loss], X.h, Y.h,
                                      float(rate_state), float(rate_params), losses.h if losses is not None else None))
@@ -655,6 +685,13 @@ class HipT:
     def rnn_stats():
         p, q = C.c_int64(), C.c_int64()
         check(lib().to_rnn_stats(C.byref(p), C.byref(q)))
+        return p.value, q.value
+
+    @staticmethod
+    def rnn_ragged_stats():
+        """(persistent runs, per-step runs) of the ragged entries (to_rnn_ragged_stats)"""
+        p, q = C.c_int64(), C.c_int64()
+        check(lib().to_rnn_ragged_stats(C.byref(p), C.byref(q)))
         return p.value, q.value
 
     _RNN_FEED = {"output": 0, "argmax": 1, "sample": 2}

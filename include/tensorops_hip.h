@@ -151,6 +151,9 @@ to_status to_get_diag(to_tensor x, to_tensor* out);           /* getDiag (Types.
 to_status to_index(to_tensor x, const int64_t* index, int64_t sample, double* out); /* (!) (Types.hs:107-109) */
 /* `TT.argMax` (src/TensorOps/Tensor.hs:291-305) of a vector, per sample when batched: the
  * index of the maximum, EARLIEST index on ties (`Max (Arg x j)` keeps its left argument).
+ * NaN: the result is that left fold's (`a >= b` is false for either NaN, so a NaN is taken and its successor replaces
+ * it): n - 1 if the last element is NaN, else the earliest maximum of the elements behind the last NaN -- a function of
+ * the row alone, whatever its length or layout.  to_arg_min likewise.
  * Writes max(batch,1) indices to host memory (one download instead of the reference's
  * per-element `ixRows` traversal, Tensor.hs:220-230). */
 to_status to_arg_max(to_tensor x, int64_t* host_out);

@@ -9,8 +9,9 @@
 //   bias_act_kernel     : a hidden layer whose GEMM has no fused epilogue (the tiled fp64 kernel): h = act(z + b), act
 //                         logistic or tanh (a template parameter), in place, one elementwise launch (what the planner
 //                         does then, lazy.cpp).
-// argMax follows arg_max_rows_kernel (reduce_layout.hip) exactly -- the same per-lane fold and the same xor tree -- so a
-// class id is bit for bit what to_arg_max returns for the stored row, ties (earliest index) and NaN included.
+// argMax follows arg_max_rows_kernel (reduce_layout.hip) exactly -- the same per-lane fold and the same xor tree, and with a NaN
+// in the row the same fold again over the elements behind the last NaN -- so a class id is bit for bit what to_arg_max returns
+// for the stored row, ties (earliest index) and NaN included.
 // Every reduction has a fixed order per row: a row's result does not depend on B or on where the row sits in the batch.
 #include <algorithm>
 #include <type_traits>
@@ -47,18 +48,23 @@ __device__ __forceinline__ void am_combine(S& best, int& bi, S ob, int oi) {
 }
 
 // what lane 0 of arg_max_rows_kernel ends with for a row of n <= NP <= 32 values (value j on lane j, one each): the
-// tree's steps with offsets >= NP only meet empty lanes, the later ones are replayed here for the lanes that reach lane 0
+// tree's steps with offsets >= NP only meet empty lanes, the later ones are replayed here for the lanes that reach lane 0.
+// As there, the elements up to the last NaN of the row are out of the fold, and n - 1 is the answer when nothing is left.
 template <class S, int NP>
 __device__ __forceinline__ int arg_max_tree(const S (&v)[NP], int n) {
   S b[NP];
   int bi[NP];
+  int ln = -1;
 #pragma unroll
-  for (int j = 0; j < NP; ++j) { b[j] = v[j]; bi[j] = j < n ? j : -1; }
+  for (int j = 0; j < NP; ++j)
+    if (j < n && v[j] != v[j]) ln = j;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) { b[j] = v[j]; bi[j] = (j < n && j > ln) ? j : -1; }
 #pragma unroll
   for (int off = NP / 2; off > 0; off >>= 1)
 #pragma unroll
     for (int j = 0; j < off; ++j) am_combine(b[j], bi[j], b[j + off], bi[j + off]);
-  return bi[0];
+  return bi[0] < 0 ? n - 1 : bi[0];
 }
 
 constexpr int NARROW_LANES = 8;                 // lanes per row
@@ -182,16 +188,32 @@ __global__ __launch_bounds__(256) void infer_narrow_kernel(const S* __restrict__
   }
 }
 
-// arg_max_rows_kernel's per-lane fold and xor tree over one wave (lane j holds elements j, j + 64, ...)
-template <class S>
-__device__ __forceinline__ int wave_arg_max(S best, long bi) {
+// arg_max_rows_kernel's per-lane fold and xor tree over one wave (lane j holds elements j, j + 64, ...).  (best, bi) and ln
+// -- the last NaN the lane met, -1: none -- come from the caller's pass over the row; with a NaN in the row the fold is taken
+// again over the elements behind the last one, which val(j) gives once more.
+template <class S, class F>
+__device__ __forceinline__ int wave_arg_max(S best, long bi, long ln, int n, int lane, F val) {
+  if (__ballot(ln >= 0)) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const long ol = __shfl_xor((long long)ln, off, 64);
+      ln = ol > ln ? ol : ln;
+    }
+    best = S(0);
+    bi = -1;
+    for (int j = lane; j < n; j += 64) {
+      if (j <= ln) continue;
+      const S v = val(j);
+      if (bi < 0 || !(best >= v)) { best = v; bi = j; }
+    }
+  }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const S ob = __shfl_xor(best, off, 64);
     const long oi = __shfl_xor((long long)bi, off, 64);
     if (oi >= 0 && (bi < 0 || (oi < bi ? !(ob < best) : !(best >= ob)))) { best = ob; bi = oi; }
   }
-  return (int)bi;
+  return bi < 0 ? n - 1 : (int)bi;
 }
 
 // z and out may be the same buffer (each element is read, then written, by the same lane)
@@ -213,24 +235,31 @@ __global__ __launch_bounds__(256) void infer_rows_kernel(const S* z, long B, con
     for (int off = 32; off > 0; off >>= 1) se += __shfl_xor(se, off, 64);
   }
   S best = S(0);
-  long bi = -1;
-  for (int j = lane; j < n; j += 64) {
+  long bi = -1, ln = -1;
+  auto prob = [&](int j) {
     const S v = zr[j] + bias[j];
-    const S p = softmax ? exp_i(v - mx) / se : S(1) / (S(1) + exp_i(-v));
+    return softmax ? exp_i(v - mx) / se : S(1) / (S(1) + exp_i(-v));
+  };
+  for (int j = lane; j < n; j += 64) {
+    const S p = prob(j);
     if (out) out[row * n + j] = p;
+    if (p != p) ln = j;
     if (bi < 0 || !(best >= p)) { best = p; bi = j; }
   }
-  const int pred = wave_arg_max(best, bi);
+  // (out may be z: what this lane stored there is then the value, z itself where nothing was stored)
+  const int pred = wave_arg_max(best, bi, ln, n, lane, [&](int j) { return out ? out[row * n + j] : prob(j); });
   int actual = 0;
   if (conf) {
     const S* yr = y + row * y_sm;
     best = S(0);
     bi = -1;
+    ln = -1;
     for (int j = lane; j < n; j += 64) {
       const S t = yr[j];
+      if (t != t) ln = j;
       if (bi < 0 || !(best >= t)) { best = t; bi = j; }
     }
-    actual = wave_arg_max(best, bi);
+    actual = wave_arg_max(best, bi, ln, n, lane, [&](int j) { return yr[j]; });
   }
   if (lane != 0) return;
   if (classes) classes[row] = pred;

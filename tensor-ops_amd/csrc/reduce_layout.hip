@@ -137,7 +137,7 @@ static void sum_axis_t(int dtype, const S* x, S* out, int64_t O, int64_t R, int6
     }
   }
   if (J >= 64 && sj == 1) {
-    dim3 grid((unsigned)((J + 63) / 64), (unsigned)O);
+    dim3 grid((unsigned)((J + 63) / 64), (unsigned)O);   // (O in grid.y uncapped: the runtime takes 65,537 -- test_sum_over_a_batch_past_grid_y)
     launch_k(sum_axis_cols_kernel<S>, grid, dim3(256), 0, s, x, out, (long)R, (long)J,
                        (long)so, (long)si, (long)sj, -1L);
   } else if (R <= 256 && OJ >= 64) {
@@ -393,7 +393,11 @@ void launch_diag(int dtype, const void* x, void* out, int64_t n, int rank, hipSt
   count_launch();
 }
 
-// argMax per row, one wave per row; ties -> earliest index (see include/tensorops_hip.h)
+// argMax per row, one wave per row; ties -> earliest index (see include/tensorops_hip.h).  The result is the Max/Arg LEFT fold's
+// (`if not (best >= x[j]) take j`).  Without NaN that comparison is associative and the per-lane folds combine in a tree.  With
+// NaN it is not: a NaN is always taken and always replaced by its successor, so the fold restarts behind every NaN -- the answer
+// is n - 1 if the last element is NaN, else the earliest maximum of the suffix behind the last NaN.  A row without NaN pays one
+// ballot; one with NaN is folded again over that suffix.  infer_head.hip and rnn_generate.hip follow the same rule.
 template <class S>
 __global__ __launch_bounds__(256) void arg_max_rows_kernel(const S* __restrict__ x,
                                                            long long* __restrict__ out, long B, long n,
@@ -403,10 +407,25 @@ __global__ __launch_bounds__(256) void arg_max_rows_kernel(const S* __restrict__
   const int lane = threadIdx.x & 63;
   const S* p = x + row * bstride;
   S best = S(0);
-  long bi = -1;
+  long bi = -1, ln = -1;   // ln: the last NaN this lane met
   for (long j = lane; j < n; j += 64) {
     const S v = sgn * p[j * stride];  // sgn = -1: argMin (Min/Arg keeps the left element on ties, like Max/Arg)
+    if (v != v) ln = j;
     if (bi < 0 || !(best >= v)) { best = v; bi = j; }   // same comparison chain as the Max/Arg fold
+  }
+  if (__ballot(ln >= 0)) {   // (wave-uniform) a NaN in the row: the fold again, over the elements behind the last one
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const long ol = __shfl_xor((long long)ln, off, 64);
+      ln = ol > ln ? ol : ln;
+    }
+    best = S(0);
+    bi = -1;
+    for (long j = lane; j < n; j += 64) {
+      if (j <= ln) continue;
+      const S v = sgn * p[j * stride];
+      if (bi < 0 || !(best >= v)) { best = v; bi = j; }
+    }
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -415,7 +434,7 @@ __global__ __launch_bounds__(256) void arg_max_rows_kernel(const S* __restrict__
     // combine two partial winners: the left (smaller index) one wins unless the other is strictly greater
     if (oi >= 0 && (bi < 0 || (oi < bi ? !(ob < best) : !(best >= ob)))) { best = ob; bi = oi; }
   }
-  if (lane == 0) out[row] = bi;
+  if (lane == 0) out[row] = bi < 0 ? n - 1 : bi;   // (nothing behind the last NaN: it is the last element)
 }
 
 void launch_arg_max_rows(int dtype, const void* x, long long* out, int64_t B, int64_t n, int64_t bstride,

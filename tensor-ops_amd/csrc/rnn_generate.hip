@@ -3,8 +3,9 @@
 // stack_rnn.cpp's one-GEMM-over-all-rows forward does not apply.
 //   gen_feed       : THE feed rule (a wave per row): the next input row and, in the one-hot modes, the symbol, from the
 //                    stored previous output row.  TO_FEED_ARGMAX follows arg_max_rows_kernel (reduce_layout.hip) exactly --
-//                    the same per-lane fold and the same xor tree -- so the symbol is bit for bit what to_arg_max returns for
-//                    the stored row, ties (earliest index) and NaN included.  TO_FEED_SAMPLE is the inverse CDF of the public
+//                    the same per-lane fold and the same xor tree, and with a NaN in the row the same fold again over the
+//                    elements behind the last NaN -- so the symbol is bit for bit what to_arg_max returns for the stored row,
+//                    ties (earliest index) and NaN included.  TO_FEED_SAMPLE is the inverse CDF of the public
 //                    header, every operation sequential and in the row's dtype on one lane.
 //   feed_kernel    : route A, one launch a generated step: gen_feed over [B][n] rows in memory.
 //   rnn_gen_kernel : route B, ONE launch for the Tp prime steps and all G generated steps.  Like rnn_seq_kernel a workgroup
@@ -48,10 +49,25 @@ __device__ __forceinline__ int gen_feed(const S* row, int n, int feed, S u, S* x
   int c = 0;
   if (feed == TO_FEED_ARGMAX) {
     S best = S(0);
-    long bi = -1;
+    long bi = -1, ln = -1;   // ln: the last NaN this lane met
     for (long j = lane; j < n; j += 64) {
       const S v = row[j];
+      if (v != v) ln = j;
       if (bi < 0 || !(best >= v)) { best = v; bi = j; }
+    }
+    if (__ballot(ln >= 0)) {   // a NaN in the row: the fold again, over the elements behind the last one
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        const long ol = __shfl_xor((long long)ln, off, 64);
+        ln = ol > ln ? ol : ln;
+      }
+      best = S(0);
+      bi = -1;
+      for (long j = lane; j < n; j += 64) {
+        if (j <= ln) continue;
+        const S v = row[j];
+        if (bi < 0 || !(best >= v)) { best = v; bi = j; }
+      }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -59,7 +75,7 @@ __device__ __forceinline__ int gen_feed(const S* row, int n, int feed, S u, S* x
       const long oi = __shfl_xor((long long)bi, off, 64);
       if (oi >= 0 && (bi < 0 || (oi < bi ? !(ob < best) : !(best >= ob)))) { best = ob; bi = oi; }
     }
-    c = __shfl((int)bi, 0, 64);   // lane 0's winner is the one arg_max_rows_kernel stores
+    c = __shfl(bi < 0 ? n - 1 : (int)bi, 0, 64);   // lane 0's winner is the one arg_max_rows_kernel stores
   } else if (feed == TO_FEED_SAMPLE) {
     if (lane == 0) {   // c_0 = p_0, c_j = c_{j-1} + p_j; thr = u * c_{n-1}; the symbol = #{j : c_j <= thr}, at most n - 1
       S tot = row[0];

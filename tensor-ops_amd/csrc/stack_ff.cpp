@@ -438,21 +438,12 @@ static void ae_out_check(to_tensor t, to_tensor like, int64_t n, const std::stri
 }
 // run / decode write caller-allocated tensors while their inputs are still being read (recon == x would have the last GEMM
 // write z over the target rows): an output may overlap neither an input, nor another output, nor a parameter
-static bool ae_overlap(to_tensor s, to_tensor t) {
-  if (!s || !t || !s->ptr || !t->ptr) return false;   // (a handle without storage yet shares none)
-  auto end = [](to_tensor u) {
-    int64_t last = u->batch > 1 ? (u->batch - 1) * u->bstride : 0;
-    for (int d = 0; d < u->rank; ++d) last += (u->dims[d] - 1) * u->strides[d];
-    return static_cast<const char*>(u->ptr) + (last + 1) * (int64_t)u->esize();
-  };
-  return static_cast<const char*>(s->ptr) < end(t) && static_cast<const char*>(t->ptr) < end(s);
-}
 static void ae_no_alias(std::initializer_list<to_tensor> outs, to_tensor in, int n, const to_tensor* w, const to_tensor* b,
                         const std::string& F) {
   for (auto o = outs.begin(); o != outs.end(); ++o) {
-    bool bad = ae_overlap(*o, in);
-    for (auto q = outs.begin(); q != o; ++q) bad = bad || ae_overlap(*o, *q);
-    for (int l = 0; l < n; ++l) bad = bad || ae_overlap(*o, w[l]) || ae_overlap(*o, b[l]);
+    bool bad = stack_overlap(*o, in);
+    for (auto q = outs.begin(); q != o; ++q) bad = bad || stack_overlap(*o, *q);
+    for (int l = 0; l < n; ++l) bad = bad || stack_overlap(*o, w[l]) || stack_overlap(*o, b[l]);
     TO_CHECK(!bad, TO_ERR_ARG, F + "an output overlaps the input, another output or a parameter");
   }
 }

@@ -35,6 +35,16 @@ int64_t stack_params_check(int n_layers, const to_tensor* w, const to_tensor* b,
   return fan_in;
 }
 
+bool stack_overlap(to_tensor s, to_tensor t) {
+  if (!s || !t || !s->ptr || !t->ptr) return false;
+  auto end = [](to_tensor u) {
+    int64_t last = u->batch > 1 ? (u->batch - 1) * u->bstride : 0;
+    for (int d = 0; d < u->rank; ++d) last += (u->dims[d] - 1) * u->strides[d];
+    return static_cast<const char*>(u->ptr) + (last + 1) * (int64_t)u->esize();
+  };
+  return static_cast<const char*>(s->ptr) < end(t) && static_cast<const char*>(t->ptr) < end(s);
+}
+
 void ew2(int dt, int kind, void* out, const void* x0, const void* x1, int64_t n) {
   EwArgs a{};
   a.dtype = dt;

@@ -22,6 +22,9 @@ inline void claim(to_tensor t) { ensure(t); before_write(t); t->id = fresh_id();
 inline void* at(const void* p, int64_t elems, int64_t es) {
   return static_cast<char*>(const_cast<void*>(p)) + elems * es;
 }
+// Do the extents of s and t (first to last addressed byte) share a byte?  Null handles and handles without storage yet
+// share none.  (`overlaps` of lazy.cpp is another predicate: it treats zero-extent handles differently.)
+bool stack_overlap(to_tensor s, to_tensor t);
 // t's rows with unit element stride: t itself, or a packed copy (held by h) of a strided vector view.  Null for null.
 inline to_tensor unit_stride_rows(to_tensor t, Holder& h) {
   if (t && t->dims[0] > 1 && t->strides[0] != 1) h.t = contiguous(t);

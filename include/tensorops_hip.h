@@ -199,6 +199,20 @@ to_status to_expr_release(to_expr e);
 /* which kernel runs it: 0 = bytecode VM, 1..99 = a pre-fused functor, 100 = a kernel specialised
  * for this program at run time (hiprtc; TOPS_EXPR_JIT=0 disables) */
 to_status to_expr_kind(to_expr e, int* kind);
+/* Semantics of the piecewise opcodes, the same in every evaluator ("Elementwise semantics"): TO_X_ABS clears the
+ * sign bit (abs(-0.0) = +0.0); TO_X_SIGNUM returns a zero or a NaN operand as it is; TO_X_MAX is `a <= b ? b : a` and
+ * TO_X_MIN is `a <= b ? a : b`, the defaults of the reference's `Ord` -- with a NaN operand max gives the first operand
+ * and min the second. */
+/* Debug: which kernel form an elementwise launch of `total` output elements over `n_inputs` operands takes, and on how
+ * many workgroups of 256 threads, without launching anything.  `periods[i]` is operand i's element count (`total` when it
+ * is full-size, less for an unbatched operand broadcast under batched ones; NULL: all full-size); `all_16b_aligned`: the
+ * result and every operand start on a 16-byte boundary.  `family` is who evaluates the program: a pre-fused functor, a
+ * run-time specialised kernel, or the bytecode VM.  *second_piece: in the stream form, whether any thread handles a second
+ * 16-byte piece in its trip.  total == 0 gives *blocks = 0 (no launch).  TO_ERR_STATE before to_init. */
+enum { TO_EW_FAMILY_FUNCTOR = 0, TO_EW_FAMILY_JIT = 1, TO_EW_FAMILY_VM = 2 };
+enum { TO_EW_FORM_SCALAR = 0, TO_EW_FORM_VEC = 1, TO_EW_FORM_STREAM = 2 };
+to_status to_ewise_route_query(int dtype, int n_inputs, int64_t total, int all_16b_aligned, const int64_t* periods,
+                               int family, int* form, int64_t* blocks, int* second_piece);
 
 /* ---- batching extension (G = sum_b gradTOp(x_b, p, y_b)) ---------- */
 to_status to_batch_sum(to_tensor x, to_tensor* out);     /* [B; ns] -> ns, sum over samples */

@@ -15,6 +15,9 @@ TO_F32 = 0
 TO_F64 = 1
 # TO_GEMM_FAMILY_* by number, TO_GEMM_EPI_* by name (to_gemm_route_query)
 GEMM_FAMILIES = ("gemv", "t32", "skinnyk", "skinnyk64", "kw16", "kw", "kw64", "small", "mfma", "f64", "naive")
+# TO_EW_FAMILY_* / TO_EW_FORM_* by number (to_ewise_route_query)
+EW_FAMILIES = ("functor", "jit", "vm")
+EW_FORMS = ("scalar", "vec", "stream")
 GEMM_EPILOGUE_BITS = {"bias": 1, "act": 2, "dact": 4, "beta": 8, "rowsum": 16}
 
 # name -> argtypes ; every function returns int32 status except to_last_error
@@ -76,6 +79,8 @@ SIGNATURES = {
                         C.POINTER(c_expr)],
     "to_expr_release": [c_expr],
     "to_expr_kind": [c_expr, C.POINTER(C.c_int)],
+    "to_ewise_route_query": [C.c_int, C.c_int, C.c_int64, C.c_int, i64p, C.c_int, C.POINTER(C.c_int), i64p,
+                             C.POINTER(C.c_int)],
     "to_batch_sum": [c_tensor, C.POINTER(c_tensor)],
     "to_batch_bcast": [c_tensor, C.c_int64, C.POINTER(c_tensor)],
     "to_batch_slice": [c_tensor, C.c_int64, C.c_int64, C.POINTER(c_tensor)],

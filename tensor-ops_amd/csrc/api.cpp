@@ -1574,8 +1574,26 @@ to_status to_expr_kind(to_expr e, int* kind) {
   API_END
 }
 
+to_status to_ewise_route_query(int dtype, int n_inputs, int64_t total, int all_16b_aligned, const int64_t* periods,
+                               int family, int* form, int64_t* blocks, int* second_piece) {
+  API_BEGIN
+  require_init();
+  NONNULL(form); NONNULL(blocks); NONNULL(second_piece);
+  TO_CHECK(dtype == TO_F32 || dtype == TO_F64, TO_ERR_ARG, "unknown dtype");
+  TO_CHECK(n_inputs >= 0 && n_inputs <= 8 && total >= 0, TO_ERR_ARG, "ewise_route_query: 0..8 inputs, total >= 0");
+  TO_CHECK(family == TO_EW_FAMILY_FUNCTOR || family == TO_EW_FAMILY_JIT || family == TO_EW_FAMILY_VM, TO_ERR_ARG,
+           "ewise_route_query: unknown family");
+  for (int i = 0; periods && i < n_inputs; ++i)
+    TO_CHECK(periods[i] >= 1 && periods[i] <= std::max<int64_t>(total, 1), TO_ERR_ARG, "ewise_route_query: period out of 1..total");
+  const EwPlan pl = ew_plan(dtype, n_inputs, total, all_16b_aligned != 0, periods, family);
+  *form = pl.form;
+  *blocks = pl.blocks;
+  *second_piece = pl.second_piece ? 1 : 0;
+  API_END
+}
+
 // ---- batching ------------------------------------------------------------------------------------------
-// The sum over the hidden batch.  The DSL's backward closures know nothing of batches: with batched data the
+// The sum over the hidden batch. The DSL's backward closures know nothing of batches: with batched data the
 // cotangent of an unbatched parameter comes back batched -- for a weight matrix the per-sample outer products
 // gmul (transp x) dtdz (src/TensorOps/TOp.hs:86-88), [B x o x i] -- and the host sums it where gradTOp returns
 // (`batchSum`, hs/TensorOps/Backend/HipTensor.hs).  Inside a scope the sum is pushed into the recorded producer so

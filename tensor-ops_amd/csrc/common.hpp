@@ -401,6 +401,16 @@ struct EwArgs {
   void* jit;                // hiprtc-built kernels for this program (null: run the VM)
 };
 void launch_ewise(const EwArgs& a, hipStream_t s);
+// The routing decision of every elementwise launch, made once and apart from the launch (ewise.hip; DESIGN.md has the
+// table).  `family`: TO_EW_FAMILY_* -- the caps that differ between the pre-fused functors, the run-time specialised
+// kernels and the VM live here and nowhere else.  Host-only; to_ewise_route_query hands it out.
+struct EwPlan {
+  int form;            // TO_EW_FORM_SCALAR / _VEC / _STREAM
+  long blocks;         // workgroups of 256 threads (0: nothing to launch)
+  bool second_piece;   // stream form: some thread takes the second 16-byte piece of its trip
+};
+EwPlan ew_plan(int dtype, int n_inputs, int64_t total, bool all_16B_aligned, const int64_t* periods, int family);
+bool ew_all_aligned(const EwArgs& a);   // the result and every operand on a 16-byte boundary
 struct to_expr_s_fwd;
 void jit_launch(void* h, const EwArgs& a, hipStream_t s);
 void jit_release(void* h);

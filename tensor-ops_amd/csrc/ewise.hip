@@ -23,6 +23,8 @@ __device__ __forceinline__ float dtanh(float x) { return tanhf(x); }
 __device__ __forceinline__ double dtanh(double x) { return tanh(x); }
 __device__ __forceinline__ float dsqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double dsqrt(double x) { return sqrt(x); }
+__device__ __forceinline__ float dabs(float x) { return fabsf(x); }
+__device__ __forceinline__ double dabs(double x) { return fabs(x); }
 __device__ __forceinline__ float dfma(float a, float b, float c) { return fmaf(a, b, c); }
 __device__ __forceinline__ double dfma(double a, double b, double c) { return fma(a, b, c); }
 
@@ -197,14 +199,14 @@ __global__ __launch_bounds__(256) void ew_vm_kernel(VmIO<S> io, int n_in, const 
           case TO_X_EXP: r = dexp(a); break;
           case TO_X_LOG: r = dlog(a); break;
           case TO_X_SQRT: r = dsqrt(a); break;
-          case TO_X_ABS: r = a < S(0) ? -a : a; break;
+          case TO_X_ABS: r = dabs(a); break;
           case TO_X_SIGNUM: r = (a > S(0)) ? S(1) : ((a < S(0)) ? S(-1) : a); break;
           case TO_X_SIN: r = sin(a); break;
           case TO_X_COS: r = cos(a); break;
           case TO_X_TANH: r = dtanh(a); break;
           case TO_X_POW: r = pow(a, b); break;
-          case TO_X_MAX: r = fmax(a, b); break;
-          case TO_X_MIN: r = fmin(a, b); break;
+          case TO_X_MAX: r = a <= b ? b : a; break;   // `Ord`'s defaults, as the reference instantiates them:
+          case TO_X_MIN: r = a <= b ? a : b; break;   // an unordered pair gives max -> first operand, min -> second
           default: r = S(__builtin_nanf("")); break;
         }
       }
@@ -216,44 +218,68 @@ __global__ __launch_bounds__(256) void ew_vm_kernel(VmIO<S> io, int n_in, const 
 
 static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// ---- the routing decision ---------------------------------------------------------------------------------------------------
+// vec: every operand and the result 16-byte aligned, total and every period a multiple of V (4 floats / 2 doubles); a period
+// that is no multiple of V would put one 16-byte piece across the wrap.  stream: from 64 MiB of output.  Everything else
+// scalar, the VM always.  Blocks: one thread per element (scalar) or per piece, capped -- 2048 below the streaming size;
+// above it the functors' measured caps (one input: 32768 up to 2^25 pieces, then one trip of two pieces; two and more inputs:
+// one piece a thread) and the specialised kernels' flat 32768.
+EwPlan ew_plan(int dtype, int n_inputs, int64_t total, bool all_16B_aligned, const int64_t* periods, int family) {
+  EwPlan pl{TO_EW_FORM_SCALAR, 0, false};
+  if (total <= 0) return pl;
+  const long esz = dtype == TO_F64 ? 8 : 4, V = 16 / esz;
+  bool vec = family != TO_EW_FAMILY_VM && all_16B_aligned && total % V == 0;
+  for (int i = 0; i < n_inputs && vec && periods; ++i) vec = periods[i] % V == 0;
+  if (!vec) {
+    pl.blocks = std::min<long>((total + 255) / 256, 2048);
+    return pl;
+  }
+  const long totalv = total / V;
+  const bool streaming = total * esz >= (64L << 20);
+  long cap = streaming ? 32768 : 2048;
+  int mode = streaming ? 2 : 0;
+  if (family == TO_EW_FAMILY_FUNCTOR) {
+    // TOPS_EW_MODE (0 plain, 2 streaming) / TOPS_EW_BLOCKS override the policy (tuning knobs)
+    static const int ew_mode_env = [] { const char* e = ab_getenv("TOPS_EW_MODE"); return e ? atoi(e) : -1; }();
+    static const int ew_blocks_env = [] { const char* e = ab_getenv("TOPS_EW_BLOCKS"); return e ? atoi(e) : 0; }();
+    if (ew_mode_env >= 0) mode = ew_mode_env;
+    // (512^3 map: 16384 -> 5.88, 24576..49152 -> 5.95-6.05 TB/s.  Round 6, tools/ew_time.py: beyond 2^25 quads a thread should make ONE
+    //  trip of two pieces -- 5 x 10^8 floats 5.33 -> 6.30 TB/s, 10^9 5.56 -> 6.35 -- and with two inputs one piece: a + b over 512^3 5.31 ->
+    //  6.47, over 10^9 5.07 -> 6.06)
+    const long stream_cap = n_inputs >= 2 ? std::min<long>((totalv + 255) / 256, 1L << 20)
+                                          : (totalv <= (1L << 25) ? 32768 : std::min<long>((totalv + 511) / 512, 1L << 20));
+    cap = ew_blocks_env > 0 ? ew_blocks_env : (streaming ? stream_cap : 2048);
+  }
+  pl.blocks = std::min<long>((totalv + 255) / 256, cap);
+  pl.form = (mode == 2 && totalv >= (1 << 20)) ? TO_EW_FORM_STREAM : TO_EW_FORM_VEC;
+  pl.second_piece = pl.form == TO_EW_FORM_STREAM && totalv > pl.blocks * 256;
+  return pl;
+}
+
+bool ew_all_aligned(const EwArgs& a) {
+  bool al = al16(a.out);
+  for (int i = 0; i < a.n; ++i) al = al && al16(a.x[i]);
+  return al;
+}
+
 template <class S, int N, class F>
 static void run(const EwArgs& a, F f, hipStream_t s) {
   if (a.total == 0) return;
   constexpr int V = 16 / sizeof(S);
   EwPtrs<S> p{};
-  bool vec = (a.total % V == 0) && al16(a.out);
   for (int i = 0; i < N; ++i) {
     p.x[i] = static_cast<const S*>(a.x[i]);
     p.period[i] = a.period[i];
-    vec = vec && al16(a.x[i]) && (a.period[i] % V == 0);
   }
   S* out = static_cast<S*>(a.out);
-  // TOPS_EW_MODE (0 plain, 2 streaming) / TOPS_EW_BLOCKS override the policy (tuning knobs)
-  static const int ew_mode_env = [] { const char* e = ab_getenv("TOPS_EW_MODE"); return e ? atoi(e) : -1; }();
-  static const int ew_blocks_env = [] { const char* e = ab_getenv("TOPS_EW_BLOCKS"); return e ? atoi(e) : 0; }();
-  if (vec) {
-    const long totalv = a.total / V;
-    const bool streaming = a.total * (long)sizeof(S) >= (64L << 20);
-    const int mode = ew_mode_env >= 0 ? ew_mode_env : (streaming ? 2 : 0);
-    // (512^3 map: 16384 -> 5.88, 24576..49152 -> 5.95-6.05 TB/s.  Round 6, tools/ew_time.py: beyond 2^25 quads a thread should make ONE
-    //  trip of two pieces -- 5 x 10^8 floats 5.33 -> 6.30 TB/s, 10^9 5.56 -> 6.35 -- and with two inputs one piece: a + b over 512^3 5.31 ->
-    //  6.47, over 10^9 5.07 -> 6.06)
-    const long stream_cap = N >= 2 ? std::min<long>((totalv + 255) / 256, 1L << 20) : (totalv <= (1L << 25) ? 32768 : std::min<long>((totalv + 511) / 512, 1L << 20));
-    const long cap = ew_blocks_env > 0 ? ew_blocks_env : (streaming ? stream_cap : 2048);
-    long blocks = (totalv + 255) / 256;
-    if (blocks > cap) blocks = cap;
-    if (mode == 2 && totalv >= (1 << 20))
-      launch_k((ew_stream_kernel<S, N, F>), dim3((unsigned)blocks), dim3(256), 0, s, p, out, totalv,
-                         (long)a.total, f);
-    else
-      launch_k((ew_vec_kernel<S, N, F>), dim3((unsigned)blocks), dim3(256), 0, s, p, out, totalv,
-                         (long)a.total, f);
-  } else {
-    long blocks = (a.total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    launch_k((ew_scalar_kernel<S, N, F>), dim3((unsigned)blocks), dim3(256), 0, s, p, out,
-                       (long)a.total, f);
-  }
+  const EwPlan pl = ew_plan(a.dtype, N, a.total, ew_all_aligned(a), a.period, TO_EW_FAMILY_FUNCTOR);
+  const dim3 grid((unsigned)pl.blocks);
+  if (pl.form == TO_EW_FORM_STREAM)
+    launch_k((ew_stream_kernel<S, N, F>), grid, dim3(256), 0, s, p, out, (long)(a.total / V), (long)a.total, f);
+  else if (pl.form == TO_EW_FORM_VEC)
+    launch_k((ew_vec_kernel<S, N, F>), grid, dim3(256), 0, s, p, out, (long)(a.total / V), (long)a.total, f);
+  else
+    launch_k((ew_scalar_kernel<S, N, F>), grid, dim3(256), 0, s, p, out, (long)a.total, f);
   TO_HIP(hipGetLastError());
   count_launch();
 }
@@ -304,9 +330,13 @@ static void launch_ewise_t(const EwArgs& a, hipStream_t s) {
     io.x[i] = static_cast<const S*>(a.x[i]);
     io.period[i] = a.period[i];
   }
-  long blocks = (a.total + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
+  const long blocks = ew_plan(a.dtype, a.n, a.total, false, a.period, TO_EW_FAMILY_VM).blocks;
   const size_t lds = (size_t)a.n_slots * 256 * sizeof(S);
+  static bool attr = false;   // up to 96 KiB of dynamic LDS (the slot limit above); set as every kernel past 64 KiB sets it
+  if (!attr) {
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ew_vm_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 4 * 256));
+    attr = true;
+  }
   launch_k(ew_vm_kernel<S>, dim3((unsigned)blocks), dim3(256), lds, s, io, a.n, a.d_code,
                      static_cast<const S*>(a.d_consts), a.n_instr, a.result_slot, static_cast<S*>(a.out),
                      (long)a.total);

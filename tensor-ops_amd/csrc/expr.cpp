@@ -18,39 +18,39 @@
 
 namespace to {
 
+// one instruction in double: THE host semantics of every opcode (classification, constant folding).  ABS clears the sign
+// bit; MAX / MIN are `Ord`'s defaults of the reference, `a <= b ? b : a` and `a <= b ? a : b` -- with a NaN operand max gives
+// the first operand and min the second; the device evaluators (ewise.hip, expr_jit.cpp) spell them the same way.
+static double eval_op(int op, double a, double b) {
+  switch (op) {
+    case TO_X_ADD: return a + b;
+    case TO_X_SUB: return a - b;
+    case TO_X_MUL: return a * b;
+    case TO_X_DIV: return a / b;
+    case TO_X_NEG: return -a;
+    case TO_X_RECIP: return 1.0 / a;
+    case TO_X_EXP: return std::exp(a);
+    case TO_X_LOG: return std::log(a);
+    case TO_X_SQRT: return std::sqrt(a);
+    case TO_X_ABS: return std::fabs(a);
+    case TO_X_SIGNUM: return (a > 0) ? 1.0 : ((a < 0) ? -1.0 : a);
+    case TO_X_SIN: return std::sin(a);
+    case TO_X_COS: return std::cos(a);
+    case TO_X_TANH: return std::tanh(a);
+    case TO_X_POW: return std::pow(a, b);
+    case TO_X_MAX: return a <= b ? b : a;
+    case TO_X_MIN: return a <= b ? a : b;
+    default: return NAN;
+  }
+}
+
 double expr_eval(const to_expr_s& e, const double* x) {
   const int n = (int)(e.code.size() / 3);
   std::vector<double> v(e.arity + n);
   for (int i = 0; i < e.arity; ++i) v[i] = x[i];
   for (int i = 0; i < n; ++i) {
     const int op = e.code[3 * i], ia = e.code[3 * i + 1], ib = e.code[3 * i + 2];
-    double r;
-    if (op == TO_X_CONST) {
-      r = e.consts[ia];
-    } else {
-      const double a = v[ia], b = v[ib];
-      switch (op) {
-        case TO_X_ADD: r = a + b; break;
-        case TO_X_SUB: r = a - b; break;
-        case TO_X_MUL: r = a * b; break;
-        case TO_X_DIV: r = a / b; break;
-        case TO_X_NEG: r = -a; break;
-        case TO_X_RECIP: r = 1.0 / a; break;
-        case TO_X_EXP: r = std::exp(a); break;
-        case TO_X_LOG: r = std::log(a); break;
-        case TO_X_SQRT: r = std::sqrt(a); break;
-        case TO_X_ABS: r = std::fabs(a); break;
-        case TO_X_SIGNUM: r = (a > 0) ? 1.0 : ((a < 0) ? -1.0 : a); break;
-        case TO_X_SIN: r = std::sin(a); break;
-        case TO_X_COS: r = std::cos(a); break;
-        case TO_X_TANH: r = std::tanh(a); break;
-        case TO_X_POW: r = std::pow(a, b); break;
-        case TO_X_MAX: r = std::fmax(a, b); break;
-        case TO_X_MIN: r = std::fmin(a, b); break;
-        default: r = NAN; break;
-      }
-    }
-    v[e.arity + i] = r;
+    v[e.arity + i] = op == TO_X_CONST ? e.consts[ia] : eval_op(op, v[ia], v[ib]);
   }
   return v.empty() ? 0.0 : v.back();
 }
@@ -97,6 +97,61 @@ bool expr_is_smooth(const to_expr_s& e) {
   return true;
 }
 
+// (coefficients, constant) of an affine program, carried through it symbolically: inputs are unit vectors, ADD / SUB / NEG
+// act on both parts, MUL and DIV by a value without coefficients (a constant as written or folded) scale them, and any
+// other instruction is folded when all its operands are constants and ends the attempt otherwise.  The coefficients are the
+// numbers the program was written with: probing it (f(e_i) - f(0)) loses |c| / |a_i| of their digits -- `1 + 1e-6 x` came out
+// with a relative error of 8e-11 in its slope, which `matches` accepts on [-2, 2] and x = 1e6 does not forgive.  What this
+// cannot follow ((x + 1)^2 - x^2, say) is not run as an affine functor; `matches` stays as the guard behind it.
+static bool affine_form(const to_expr_s& e, double* a_out, double* c_out) {
+  struct Aff { double a[4]; double c; };
+  const int n = (int)(e.code.size() / 3), ar = e.arity;
+  if (ar > 4) return false;
+  std::vector<Aff> v(ar + n);
+  for (int i = 0; i < ar; ++i) {
+    v[i] = Aff{{0, 0, 0, 0}, 0};
+    v[i].a[i] = 1.0;
+  }
+  auto constant = [](const Aff& x) { return x.a[0] == 0 && x.a[1] == 0 && x.a[2] == 0 && x.a[3] == 0; };
+  for (int i = 0; i < n; ++i) {
+    const int op = e.code[3 * i];
+    Aff r{{0, 0, 0, 0}, 0};
+    if (op == TO_X_CONST) {
+      r.c = e.consts[e.code[3 * i + 1]];
+    } else {
+      const Aff &A = v[e.code[3 * i + 1]], &B = v[e.code[3 * i + 2]];
+      if (constant(A) && (constant(B) || op == TO_X_NEG || op == TO_X_RECIP || (op >= TO_X_EXP && op <= TO_X_TANH))) {
+        r.c = eval_op(op, A.c, B.c);   // folded, as expr_eval would
+      } else if (op == TO_X_ADD || op == TO_X_SUB) {
+        const double sg = op == TO_X_ADD ? 1.0 : -1.0;
+        for (int k = 0; k < 4; ++k) r.a[k] = A.a[k] + sg * B.a[k];
+        r.c = A.c + sg * B.c;
+      } else if (op == TO_X_NEG) {
+        for (int k = 0; k < 4; ++k) r.a[k] = -A.a[k];
+        r.c = -A.c;
+      } else if (op == TO_X_MUL && (constant(A) || constant(B))) {
+        const Aff& K = constant(A) ? A : B;
+        const Aff& X = constant(A) ? B : A;
+        for (int k = 0; k < 4; ++k) r.a[k] = K.c * X.a[k];
+        r.c = K.c * X.c;
+      } else if (op == TO_X_DIV && constant(B)) {
+        for (int k = 0; k < 4; ++k) r.a[k] = A.a[k] / B.c;
+        r.c = A.c / B.c;
+      } else {
+        return false;
+      }
+    }
+    for (int k = 0; k < 4; ++k)
+      if (!std::isfinite(r.a[k])) return false;
+    if (!std::isfinite(r.c)) return false;
+    v[ar + i] = r;
+  }
+  if (v.empty()) return false;
+  for (int k = 0; k < 4; ++k) a_out[k] = v.back().a[k];
+  *c_out = v.back().c;
+  return true;
+}
+
 static void classify(to_expr_s& e) {
   e.kind = EW_VM;
   const int n = e.arity;
@@ -107,17 +162,8 @@ static void classify(to_expr_s& e) {
     return;
   }
   if (n <= 4) {  // affine: c + sum a_i x_i
-    double zero[8] = {0};
-    const double c = expr_eval(e, zero);
-    double a[4] = {0, 0, 0, 0};
-    bool ok = std::isfinite(c);
-    for (int i = 0; i < n && ok; ++i) {
-      double x[8] = {0};
-      x[i] = 1.0;
-      a[i] = expr_eval(e, x) - c;
-      ok = std::isfinite(a[i]);
-    }
-    if (ok && matches(e, [&](const double* x) {
+    double a[4] = {0, 0, 0, 0}, c = 0;
+    if (affine_form(e, a, &c) && matches(e, [&](const double* x) {
           double r = c;
           for (int i = 0; i < n; ++i) r += a[i] * x[i];
           return r;

@@ -56,8 +56,8 @@ static std::string body(const to_expr_s& e, bool f64) {
       case TO_X_COS: o << "cos" << sfx << "(" << A << ")"; break;
       case TO_X_TANH: o << "tanh" << sfx << "(" << A << ")"; break;
       case TO_X_POW: o << "pow" << sfx << "(" << A << ", " << B << ")"; break;
-      case TO_X_MAX: o << "fmax" << sfx << "(" << A << ", " << B << ")"; break;
-      case TO_X_MIN: o << "fmin" << sfx << "(" << A << ", " << B << ")"; break;
+      case TO_X_MAX: o << "(" << A << " <= " << B << ") ? " << B << " : " << A; break;   // (`Ord`'s defaults: ewise.hip)
+      case TO_X_MIN: o << "(" << A << " <= " << B << ") ? " << A << " : " << B; break;
       default: o << "S(__builtin_nanf(\"\"))"; break;
     }
     o << ";\n";
@@ -194,30 +194,16 @@ std::string jit_literal(double c, bool f64) { return lit(c, f64); }
 void jit_launch(void* h, const EwArgs& a, hipStream_t s) {
   auto* k = static_cast<JitKernels*>(h);
   struct { const void* x[8]; long period[8]; } p{};
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-  const long V = a.dtype == TO_F64 ? 2 : 4, esz = a.dtype == TO_F64 ? 8 : 4;
-  bool vec = (a.total % V == 0) && al16(a.out);
   for (int i = 0; i < a.n; ++i) {
     p.x[i] = a.x[i];
     p.period[i] = a.period[i];
-    vec = vec && al16(a.x[i]) && (a.period[i] % V == 0);
   }
   void* out = a.out;
-  long total = a.total, total4 = a.total / V;
+  long total = a.total, total4 = a.total / (a.dtype == TO_F64 ? 2 : 4);
   void* args[] = {&p, &out, &total4, &total};
-  hipFunction_t f;
-  long blocks;
-  if (vec) {
-    const bool streaming = a.total * esz >= (64L << 20);
-    f = (streaming && total4 >= (1 << 20)) ? k->vecnt : k->vec;
-    blocks = (total4 + 255) / 256;
-    const long cap = streaming ? 32768 : 2048;
-    if (blocks > cap) blocks = cap;
-  } else {
-    f = k->scalar;
-    blocks = (total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-  }
+  const EwPlan pl = ew_plan(a.dtype, a.n, a.total, ew_all_aligned(a), a.period, TO_EW_FAMILY_JIT);
+  const hipFunction_t f = pl.form == TO_EW_FORM_STREAM ? k->vecnt : (pl.form == TO_EW_FORM_VEC ? k->vec : k->scalar);
+  const long blocks = pl.blocks;
   TO_HIP(hipModuleLaunchKernel(f, (unsigned)blocks, 1, 1, 256, 1, 1, 0, s, args, nullptr));
   count_launch();
 }

@@ -858,6 +858,15 @@ class HipT:
         return {"families": None if nl.value < 0 else [capi.GEMM_FAMILIES[fam[i]] for i in range(nl.value)],
                 "epilogue_ok": bool(ok.value), "small_route": bool(small.value), "split_workspace": bool(ws.value)}
 
+    def ewise_route(self, total, n_inputs, family="functor", periods=None, aligned=True, dtype=None):
+        """Debug (to_ewise_route_query): (form, blocks, second piece?) of an elementwise launch, launching nothing."""
+        dt = self.to_dtype if dtype is None else (capi.TO_F64 if dtype in ("f64", capi.TO_F64) else capi.TO_F32)
+        per = None if periods is None else (C.c_int64 * max(len(periods), 1))(*[int(p) for p in periods])
+        form, blocks, second = C.c_int(), C.c_int64(), C.c_int()
+        check(lib().to_ewise_route_query(dt, n_inputs, int(total), int(bool(aligned)), per, capi.EW_FAMILIES.index(family),
+                                         C.byref(form), C.byref(blocks), C.byref(second)))
+        return capi.EW_FORMS[form.value], blocks.value, bool(second.value)
+
     def transfer_stats(self):
         v = [C.c_int64() for _ in range(4)]
         check(lib().to_transfer_stats(*[C.byref(x) for x in v]))

@@ -93,8 +93,8 @@ inline Expr cos(const Expr& a) { return expr_un(TO_X_COS, a, [](double x) { retu
 inline Expr tanh(const Expr& a) { return expr_un(TO_X_TANH, a, [](double x) { return std::tanh(x); }); }
 inline Expr recip(const Expr& a) { return expr_un(TO_X_RECIP, a, [](double x) { return 1.0 / x; }); }
 inline Expr pow(const Expr& a, const Expr& b) { return expr_bin(TO_X_POW, a, b, [](double x, double y) { return std::pow(x, y); }); }
-inline Expr max(const Expr& a, const Expr& b) { return expr_bin(TO_X_MAX, a, b, [](double x, double y) { return std::fmax(x, y); }); }
-inline Expr min(const Expr& a, const Expr& b) { return expr_bin(TO_X_MIN, a, b, [](double x, double y) { return std::fmin(x, y); }); }
+inline Expr max(const Expr& a, const Expr& b) { return expr_bin(TO_X_MAX, a, b, [](double x, double y) { return x <= y ? y : x; }); }
+inline Expr min(const Expr& a, const Expr& b) { return expr_bin(TO_X_MIN, a, b, [](double x, double y) { return x <= y ? x : y; }); }
 
 // the same vocabulary at `double`, so one generic closure serves host evaluation too
 inline double exp(double x) { return std::exp(x); }
@@ -107,8 +107,8 @@ inline double cos(double x) { return std::cos(x); }
 inline double tanh(double x) { return std::tanh(x); }
 inline double recip(double x) { return 1.0 / x; }
 inline double pow(double x, double y) { return std::pow(x, y); }
-inline double max(double x, double y) { return std::fmax(x, y); }
-inline double min(double x, double y) { return std::fmin(x, y); }
+inline double max(double x, double y) { return x <= y ? y : x; }   // (`Ord`'s defaults, as the library's evaluators)
+inline double min(double x, double y) { return x <= y ? x : y; }
 
 // ---- forward-mode dual numbers ----------------------------------------------------------
 template <class A>

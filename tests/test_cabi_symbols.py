@@ -68,6 +68,18 @@ def test_route_query_refuses_before_init(built):
     assert got.decode().startswith("4 [-7, -7, -7, -7] ") and "to_init" in got.decode(), got   # 4: TO_ERR_STATE
 
 
+def test_ewise_route_query_refuses_before_init(built):
+    """The elementwise routing query launches nothing and reads no device state, but it is part of the library's debug
+    surface like the contraction query: TO_ERR_STATE before to_init, outputs untouched."""
+    import sys
+    code = ("import ctypes as C; from tensor_ops_amd import capi; L = capi.lib(); "
+            "form, blocks, second = C.c_int(-7), C.c_int64(-7), C.c_int(-7); "
+            "st = L.to_ewise_route_query(0, 1, 1024, 1, None, 0, C.byref(form), C.byref(blocks), C.byref(second)); "
+            "print(st, [form.value, blocks.value, second.value], L.to_last_error().decode())")
+    got = subprocess.check_output([sys.executable, "-c", code], cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert got.decode().startswith("4 [-7, -7, -7] ") and "to_init" in got.decode(), got   # 4: TO_ERR_STATE
+
+
 def test_kernels_are_gfx950(built):
     """The shared object carries gfx950 code objects only (no other arch, no generic fallback)."""
     blob = open(built, "rb").read()

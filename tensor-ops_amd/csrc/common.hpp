@@ -337,32 +337,12 @@ bool gemm_f64_w4_full_rounds(const GemmProblem& p);
 
 // The hidden / state activations of the one-call stack entries (to_fflayer_stack_*, to_rnn_stack_*), numbered like
 // GemmProblem::dact_kind (GemmProblem::act is this + 1).  The persistent kernels and the loss head's fused tail take the
-// number as a template parameter.  The tanh pair -- the value, and the derivative FROM THE STORED OUTPUT -- is what the GEMM
-// epilogues compute (tanhf / tanh, 1 - h h): every route of an entry computes the same function.  A further activation
-// whose derivative can be written on its output goes here.
+// number as a template parameter.  The device functions behind the numbers are devmath.hpp's; a further activation whose
+// derivative can be written on its output gets its number here and its pair there.
 constexpr int ACT_KIND_LOGISTIC = 0, ACT_KIND_TANH = 1;
 // No activation (an autoencoder's linear code layer): GemmProblem::act = this + 1 = 0, and no dact / tail behind it.  The host
 // side's per-layer number only; no kernel takes it as dact_kind / tail_kind.
 constexpr int ACT_KIND_IDENTITY = -1;
-__device__ __forceinline__ float tanh_act(float z) { return tanhf(z); }
-__device__ __forceinline__ double tanh_act(double z) { return tanh(z); }
-__device__ __forceinline__ float tanh_dact(float h) { return 1.0f - h * h; }
-__device__ __forceinline__ double tanh_dact(double h) { return 1.0 - h * h; }
-// The two persistent per-sample kernels (online_sgd.hip, induce_seq.hip) share their logistic -- the fast exponential in
-// fp32 -- and the dispatch on the hidden activation: the value, and `s * act'` written on the stored output h.
-// (rnn_seq.hip's logistic calls expf and stays its own.)
-__device__ __forceinline__ float logistic_f(float z) { return 1.0f / (1.0f + __expf(-z)); }
-__device__ __forceinline__ double logistic_f(double z) { return 1.0 / (1.0 + exp(-z)); }
-template <int ACT, class S>
-__device__ __forceinline__ S hid_act(S z) {
-  if constexpr (ACT == ACT_KIND_TANH) return tanh_act(z);
-  else return logistic_f(z);
-}
-template <int ACT, class S>
-__device__ __forceinline__ S hid_dact(S s, S h) {
-  if constexpr (ACT == ACT_KIND_TANH) return s * tanh_dact(h);
-  else return s * h * (S(1.0) - h);
-}
 
 // elementwise
 enum EwKind {

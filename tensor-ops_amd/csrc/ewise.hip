@@ -12,21 +12,9 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
-
-__device__ __forceinline__ float dexp(float x) { return expf(x); }
-__device__ __forceinline__ double dexp(double x) { return exp(x); }
-__device__ __forceinline__ float dlog(float x) { return logf(x); }
-__device__ __forceinline__ double dlog(double x) { return log(x); }
-__device__ __forceinline__ float dtanh(float x) { return tanhf(x); }
-__device__ __forceinline__ double dtanh(double x) { return tanh(x); }
-__device__ __forceinline__ float dsqrt(float x) { return sqrtf(x); }
-__device__ __forceinline__ double dsqrt(double x) { return sqrt(x); }
-__device__ __forceinline__ float dabs(float x) { return fabsf(x); }
-__device__ __forceinline__ double dabs(double x) { return fabs(x); }
-__device__ __forceinline__ float dfma(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double dfma(double a, double b, double c) { return fma(a, b, c); }
 
 template <class S>
 struct FAffine {
@@ -37,26 +25,26 @@ struct FAffine {
     S r = c;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      if (i < n) r = dfma(a[i], x[i], r);
+      if (i < n) r = dm::fma(a[i], x[i], r);
     return r;
   }
 };
 template <class S> struct FMul { __device__ __forceinline__ S operator()(const S* x) const { return x[0] * x[1]; } };
 template <class S> struct FDiv { __device__ __forceinline__ S operator()(const S* x) const { return x[0] / x[1]; } };
-template <class S> struct FExp { __device__ __forceinline__ S operator()(const S* x) const { return dexp(x[0]); } };
-template <class S> struct FLog { __device__ __forceinline__ S operator()(const S* x) const { return dlog(x[0]); } };
+template <class S> struct FExp { __device__ __forceinline__ S operator()(const S* x) const { return dm::exp(x[0]); } };
+template <class S> struct FLog { __device__ __forceinline__ S operator()(const S* x) const { return dm::log(x[0]); } };
 template <class S> struct FRecip { __device__ __forceinline__ S operator()(const S* x) const { return S(1) / x[0]; } };
-template <class S> struct FTanh { __device__ __forceinline__ S operator()(const S* x) const { return dtanh(x[0]); } };
-template <class S> struct FSqrt { __device__ __forceinline__ S operator()(const S* x) const { return dsqrt(x[0]); } };
+template <class S> struct FTanh { __device__ __forceinline__ S operator()(const S* x) const { return dm::tanh(x[0]); } };
+template <class S> struct FSqrt { __device__ __forceinline__ S operator()(const S* x) const { return dm::sqrt(x[0]); } };
 // logistic x = 1 / (1 + exp (-x))   (src/TensorOps/Learn/NeuralNet.hs:42-44)
 template <class S> struct FLogistic {
-  __device__ __forceinline__ S operator()(const S* x) const { return S(1) / (S(1) + dexp(-x[0])); }
+  __device__ __forceinline__ S operator()(const S* x) const { return dm::logistic(x[0]); }
 };
 // d * logistic'(x), logistic' x = s (1 - s)   (NeuralNet.hs:46-50; the `gradLift`
 // form `\(d :* x) -> d * f' x`, src/TensorOps/Tensor.hs:127)
 template <class S> struct FMulDLogistic {
   __device__ __forceinline__ S operator()(const S* x) const {
-    const S s = S(1) / (S(1) + dexp(-x[1]));
+    const S s = dm::logistic(x[1]);
     return x[0] * (s * (S(1) - s));
   }
 };
@@ -68,7 +56,7 @@ template <class S> struct FMulHOneMinusH {
 // the same pair for tanh: d * tanh'(x) = d (1 - tanh(x)^2), and on h = tanh(x) already computed
 template <class S> struct FMulDTanh {
   __device__ __forceinline__ S operator()(const S* x) const {
-    const S t = dtanh(x[1]);
+    const S t = dm::tanh(x[1]);
     return x[0] * (S(1) - t * t);
   }
 };
@@ -196,14 +184,14 @@ __global__ __launch_bounds__(256) void ew_vm_kernel(VmIO<S> io, int n_in, const 
           case TO_X_DIV: r = a / b; break;
           case TO_X_NEG: r = -a; break;
           case TO_X_RECIP: r = S(1) / a; break;
-          case TO_X_EXP: r = dexp(a); break;
-          case TO_X_LOG: r = dlog(a); break;
-          case TO_X_SQRT: r = dsqrt(a); break;
-          case TO_X_ABS: r = dabs(a); break;
+          case TO_X_EXP: r = dm::exp(a); break;
+          case TO_X_LOG: r = dm::log(a); break;
+          case TO_X_SQRT: r = dm::sqrt(a); break;
+          case TO_X_ABS: r = dm::abs(a); break;
           case TO_X_SIGNUM: r = (a > S(0)) ? S(1) : ((a < S(0)) ? S(-1) : a); break;
           case TO_X_SIN: r = sin(a); break;
           case TO_X_COS: r = cos(a); break;
-          case TO_X_TANH: r = dtanh(a); break;
+          case TO_X_TANH: r = dm::tanh(a); break;
           case TO_X_POW: r = pow(a, b); break;
           case TO_X_MAX: r = a <= b ? b : a; break;   // `Ord`'s defaults, as the reference instantiates them:
           case TO_X_MIN: r = a <= b ? a : b; break;   // an unordered pair gives max -> first operand, min -> second

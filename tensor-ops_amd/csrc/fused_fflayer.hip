@@ -5,29 +5,9 @@
 //   logistic >>> squaredError backward: dz = -2 (y - s) s (1 - s),  s = logistic(z)
 // One wave per sample row; the row lives in registers (n <= 64 per pass, looped beyond).
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
-
-template <class S>
-__device__ __forceinline__ S wsum(S v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ double wmax(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ float exp_s(float x) { return expf(x); }
-__device__ __forceinline__ double exp_s(double x) { return exp(x); }
-__device__ __forceinline__ float log_s(float x) { return logf(x); }
-__device__ __forceinline__ double log_s(double x) { return log(x); }
 
 // kind 0: softmax + crossEntropy ; kind 1: logistic + squaredError.
 // z: [B, n] pre-activations of the last layer; y: [B, n]; dz: [B, n]; loss (optional): [B]
@@ -46,35 +26,35 @@ __global__ __launch_bounds__(256) void loss_grad_rows_kernel(const S* __restrict
     // subtracting the row max is the same value in exact arithmetic and avoids overflow
     S mx = S(-INFINITY);
     for (int j = lane; j < n; j += 64) mx = zr[j] > mx ? zr[j] : mx;
-    mx = wmax(mx);
+    mx = dm::wave_max(mx);
     S se = S(0), sy = S(0);
     for (int j = lane; j < n; j += 64) {
-      se += exp_s(zr[j] - mx);
+      se += dm::exp(zr[j] - mx);
       sy += yr[j];
     }
-    se = wsum(se);
-    sy = wsum(sy);
+    se = dm::wave_sum(se);
+    sy = dm::wave_sum(sy);
     const S inv = S(1) / se;
     S l = S(0);
     for (int j = lane; j < n; j += 64) {
-      const S p = exp_s(zr[j] - mx) * inv;
+      const S p = dm::exp(zr[j] - mx) * inv;
       dr[j] = p * sy - yr[j];
-      l -= yr[j] * log_s(p);
+      l -= yr[j] * dm::log(p);
     }
     if (loss) {
-      l = wsum(l);
+      l = dm::wave_sum(l);
       if (lane == 0) loss[row] = l;
     }
   } else {
     S l = S(0);
     for (int j = lane; j < n; j += 64) {
-      const S s = S(1) / (S(1) + exp_s(-zr[j]));
+      const S s = dm::logistic(zr[j]);
       const S e = yr[j] - s;
       dr[j] = S(-2) * e * s * (S(1) - s);
       l += e * e;
     }
     if (loss) {
-      l = wsum(l);
+      l = dm::wave_sum(l);
       if (lane == 0) loss[row] = l;
     }
   }

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -678,7 +679,7 @@ __device__ __forceinline__ void gemm_body(const GemmKArgs& g, float* smem, int t
                 if constexpr (ACT >= 0) {
                   // bias and activation ride along (the fused `map logistic (gmul ...)` of config 5 stores once)
                   v += bj[j];
-                  if constexpr (ACT == 1) v = __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+                  if constexpr (ACT == 1) v = dm::logistic_rcp(v);
                   else if constexpr (ACT == 2) v = tanhf(v);
                 }
                 Ws[lrow * LDW + wcol(j)] = v;
@@ -722,7 +723,7 @@ __device__ __forceinline__ void gemm_body(const GemmKArgs& g, float* smem, int t
           float v = g.alpha * acc[i][j][r];
           if (Ci) v += g.beta * Ci[row * g.c_sm + col];
           if (g.bias) v += g.bias[col];
-          if (g.act == 1) v = 1.0f / (1.0f + expf(-v));
+          if (g.act == 1) v = dm::logistic(v);
           else if (g.act == 2) v = tanhf(v);
           if (g.dact) {
             const float h = g.dact[(red ? 0 : (long)bz * g.c_sb) + row * g.c_sm + col];
@@ -1107,7 +1108,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_mfma_persistent_kernel(GemmK
               const int lrow = (r & 3) + 8 * ((r >> 2) & 1) + 4 * half;
               float v = g.alpha * acc[i][j][r];
               if (g.bias) v += g.bias[n0 + wn0 + j * 32 + l31];
-              if (g.act == 1) v = __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+              if (g.act == 1) v = dm::logistic_rcp(v);
               else if (g.act == 2) v = tanhf(v);
               Ws[lrow * LDW + j * 32 + l31] = v;
             }
@@ -1180,7 +1181,7 @@ __global__ void gemm_naive_kernel(NaiveArgs<S> g, long total) {
   const long off = bz * g.c_sb + m * g.c_sm + n;
   if (g.Cin) v += g.beta * g.Cin[off];
   if (g.bias) v += g.bias[n];
-  if (g.act == 1) v = S(1) / (S(1) + exp(-v));
+  if (g.act == 1) v = dm::logistic(v);
   else if (g.act == 2) v = tanh(v);
   if (g.dact) {
     const S h = g.dact[off];

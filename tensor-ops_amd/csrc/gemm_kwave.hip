@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -499,7 +500,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_kw_kernel(KwArgs g) {
           float x = g.alpha * v[e];
           if (g.cin) x += g.beta * g.cin[gr * g.c_sm + gc + e];
           if (g.bias) x += g.bias[gc + e];
-          if (g.act == 1) x = 1.0f / (1.0f + expf(-x));
+          if (g.act == 1) x = dm::logistic(x);
           else if (g.act == 2) x = tanhf(x);
           if (g.dact) {
             const float hh = g.dact[gr * g.c_sm + gc + e];

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -355,7 +356,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_kw64_kernel(Kw64Args g) {
           double x = g.alpha * v[e];
           if (g.cin) x += g.beta * g.cin[gr * g.c_sm + gc + e];
           if (g.bias) x += g.bias[gc + e];
-          if (g.act == 1) x = 1.0 / (1.0 + exp(-x));
+          if (g.act == 1) x = dm::logistic(x);
           else if (g.act == 2) x = tanh(x);
           if (g.dact) {
             const double hh = g.dact[gr * g.c_sm + gc + e];

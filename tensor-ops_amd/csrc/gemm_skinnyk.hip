@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(512) void gemm_skinnyk_kernel(SkinnyArgs g) {
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
           float v = g.alpha * acc[j][4 * p + rr] + bj[j];
-          if (ACT == 1) v = __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+          if (ACT == 1) v = dm::logistic_rcp(v);
           strip[(rr + 4 * half) * SK_ROW + j * 32 + l31] = v;
         }
 #pragma unroll

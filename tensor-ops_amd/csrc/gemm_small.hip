@@ -11,6 +11,7 @@
 // Serves the batched ffLayer step (config 3): X.W1^T, dZ^T.X, H.W2^T, dZ2^T.H, dZ2.W2.
 #include "arg_fit.hpp"
 #include "common.hpp"
+#include "devmath.hpp"
 
 #include <cstddef>
 #include <type_traits>
@@ -98,19 +99,11 @@ __device__ __forceinline__ void tile_of(const G& g, int bid, int& tile_m, int& t
   tile_n = (int)(g.tile_order == 2 ? hi : lo);
 }
 
-__device__ __forceinline__ float tanh_s(float x) { return tanhf(x); }
-__device__ __forceinline__ double tanh_s(double x) { return tanh(x); }
-__device__ __forceinline__ float exp_s(float x) { return expf(x); }
-__device__ __forceinline__ double exp_s(double x) { return exp(x); }
-__device__ __forceinline__ float log_s(float x) { return logf(x); }
-__device__ __forceinline__ double log_s(double x) { return log(x); }
-__device__ __forceinline__ float max_s(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ double max_s(double a, double b) { return fmax(a, b); }
-
 // The value of lane (l ^ OFF) within the lane's row of sixteen, OFF = 8, 4, 2, 1: what the loss head's sixteen-lane
 // butterflies exchange.  fp32: a row-local DPP move (a few cycles; the compiler folds it into the add or the max) instead
 // of __shfl_xor's ds_bpermute_b32, an LDS round trip with an lgkmcnt wait -- twelve of those in one dependent chain were
 // most of the head.  Every lane of the wave is active where the head runs.  fp64 keeps the shuffle.
+// (Not a dm:: fold: those span the wave's 64 lanes, this one a row of sixteen.)
 template <int OFF>
 __device__ __forceinline__ float xor16(float x) {
   const int v = __float_as_int(x);
@@ -611,15 +604,15 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
         S out, l;
         if (g.loss_rows == 1) {
           S mx = valid ? v : S(-INFINITY);
-          mx = max_s(mx, xor16<8>(mx)); mx = max_s(mx, xor16<4>(mx));
-          mx = max_s(mx, xor16<2>(mx)); mx = max_s(mx, xor16<1>(mx));
-          const S e = valid ? exp_s(v - mx) : S(0);
+          mx = dm::max(mx, xor16<8>(mx)); mx = dm::max(mx, xor16<4>(mx));
+          mx = dm::max(mx, xor16<2>(mx)); mx = dm::max(mx, xor16<1>(mx));
+          const S e = valid ? dm::exp(v - mx) : S(0);
           const S se = sum16(e), sy = sum16(t);
           const S pr = e / se;
           out = pr * sy - t;
-          l = valid ? -t * log_s(pr) : S(0);
+          l = valid ? -t * dm::log(pr) : S(0);
         } else {
-          const S sg = S(1) / (S(1) + exp_s(-v));
+          const S sg = dm::logistic(v);
           const S e = t - sg;
           out = S(-2) * e * sg * (S(1) - sg);
           l = valid ? e * e : S(0);
@@ -647,8 +640,8 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
       v *= g.alpha;
       if (Ci) v += g.beta * pf_ci[i];
       v += pf_bias;
-      if (g.act == 1) v = S(1) / (S(1) + exp_s(-v));
-      else if (g.act == 2) v = tanh_s(v);
+      if (g.act == 1) v = dm::logistic(v);
+      else if (g.act == 2) v = dm::tanh(v);
       if (Hd) {
         const S h = pf_hd[i];
         v *= g.dact_kind ? S(1) - h * h : h * (S(1) - h);
@@ -692,7 +685,7 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
         for (int u = 0; u < 2; ++u)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            if constexpr (TAILK == ACT_KIND_TANH) tv[u][r] = acc2[u][r] * tanh_dact(tl_hv[u][r]);
+            if constexpr (TAILK == ACT_KIND_TANH) tv[u][r] = acc2[u][r] * dm::tanh_dact(tl_hv[u][r]);
             else tv[u][r] = acc2[u][r] * tl_hv[u][r] * (S(1) - tl_hv[u][r]);
           }
         __builtin_amdgcn_sched_barrier(0);
@@ -716,7 +709,7 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
           for (int r = 0; r < 4; ++r) {
             const long row = (long)tile_m * 16 + row16(kg, r);
             if (t < ntiles && row < g.M && col < g.tail_n) {
-              if constexpr (TAILK == ACT_KIND_TANH) g.tail_out[row * g.tail_n + col] = acc2[u][r] * tanh_dact(tl_hv[u][r]);
+              if constexpr (TAILK == ACT_KIND_TANH) g.tail_out[row * g.tail_n + col] = acc2[u][r] * dm::tanh_dact(tl_hv[u][r]);
               else g.tail_out[row * g.tail_n + col] = acc2[u][r] * tl_hv[u][r] * (S(1) - tl_hv[u][r]);
             }
           }
@@ -1149,7 +1142,7 @@ __device__ __forceinline__ void gemm_small_f64_t32_body(const SmallArgsT<double>
       v *= g.alpha;
       if (Ci) v += g.beta * pf_ci[u];
       v += pf_bias[u];
-      if (g.act == 1) v = 1.0 / (1.0 + exp(-v));
+      if (g.act == 1) v = dm::logistic(v);
       else if (g.act == 2) v = tanh(v);
       if (Hd) v *= g.dact_kind ? 1.0 - pf_hd[u] * pf_hd[u] : pf_hd[u] * (1.0 - pf_hd[u]);
       Cb[row * g.c_sm + col] = v;

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "devmath.hpp"
 #include "arg_fit.hpp"
 
 namespace to {
@@ -486,8 +487,8 @@ __device__ __forceinline__ int gemm_t32_body(const T32Args& g, const int bid, fl
     if (g.Cin) v += pf_ci * g.beta;
     if (g.bias) v += pf_bias;
     if (g.act == 1) {
-      v.x = 1.f / (1.f + __expf(-v.x)); v.y = 1.f / (1.f + __expf(-v.y));
-      v.z = 1.f / (1.f + __expf(-v.z)); v.w = 1.f / (1.f + __expf(-v.w));
+      v.x = dm::logistic_fast(v.x); v.y = dm::logistic_fast(v.y);
+      v.z = dm::logistic_fast(v.z); v.w = dm::logistic_fast(v.w);
     } else if (g.act == 2) {
       v.x = tanhf(v.x); v.y = tanhf(v.y); v.z = tanhf(v.z); v.w = tanhf(v.w);
     }
@@ -612,10 +613,10 @@ __global__ __launch_bounds__(256) void gemm_t32_head_kernel(T32Args g, T32HeadAr
     if (n < h.N2) {
       z[n] = h4.x * w4[n].x + h4.y * w4[n].y + h4.z * w4[n].z + h4.w * w4[n].w;
 #pragma unroll
-      for (int off = 1; off < 64; off <<= 1) z[n] += __shfl_xor(z[n], off, 64);
+      for (int off = 1; off < 64; off <<= 1) z[n] += __shfl_xor(z[n], off, 64);   // offsets ascending: not dm::wave_sum's tree
     }
   }
-  // lane n < N2 finishes output n; the sums over the row's outputs are sixteen-lane butterflies
+  // lane n < N2 finishes output n; the sums over the row's outputs are sixteen-lane butterflies (dm::'s folds are 64 wide)
   float v = -INFINITY;
 #pragma unroll
   for (int n = 0; n < 16; ++n)
@@ -637,7 +638,7 @@ __global__ __launch_bounds__(256) void gemm_t32_head_kernel(T32Args g, T32HeadAr
     out_l = lv ? pr * sy - t_l : 0.f;
     loss_l = lv ? -t_l * logf(pr) : 0.f;
   } else {
-    const float sg = 1.f / (1.f + expf(-v));
+    const float sg = dm::logistic(v);
     const float e = t_l - sg;
     out_l = lv ? -2.f * e * sg * (1.f - sg) : 0.f;
     loss_l = lv ? e * e : 0.f;

@@ -20,6 +20,7 @@
 // `outer_kernel`: C[m][n] = alpha a[m] b[n] (K = 1), four columns a thread, 16-byte stores, a few rows per workgroup; with the rank
 // as a template parameter (8 or 16 rows of b in registers) also the rank-2 .. 15 update below the MFMA kernels' K of 16.
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -43,7 +44,7 @@ __device__ __forceinline__ S gemv_epilogue(const GemvArgs& g, S acc, long o) {
   S v = (S)g.alpha * acc;
   if (g.beta != 0.0) v += (S)g.beta * static_cast<const S*>(g.out_in)[o * g.ys];
   if (g.bias) v += static_cast<const S*>(g.bias)[g.bias_per_out ? o : 0];
-  if (g.act == 1) v = S(1) / (S(1) + exp(-v));
+  if (g.act == 1) v = dm::logistic(v);
   else if (g.act == 2) v = tanh(v);
   return v;
 }
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(GemvArgs g) {
     for (long r = r0 + l; r < r1; r += LPR) acc += v ? row[r] * v[r * g.vs] : row[r];
   }
 #pragma unroll
-  for (int d = LPR / 2; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+  for (int d = LPR / 2; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);   // the row's LPR lanes, not dm::wave_sum's 64
   if (l == 0) {
     if (gridDim.y > 1) static_cast<S*>(g.part)[(long)blockIdx.y * g.OUT + o] = acc;
     else static_cast<S*>(g.out)[o * g.ys] = gemv_epilogue<S>(g, acc, o);
@@ -239,7 +240,7 @@ __global__ __launch_bounds__(256) void outer_kernel(OuterArgs g) {
 #pragma unroll
       for (int e = 0; e < W; ++e) {
         if (g.beta != 0.0) v[e] += (S)g.beta * static_cast<const S*>(g.Cin)[m * g.c_sm + n + e];
-        if (g.act == 1) v[e] = S(1) / (S(1) + exp(-v[e]));
+        if (g.act == 1) v[e] = dm::logistic(v[e]);
         else if (g.act == 2) v[e] = tanh(v[e]);
       }
     }

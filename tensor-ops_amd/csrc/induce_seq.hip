@@ -11,7 +11,7 @@
 //   * forward: every workgroup puts its partial product W_1[:, J_g] x[J_g] (o1 numbers) into an exchange buffer and then
 //     sums the G partials in workgroup order (every workgroup gets the same bits): z_1.  ONE exchange per iteration;
 //   * layers 2..L, the head, the loss and the cotangents back to dz_1 are replicated in every workgroup; the hidden
-//     activation is a template parameter of the kernel: logistic (h (1 - h) backward) or tanh (1 - h h; common.hpp);
+//     activation is a template parameter of the kernel: logistic (h (1 - h) backward) or tanh (1 - h h; devmath.hpp);
 //   * G == 1 (the stack fits one workgroup's LDS) is the same kernel without any exchange: independent workgroups, as many
 //     as there are rows (up to 256), each walking its share of the rows.  With G > 1 one group -- the workgroups with
 //     blockIdx.x % 8 == 0 of a grid of 8 G, the others leave at once -- takes the rows one after the other.
@@ -31,6 +31,7 @@
 // The automatic rule (which shapes take this route by default) is in stack_ff.cpp beside the measurements it was derived from
 // (tools/induce_scan.py, profiles/r08_induce_scan.txt).
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -59,21 +60,6 @@ struct InduceArgs {
   long long timeout; // wall_clock64 ticks
 };
 
-// (logistic_f, hid_act<ACT>, hid_dact<ACT>: common.hpp, shared by the two persistent per-sample kernels)
-__device__ __forceinline__ float exp_f(float z) { return __expf(z); }
-__device__ __forceinline__ double exp_f(double z) { return exp(z); }
-__device__ __forceinline__ float log_f(float z) { return logf(z); }
-__device__ __forceinline__ double log_f(double z) { return log(z); }
-__device__ __forceinline__ float fma_f(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double fma_f(double a, double b, double c) { return fma(a, b, c); }
-
-template <class S>
-__device__ __forceinline__ S wave_sum(S v) {   // the sum over the 64 lanes, in every lane
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // out(j) = sum_k W[j * ld + k] x[k], j < O.  K >= 64: one wave per row, four chains per lane; else one thread per row
 // (ld is odd: the rows of consecutive threads start in different banks).  No barrier inside.
 template <class S, class F>
@@ -85,20 +71,20 @@ __device__ __forceinline__ void matvec(const S* __restrict__ W, int ld, int O, i
       S a0 = S(0.), a1 = S(0.), a2 = S(0.), a3 = S(0.);
       int k = lane;
       for (; k + 192 < K; k += 256) {
-        a0 = fma_f(w[k], x[k], a0);
-        a1 = fma_f(w[k + 64], x[k + 64], a1);
-        a2 = fma_f(w[k + 128], x[k + 128], a2);
-        a3 = fma_f(w[k + 192], x[k + 192], a3);
+        a0 = dm::fma(w[k], x[k], a0);
+        a1 = dm::fma(w[k + 64], x[k + 64], a1);
+        a2 = dm::fma(w[k + 128], x[k + 128], a2);
+        a3 = dm::fma(w[k + 192], x[k + 192], a3);
       }
-      for (; k < K; k += 64) a0 = fma_f(w[k], x[k], a0);
-      const S acc = wave_sum((a0 + a1) + (a2 + a3));
+      for (; k < K; k += 64) a0 = dm::fma(w[k], x[k], a0);
+      const S acc = dm::wave_sum((a0 + a1) + (a2 + a3));
       if (lane == 0) put(j, acc);
     }
   } else {
     for (int j = tid; j < O; j += IN_THREADS) {
       const S* __restrict__ w = W + (long)j * ld;
       S acc = S(0.);
-      for (int k = 0; k < K; ++k) acc = fma_f(w[k], x[k], acc);
+      for (int k = 0; k < K; ++k) acc = dm::fma(w[k], x[k], acc);
       put(j, acc);
     }
   }
@@ -116,7 +102,7 @@ __device__ __forceinline__ void matvec_t(const S* __restrict__ W, int ld, int O,
   if (nch <= 1) {
     for (int k = tid; k < K; k += IN_THREADS) {
       S s = S(0.);
-      for (int j = 0; j < O; ++j) s = fma_f(W[(long)j * ld + k], d[j], s);
+      for (int j = 0; j < O; ++j) s = dm::fma(W[(long)j * ld + k], d[j], s);
       put(k, s);
     }
     return;
@@ -126,7 +112,7 @@ __device__ __forceinline__ void matvec_t(const S* __restrict__ W, int ld, int O,
     const int q = tid / K, k = tid - q * K;
     const int j1 = (q + 1) * len < O ? (q + 1) * len : O;
     S s = S(0.);
-    for (int j = q * len; j < j1; ++j) s = fma_f(W[(long)j * ld + k], d[j], s);
+    for (int j = q * len; j < j1; ++j) s = dm::fma(W[(long)j * ld + k], d[j], s);
     scr[q * K + k] = s;
   }
   __syncthreads();
@@ -252,7 +238,7 @@ __global__ __launch_bounds__(IN_THREADS) void induce_seq_kernel(InduceArgs<S> a)
             }
           }
           z += bb[0][j];
-          act[1][j] = L == 1 ? z : hid_act<ACT>(z);
+          act[1][j] = L == 1 ? z : dm::hid_act_fast<ACT>(z);
         }
         if (!ok) {
           a.status[1] = row;
@@ -267,7 +253,7 @@ __global__ __launch_bounds__(IN_THREADS) void induce_seq_kernel(InduceArgs<S> a)
         const bool last = l + 1 == L;
         matvec(Wl[l], ld[l], a.dims[l + 1], a.dims[l], act[l], [&](int j, S v) {
           const S z = v + bb[l][j];
-          act[l + 1][j] = last ? z : hid_act<ACT>(z);
+          act[l + 1][j] = last ? z : dm::hid_act_fast<ACT>(z);
         });
         __syncthreads();
       }
@@ -282,19 +268,19 @@ __global__ __launch_bounds__(IN_THREADS) void induce_seq_kernel(InduceArgs<S> a)
             const S other = __shfl_xor(mx, off);
             mx = mx > other ? mx : other;
           }
-          const S sy = wave_sum(y);
-          const S e = lane < oL ? exp_f(z - mx) : S(0.);
-          const S se = wave_sum(e);
+          const S sy = dm::wave_sum(y);
+          const S e = lane < oL ? dm::exp_fast(z - mx) : S(0.);
+          const S se = dm::wave_sum(e);
           d = e / se * sy - y;                                      // softmax(z) * sum(y) - y
-          lossv = lane < oL ? y * (log_f(se) - (z - mx)) : S(0.);   // -y log softmax(z)
+          lossv = lane < oL ? y * (dm::log(se) - (z - mx)) : S(0.);   // -y log softmax(z)
         } else {
-          const S s = logistic_f(z), e = y - s;
+          const S s = dm::logistic_fast(z), e = y - s;
           d = -S(2.0) * e * s * (S(1.0) - s);                       // logistic >>> squaredError
           lossv = lane < oL ? e * e : S(0.);
         }
         if (lane < oL) dz[L][lane] = d;
         if (a.losses && g == 0) {
-          lossv = wave_sum(lossv);
+          lossv = dm::wave_sum(lossv);
           if (lane == 0) a.losses[row * a.iters + k] = lossv;
         }
       }
@@ -303,7 +289,7 @@ __global__ __launch_bounds__(IN_THREADS) void induce_seq_kernel(InduceArgs<S> a)
       for (int l = L - 1; l >= 1; --l) {
         matvec_t(Wl[l], ld[l], a.dims[l + 1], a.dims[l], dz[l + 1], scr, [&](int kk, S s) {
           const S h = act[l][kk];
-          dz[l][kk] = hid_dact<ACT>(s, h);
+          dz[l][kk] = dm::hid_dact_fast<ACT>(s, h);
         });
         __syncthreads();
       }

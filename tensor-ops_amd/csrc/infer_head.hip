@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -27,13 +28,6 @@ namespace {
     if ((dtype) == TO_F64) { using S = double; CALL; } \
     else { using S = float; CALL; }                    \
   } while (0)
-
-__device__ __forceinline__ float exp_i(float x) { return expf(x); }
-__device__ __forceinline__ double exp_i(double x) { return exp(x); }
-__device__ __forceinline__ float max_i(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ double max_i(double a, double b) { return fmax(a, b); }
-__device__ __forceinline__ float fma_i(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double fma_i(double a, double b, double c) { return fma(a, b, c); }
 
 template <class S>
 struct alignas(16) Vec16 {  // one 16-byte load: 4 floats / 2 doubles
@@ -136,7 +130,7 @@ __global__ __launch_bounds__(256) void infer_narrow_kernel(const S* __restrict__
             if (j >= n) break;
             const Vec16<S> w = *reinterpret_cast<const Vec16<S>*>(Wl + (long)j * Kc + kk);
 #pragma unroll
-            for (int e = 0; e < V; ++e) acc[j] = fma_i(av[u][e], w.v[e], acc[j]);
+            for (int e = 0; e < V; ++e) acc[j] = dm::fma(av[u][e], w.v[e], acc[j]);
           }
         }
       }
@@ -154,16 +148,16 @@ __global__ __launch_bounds__(256) void infer_narrow_kernel(const S* __restrict__
       S mx = S(-INFINITY);
 #pragma unroll
       for (int j = 0; j < NP; ++j)
-        if (j < n) mx = max_i(mx, v[j]);
+        if (j < n) mx = dm::max(mx, v[j]);
       S se = S(0);
 #pragma unroll
       for (int j = 0; j < NP; ++j)
-        if (j < n) { v[j] = exp_i(v[j] - mx); se += v[j]; }
+        if (j < n) { v[j] = dm::exp(v[j] - mx); se += v[j]; }
 #pragma unroll
       for (int j = 0; j < NP; ++j) v[j] = v[j] / se;
     } else {
 #pragma unroll
-      for (int j = 0; j < NP; ++j) v[j] = S(1) / (S(1) + exp_i(-v[j]));
+      for (int j = 0; j < NP; ++j) v[j] = dm::logistic(v[j]);
     }
     if (out) {
       S* o = out + row * n;
@@ -227,18 +221,16 @@ __global__ __launch_bounds__(256) void infer_rows_kernel(const S* z, long B, con
   const S* zr = z + row * n;
   S mx = S(-INFINITY), se = S(0);
   if (softmax) {
-    for (int j = lane; j < n; j += 64) mx = max_i(mx, zr[j] + bias[j]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = max_i(mx, __shfl_xor(mx, off, 64));
-    for (int j = lane; j < n; j += 64) se += exp_i(zr[j] + bias[j] - mx);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) se += __shfl_xor(se, off, 64);
+    for (int j = lane; j < n; j += 64) mx = dm::max(mx, zr[j] + bias[j]);
+    mx = dm::wave_max(mx);
+    for (int j = lane; j < n; j += 64) se += dm::exp(zr[j] + bias[j] - mx);
+    se = dm::wave_sum(se);
   }
   S best = S(0);
   long bi = -1, ln = -1;
   auto prob = [&](int j) {
     const S v = zr[j] + bias[j];
-    return softmax ? exp_i(v - mx) / se : S(1) / (S(1) + exp_i(-v));
+    return softmax ? dm::exp(v - mx) / se : dm::logistic(v);
   };
   for (int j = lane; j < n; j += 64) {
     const S p = prob(j);
@@ -269,9 +261,9 @@ __global__ __launch_bounds__(256) void infer_rows_kernel(const S* z, long B, con
 template <class S, int ACT>
 __global__ __launch_bounds__(256) void bias_act_kernel(S* __restrict__ x, const S* __restrict__ bias, long total, long n) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    if constexpr (ACT == ACT_KIND_TANH) x[i] = tanh_act(x[i] + bias[i % n]);
+    if constexpr (ACT == ACT_KIND_TANH) x[i] = dm::tanh_act(x[i] + bias[i % n]);
     else if constexpr (ACT == ACT_KIND_IDENTITY) x[i] = x[i] + bias[i % n];
-    else x[i] = S(1) / (S(1) + exp_i(-(x[i] + bias[i % n])));
+    else x[i] = dm::logistic(x[i] + bias[i % n]);
   }
 }
 

@@ -8,7 +8,7 @@
 //
 //   * layer 1 (the big one: 300 x 784) is split by ROWS over G <= 32 workgroups; workgroup g owns rows R_g of W1, b1
 //     and computes its slice of h1 = act(W1 x + b1) -- act, the hidden activation, is a template parameter of the kernel:
-//     logistic (h (1 - h) backward) or tanh (1 - h h; common.hpp);
+//     logistic (h (1 - h) backward) or tanh (1 - h h; devmath.hpp);
 //   * layer 2 is split by COLUMNS along the same index set: workgroup g owns W2[:, R_g] and contributes the partial
 //     product W2[:, R_g] h1[R_g] -- o2 numbers -- to an exchange buffer.  One barrier per sample; afterwards every
 //     workgroup sums the G partials (in workgroup order: every workgroup gets the same bits) and has z2;
@@ -25,6 +25,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -57,15 +58,10 @@ struct OnlineArgs {
   long long* dbg;    // development (TOPS_ONLINE_STAMPS): phase time stamps of workgroup 0 at sample 64
 };
 
-// (logistic_f, hid_act<ACT>, hid_dact<ACT>: common.hpp, shared by the two persistent per-sample kernels)
-__device__ __forceinline__ float exp_f(float z) { return __expf(z); }
-__device__ __forceinline__ double exp_f(double z) { return exp(z); }
-__device__ __forceinline__ float fma_f(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double fma_f(double a, double b, double c) { return fma(a, b, c); }
-
 // Sum over the 64 lanes of a wave, result in every lane.  Row operations on the VALU's data path (DPP) instead of six
 // trips through the LDS crossbar (ds_bpermute, what __shfl_xor compiles to): quads, half rows, rows, then the two row
-// broadcasts; lane 63 ends up with the total.
+// broadcasts; lane 63 ends up with the total.  Not dm::wave_sum: a different summation tree (its
+// roundings differ); fp64 has no DPP form and takes the shared butterfly.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_f(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, true));
@@ -79,11 +75,7 @@ __device__ __forceinline__ float wave_sum(float v) {
   v += dpp_f<0x143, 0xc>(v);   // row_bcast31 into rows 2 and 3
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
+__device__ __forceinline__ double wave_sum(double v) { return dm::wave_sum(v); }
 
 // L1-bypassing accesses to the exchange buffer (all readers and writers share one L2)
 template <class S> __device__ __forceinline__ void st_l2(S* p, S v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -180,35 +172,35 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
         S bcc0 = S(0.), bcc1 = S(0.), bcc2 = S(0.), bcc3 = S(0.);
         for (; k + 192 < i0; k += 256) {   // four independent chains per row: the LDS reads of one pass are all in flight together
           const S x0 = xs[k], x1 = xs[k + 64], x2 = xs[k + 128], x3 = xs[k + 192];
-          acc0 = fma_f(w[k], x0, acc0);
-          acc1 = fma_f(w[k + 64], x1, acc1);
-          acc2 = fma_f(w[k + 128], x2, acc2);
-          acc3 = fma_f(w[k + 192], x3, acc3);
-          bcc0 = fma_f(v[k], x0, bcc0);
-          bcc1 = fma_f(v[k + 64], x1, bcc1);
-          bcc2 = fma_f(v[k + 128], x2, bcc2);
-          bcc3 = fma_f(v[k + 192], x3, bcc3);
+          acc0 = dm::fma(w[k], x0, acc0);
+          acc1 = dm::fma(w[k + 64], x1, acc1);
+          acc2 = dm::fma(w[k + 128], x2, acc2);
+          acc3 = dm::fma(w[k + 192], x3, acc3);
+          bcc0 = dm::fma(v[k], x0, bcc0);
+          bcc1 = dm::fma(v[k + 64], x1, bcc1);
+          bcc2 = dm::fma(v[k + 128], x2, bcc2);
+          bcc3 = dm::fma(v[k + 192], x3, bcc3);
         }
         for (; k < i0; k += 64) {
           const S x0 = xs[k];
-          acc0 = fma_f(w[k], x0, acc0);
-          bcc0 = fma_f(v[k], x0, bcc0);
+          acc0 = dm::fma(w[k], x0, acc0);
+          bcc0 = dm::fma(v[k], x0, bcc0);
         }
         S bcc = (bcc0 + bcc1) + (bcc2 + bcc3);
         bcc = wave_sum(bcc);
-        if (lane == 1) h1s[r + NWV] = hid_act<ACT>(bcc + b1s[r + NWV]);
+        if (lane == 1) h1s[r + NWV] = dm::hid_act_fast<ACT>(bcc + b1s[r + NWV]);
       } else {
         for (; k + 192 < i0; k += 256) {
-          acc0 = fma_f(w[k], xs[k], acc0);
-          acc1 = fma_f(w[k + 64], xs[k + 64], acc1);
-          acc2 = fma_f(w[k + 128], xs[k + 128], acc2);
-          acc3 = fma_f(w[k + 192], xs[k + 192], acc3);
+          acc0 = dm::fma(w[k], xs[k], acc0);
+          acc1 = dm::fma(w[k + 64], xs[k + 64], acc1);
+          acc2 = dm::fma(w[k + 128], xs[k + 128], acc2);
+          acc3 = dm::fma(w[k + 192], xs[k + 192], acc3);
         }
-        for (; k < i0; k += 64) acc0 = fma_f(w[k], xs[k], acc0);
+        for (; k < i0; k += 64) acc0 = dm::fma(w[k], xs[k], acc0);
       }
       S acc = (acc0 + acc1) + (acc2 + acc3);
       acc = wave_sum(acc);
-      if (lane == 0) h1s[r] = hid_act<ACT>(acc + b1s[r]);
+      if (lane == 0) h1s[r] = dm::hid_act_fast<ACT>(acc + b1s[r]);
     }
     __syncthreads();
     ON_STAMP();
@@ -224,7 +216,7 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
     for (int j = tid; j < o2; j += ON_THREADS) {
       const S* w = W2s + j * a.rpw;
       S acc = S(0.);
-      for (int r = 0; r < nr; ++r) acc = fma_f(w[r], h1s[r], acc);
+      for (int r = 0; r < nr; ++r) acc = dm::fma(w[r], h1s[r], acc);
       unsigned wd[WORDS];
       __builtin_memcpy(wd, &acc, sizeof(S));
 #pragma unroll
@@ -311,7 +303,7 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
       }
       for (; q < a.G; ++q) z0 += part[q * o2 + j];
       const S z = bb[1][j] + ((z0 + z1) + (z2 + z3));
-      act[2][j] = L == 2 ? z : hid_act<ACT>(z);
+      act[2][j] = L == 2 ? z : dm::hid_act_fast<ACT>(z);
     }
     __syncthreads();
     ON_STAMP();
@@ -321,10 +313,10 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
       for (int j = wave; j < O; j += ON_THREADS / 64) {   // one wave per output: a 64-lane dot product
         const S* w = Wr[l] + j * (K + 1);
         S z = S(0.);
-        for (int k = lane; k < K; k += 64) z = fma_f(w[k], act[l][k], z);
+        for (int k = lane; k < K; k += 64) z = dm::fma(w[k], act[l][k], z);
         z = wave_sum(z);
         z += bb[l][j];
-        if (lane == 0) act[l + 1][j] = l + 1 == L ? z : hid_act<ACT>(z);
+        if (lane == 0) act[l + 1][j] = l + 1 == L ? z : dm::hid_act_fast<ACT>(z);
       }
       __syncthreads();
     ON_STAMP();
@@ -341,12 +333,12 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
           mx = mx > other ? mx : other;
           sy += __shfl_xor(sy, off);
         }
-        const S e = lane < oL ? exp_f(z - mx) : S(0.);
+        const S e = lane < oL ? dm::exp_fast(z - mx) : S(0.);
         S se = e;
         se = wave_sum(se);
         d = e / se * sy - y;              // softmax(z) * sum(y) - y
       } else {
-        const S s = logistic_f(z), e = y - s;
+        const S s = dm::logistic_fast(z), e = y - s;
         d = -S(2.0) * e * s * (S(1.0) - s);   // logistic >>> squaredError
       }
       if (lane < oL) dz[L][lane] = d;
@@ -358,9 +350,9 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
       const int K = a.dims[l], O = a.dims[l + 1];
       for (int k = tid; k < K; k += ON_THREADS) {
         S s = S(0.);
-        for (int j = 0; j < O; ++j) s = fma_f(Wr[l][j * (K + 1) + k], dz[l + 1][j], s);
+        for (int j = 0; j < O; ++j) s = dm::fma(Wr[l][j * (K + 1) + k], dz[l + 1][j], s);
         const S h = act[l][k];
-        dz[l][k] = hid_dact<ACT>(s, h);
+        dz[l][k] = dm::hid_dact_fast<ACT>(s, h);
       }
       __syncthreads();
     ON_STAMP();
@@ -373,21 +365,21 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
         S s2 = S(0.);
         for (int j = lane; j < o2; j += 64) {
           const S d = dz[2][j];
-          s = fma_f(W2s[j * a.rpw + r], d, s);
-          s2 = fma_f(W2s[j * a.rpw + r2], d, s2);
+          s = dm::fma(W2s[j * a.rpw + r], d, s);
+          s2 = dm::fma(W2s[j * a.rpw + r2], d, s2);
         }
         s2 = wave_sum(s2);
         if (lane == 1) {
           const S h = h1s[r2];
-          dz1s[r2] = hid_dact<ACT>(s2, h);
+          dz1s[r2] = dm::hid_dact_fast<ACT>(s2, h);
         }
       } else {
-        for (int j = lane; j < o2; j += 64) s = fma_f(W2s[j * a.rpw + r], dz[2][j], s);
+        for (int j = lane; j < o2; j += 64) s = dm::fma(W2s[j * a.rpw + r], dz[2][j], s);
       }
       s = wave_sum(s);
       if (lane == 0) {
         const S h = h1s[r];
-        dz1s[r] = hid_dact<ACT>(s, h);
+        dz1s[r] = dm::hid_dact_fast<ACT>(s, h);
       }
     }
     __syncthreads();
@@ -404,13 +396,13 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
       int r = 0;
       for (; r + 4 <= nr; r += 4) {
         S w0 = w[(r + 0) * i0], w1 = w[(r + 1) * i0], w2 = w[(r + 2) * i0], w3 = w[(r + 3) * i0];
-        w0 = fma_f(dz1s[r + 0], x, w0);
-        w1 = fma_f(dz1s[r + 1], x, w1);
-        w2 = fma_f(dz1s[r + 2], x, w2);
-        w3 = fma_f(dz1s[r + 3], x, w3);
+        w0 = dm::fma(dz1s[r + 0], x, w0);
+        w1 = dm::fma(dz1s[r + 1], x, w1);
+        w2 = dm::fma(dz1s[r + 2], x, w2);
+        w3 = dm::fma(dz1s[r + 3], x, w3);
         w[(r + 0) * i0] = w0; w[(r + 1) * i0] = w1; w[(r + 2) * i0] = w2; w[(r + 3) * i0] = w3;
       }
-      for (; r < nr; ++r) w[r * i0] = fma_f(dz1s[r], x, w[r * i0]);
+      for (; r < nr; ++r) w[r * i0] = dm::fma(dz1s[r], x, w[r * i0]);
     }
     for (int e = tid; e < nr; e += ON_THREADS) b1s[e] -= rate * dz1s[e];
     int j_top = ON_THREADS - 1 - tid;   // W2's outputs from the TOP of the workgroup: the threads without a second column of W1
@@ -424,10 +416,10 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
       int r = 0;
       for (; r + 4 <= nr; r += 4) {
         S w0 = w[r], w1 = w[r + 1], w2 = w[r + 2], w3 = w[r + 3];
-        w0 = fma_f(c, h1s[r], w0); w1 = fma_f(c, h1s[r + 1], w1); w2 = fma_f(c, h1s[r + 2], w2); w3 = fma_f(c, h1s[r + 3], w3);
+        w0 = dm::fma(c, h1s[r], w0); w1 = dm::fma(c, h1s[r + 1], w1); w2 = dm::fma(c, h1s[r + 2], w2); w3 = dm::fma(c, h1s[r + 3], w3);
         w[r] = w0; w[r + 1] = w1; w[r + 2] = w2; w[r + 3] = w3;
       }
-      for (; r < nr; ++r) w[r] = fma_f(c, h1s[r], w[r]);
+      for (; r < nr; ++r) w[r] = dm::fma(c, h1s[r], w[r]);
     }
     for (int e = tid; e < o2; e += ON_THREADS) bb[1][e] -= rate * dz[2][e];
     for (int l = 2; l < L; ++l) {
@@ -435,7 +427,7 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
       for (int e = tid; e < O * K; e += ON_THREADS) {
         const int j = e / K, k = e - j * K;
         S* w = Wr[l] + j * (K + 1) + k;
-        *w = fma_f(-rate * dz[l + 1][j], act[l][k], *w);
+        *w = dm::fma(-rate * dz[l + 1][j], act[l][k], *w);
       }
       for (int e = tid; e < O; e += ON_THREADS) bb[l][e] -= rate * dz[l + 1][e];
     }

@@ -15,6 +15,7 @@
 // i, i + 64, ...: one 16-byte load / store per piece where the row bytes and every base allow (VEC), the same elements one at
 // a time otherwise -- so which lane adds which element, and with it every bit of the result, does not depend on alignment.
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 namespace {
@@ -26,12 +27,7 @@ struct alignas(16) Piece {
   S v[16 / sizeof(S)];
 };
 
-template <class S>
-__device__ __forceinline__ S rh_wsum(S v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
+// Not dm::wave_max: compare-select keeps the value held where the other one is a NaN; fmax would drop the NaN.
 template <class S>
 __device__ __forceinline__ S rh_wmax(S v) {
 #pragma unroll
@@ -41,22 +37,18 @@ __device__ __forceinline__ S rh_wmax(S v) {
   }
   return v;
 }
-__device__ __forceinline__ float rh_exp(float x) { return expf(x); }
-__device__ __forceinline__ double rh_exp(double x) { return exp(x); }
-__device__ __forceinline__ float rh_log(float x) { return logf(x); }
-__device__ __forceinline__ double rh_log(double x) { return log(x); }
 
 // a = act(v) of the three elementwise pairs, and act' written on a
 template <int PAIR, class S>
 __device__ __forceinline__ S rh_act(S v) {
-  if constexpr (PAIR == 2) return S(1) / (S(1) + rh_exp(-v));
-  else if constexpr (PAIR == 3) return tanh_act(v);
+  if constexpr (PAIR == 2) return dm::logistic(v);
+  else if constexpr (PAIR == 3) return dm::tanh_act(v);
   else return v;
 }
 template <int PAIR, class S>
 __device__ __forceinline__ S rh_dact(S a) {
   if constexpr (PAIR == 2) return a * (S(1) - a);
-  else if constexpr (PAIR == 3) return tanh_dact(a);
+  else if constexpr (PAIR == 3) return dm::tanh_dact(a);
   else return S(1);
 }
 
@@ -146,13 +138,13 @@ __global__ __launch_bounds__(256) void recon_head_kernel(const S* z, const S* __
       for (int c = 0; c < T::NC; ++c)
 #pragma unroll
         for (int e = 0; e < T::V; ++e) {
-          if (v.in(base, n, lane, c, e)) se += rh_exp(v.x[c][e] - mx);
+          if (v.in(base, n, lane, c, e)) se += dm::exp(v.x[c][e] - mx);
           st += y.x[c][e];
         }
     }
-    se = rh_wsum(se);
-    st = rh_wsum(st);
-    const S inv = S(1) / se, lse = rh_log(se);
+    se = dm::wave_sum(se);
+    st = dm::wave_sum(st);
+    const S inv = S(1) / se, lse = dm::log(se);
     for (int base = 0; base < n; base += RECON_TILE) {
       if (!one) {
         v.load(zr, bias, base, n, lane, S(-INFINITY));
@@ -163,7 +155,7 @@ __global__ __launch_bounds__(256) void recon_head_kernel(const S* z, const S* __
 #pragma unroll
         for (int e = 0; e < T::V; ++e) {
           if (!v.in(base, n, lane, c, e)) continue;
-          const S d = v.x[c][e] - mx, p = rh_exp(d) * inv, tt = y.x[c][e];
+          const S d = v.x[c][e] - mx, p = dm::exp(d) * inv, tt = y.x[c][e];
           l -= tt * (d - lse);          // log p, finite where p underflows
           v.x[c][e] = p;
           y.x[c][e] = p * st - tt;
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(256) void recon_head_kernel(const S* z, const S* __
     }
   }
   if (loss) {
-    l = rh_wsum(l);
+    l = dm::wave_sum(l);
     if (lane == 0) loss[row] = l;
   }
 }

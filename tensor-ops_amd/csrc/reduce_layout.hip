@@ -9,6 +9,7 @@
 
 namespace to {
 
+// Not dm::wave_sum: a __shfl_down tree, only lane 0 ends with the wave's sum.
 template <class S>
 __device__ __forceinline__ S wave_sum(S v) {
 #pragma unroll

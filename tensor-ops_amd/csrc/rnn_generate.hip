@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -30,17 +31,6 @@ namespace {
 
 constexpr int GEN_THREADS = 256;
 constexpr int64_t GEN_MAX_ITEMS = 4096;      // (row, column) items of the widest layer per workgroup
-
-__device__ __forceinline__ float exp_g(float x) { return expf(x); }
-__device__ __forceinline__ double exp_g(double x) { return exp(x); }
-__device__ __forceinline__ float max_g(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ double max_g(double a, double b) { return fmax(a, b); }
-__device__ __forceinline__ float fma_g(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double fma_g(double a, double b, double c) { return fma(a, b, c); }
-template <class S>
-__device__ __forceinline__ S act_g(int kind, S z) {
-  return kind == ACT_KIND_TANH ? tanh_act(z) : S(1) / (S(1) + exp_g(-z));
-}
 
 // The feed rule, by one whole wave (all 64 lanes call it): x[0 .. n) = the input made from row[0 .. n); returns the symbol
 // (0 for TO_FEED_OUTPUT) on every lane.  row and x do not overlap.
@@ -222,16 +212,16 @@ __global__ __launch_bounds__(GEN_THREADS) void rnn_gen_kernel(RnnGenArgs<S> a) {
         const S* wj = Wk + j;
         S acc = S(0);
 #pragma unroll 4
-        for (int kk = 0; kk < m; ++kk) acc = fma_g(ar[kk], wj[(size_t)kk * n], acc);
+        for (int kk = 0; kk < m; ++kk) acc = dm::fma(ar[kk], wj[(size_t)kk * n], acc);
         if (sk >= 0) {
           const S* sr = sc + (size_t)r * sp;
           const S* vj = WSk + j;
 #pragma unroll 4
-          for (int kk = 0; kk < n; ++kk) acc = fma_g(sr[kk], vj[(size_t)kk * n], acc);
+          for (int kk = 0; kk < n; ++kk) acc = dm::fma(sr[kk], vj[(size_t)kk * n], acc);
         }
         const S z = acc + bb[j];
-        if (sk >= 0) sn[(size_t)r * sp + j] = act_g(sk, z);
-        outb[(size_t)r * wp + j] = last ? z : act_g(a.hidden_kind, z);
+        if (sk >= 0) sn[(size_t)r * sp + j] = dm::act(sk, z);
+        outb[(size_t)r * wp + j] = last ? z : dm::act(a.hidden_kind, z);
       }
       if (sk >= 0) sq += 2 * (size_t)R * sp;
       __syncthreads();
@@ -244,17 +234,15 @@ __global__ __launch_bounds__(GEN_THREADS) void rnn_gen_kernel(RnnGenArgs<S> a) {
       S* zr = zl + (size_t)r * wp;
       S mx = S(-INFINITY), se = S(0);
       if (a.softmax) {
-        for (int j = lane; j < nL; j += 64) mx = max_g(mx, zr[j]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = max_g(mx, __shfl_xor(mx, off, 64));
-        for (int j = lane; j < nL; j += 64) se += exp_g(zr[j] - mx);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) se += __shfl_xor(se, off, 64);
+        for (int j = lane; j < nL; j += 64) mx = dm::max(mx, zr[j]);
+        mx = dm::wave_max(mx);
+        for (int j = lane; j < nL; j += 64) se += dm::exp(zr[j] - mx);
+        se = dm::wave_sum(se);
       }
       S* o = k >= 0 ? a.out + ((b0 + r) * a.G + k) * nL : a.prime_out ? a.prime_out + ((b0 + r) * a.Tp + t) * nL : nullptr;
       for (int j = lane; j < nL; j += 64) {
         const S v = zr[j];
-        const S p = a.softmax ? exp_g(v - mx) / se : S(1) / (S(1) + exp_g(-v));
+        const S p = a.softmax ? dm::exp(v - mx) / se : dm::logistic(v);
         zr[j] = p;
         if (o) o[j] = p;
       }

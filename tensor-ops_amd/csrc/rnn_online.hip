@@ -40,6 +40,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -47,37 +48,6 @@ namespace {
 
 constexpr int ONLINE_THREADS = 512;
 
-__device__ __forceinline__ float exp_o(float x) { return expf(x); }
-__device__ __forceinline__ double exp_o(double x) { return exp(x); }
-__device__ __forceinline__ float log_o(float x) { return logf(x); }
-__device__ __forceinline__ double log_o(double x) { return log(x); }
-__device__ __forceinline__ float fma_o(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double fma_o(double a, double b, double c) { return fma(a, b, c); }
-__device__ __forceinline__ float wmax_o(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ double wmax_o(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-template <class S>
-__device__ __forceinline__ S wsum_o(S v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-// the activation, and its derivative written on the stored output h (tanh: common.hpp's pair)
-template <class S>
-__device__ __forceinline__ S act_o(int kind, S z) {
-  return kind == ACT_KIND_TANH ? tanh_act(z) : S(1) / (S(1) + exp_o(-z));
-}
-template <class S>
-__device__ __forceinline__ S dact_o(int kind, S h) {
-  return kind == ACT_KIND_TANH ? tanh_dact(h) : h * (S(1) - h);
-}
 // The (t, c) items of a [T][w] index space spread over the workgroup: thread tid takes items tid, tid + TH, ... with item
 // i = (i / w, i % w), stepped without a division a turn.
 template <int TH, class F>
@@ -116,10 +86,10 @@ __device__ __forceinline__ void update_tiles(const S* tape, long rec, long T, in
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
         const S xv = x[kk];
-        g[kk][0] = fma_o(d0, xv, g[kk][0]);
-        g[kk][1] = fma_o(d1, xv, g[kk][1]);
-        g[kk][2] = fma_o(d2, xv, g[kk][2]);
-        g[kk][3] = fma_o(d3, xv, g[kk][3]);
+        g[kk][0] = dm::fma(d0, xv, g[kk][0]);
+        g[kk][1] = dm::fma(d1, xv, g[kk][1]);
+        g[kk][2] = dm::fma(d2, xv, g[kk][2]);
+        g[kk][3] = dm::fma(d3, xv, g[kk][3]);
       }
     }
 #pragma unroll
@@ -218,13 +188,13 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
         const S* wj = Wk + j;
         S acc = S(0);
 #pragma unroll 8
-        for (int k = 0; k < m; ++k) acc = fma_o(in[k], wj[k * ld], acc);
+        for (int k = 0; k < m; ++k) acc = dm::fma(in[k], wj[k * ld], acc);
         if (sk >= 0) {
           rt[odz + j] = acc;   // parked: the recurrence goes on from here
         } else {
           const S z = acc + bb[j];
           if (last) rt[odz + j] = z;
-          else rt[onx + j] = act_o(hk, z);
+          else rt[onx + j] = dm::act(hk, z);
         }
       });
       __syncthreads();
@@ -249,9 +219,9 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
           if (mine) {
             S acc = pz;
 #pragma unroll 8
-            for (int k = 0; k < n; ++k) acc = fma_o(sc[k], vj[k * ld], acc);
+            for (int k = 0; k < n; ++k) acc = dm::fma(sc[k], vj[k * ld], acc);
             const S z = acc + bj;
-            const S ns = act_o(sk, z);
+            const S ns = dm::act(sk, z);
             sn[tid] = ns;
             if (more) rt[rec + os + tid] = ns;   // S_{t+1}
             rt[odz + tid] = z;
@@ -264,7 +234,7 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
       if (!last) {   // hidden_act(z) of all steps: the next layer's input rows
         for_items<TH>(T, n, tid, [&](long t, int j) {
           S* const rt = tape + t * rec;
-          rt[onx + j] = act_o(hk, rt[odz + j]);
+          rt[onx + j] = dm::act(hk, rt[odz + j]);
         });
         __syncthreads();
       }
@@ -278,30 +248,30 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
       if (a.softmax) {
         S mx = S(-INFINITY);
         for (int j = lane; j < nL; j += 64) mx = zr[j] > mx ? zr[j] : mx;
-        mx = wmax_o(mx);
+        mx = dm::wave_max(mx);
         S se = S(0), sy = S(0);
         for (int j = lane; j < nL; j += 64) {
-          se += exp_o(zr[j] - mx);
+          se += dm::exp(zr[j] - mx);
           sy += yr[j];
         }
-        se = wsum_o(se);
-        sy = wsum_o(sy);
+        se = dm::wave_sum(se);
+        sy = dm::wave_sum(sy);
         const S inv = S(1) / se;
         for (int j = lane; j < nL; j += 64) {
-          const S p = exp_o(zr[j] - mx) * inv;
+          const S p = dm::exp(zr[j] - mx) * inv;
           zr[j] = p * sy - yr[j];
-          l -= yr[j] * log_o(p);
+          l -= yr[j] * dm::log(p);
         }
       } else {
         for (int j = lane; j < nL; j += 64) {
-          const S sg = S(1) / (S(1) + exp_o(-zr[j]));
+          const S sg = dm::logistic(zr[j]);
           const S e = yr[j] - sg;
           zr[j] = S(-2) * e * sg * (S(1) - sg);
           l += e * e;
         }
       }
       if (a.losses) {
-        l = wsum_o(l);
+        l = dm::wave_sum(l);
         if (lane == 0) a.losses[js * T + t] = l;
       }
     }
@@ -331,8 +301,8 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
           if (mine) {
             S acc = S(0);
 #pragma unroll 8
-            for (int j = 0; j < n; ++j) acc = fma_o(vk[j], dcur[j], acc);
-            const S d = g0 + acc * dact_o(sk, s1);
+            for (int j = 0; j < n; ++j) acc = dm::fma(vk[j], dcur[j], acc);
+            const S d = g0 + acc * dm::dact(sk, s1);
             dnxt[tid] = d;
             rt[odz + tid] = d;
           }
@@ -344,7 +314,7 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
           const S* dcur = d0 + cur * wq;
           S acc = S(0);
 #pragma unroll 8
-          for (int j = 0; j < n; ++j) acc = fma_o(vk[j], dcur[j], acc);
+          for (int j = 0; j < n; ++j) acc = dm::fma(vk[j], dcur[j], acc);
           lds[a.s_off[l] + tid] -= a.rate_state * acc;
         }
         __syncthreads();
@@ -358,8 +328,8 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
           const S h = rt[oin + k];
           S acc = S(0);
 #pragma unroll 8
-          for (int j = 0; j < n; ++j) acc = fma_o(wk[j], dz[j], acc);
-          rt[odn + k] = acc * dact_o(hk, h);
+          for (int j = 0; j < n; ++j) acc = dm::fma(wk[j], dz[j], acc);
+          rt[odn + k] = acc * dm::dact(hk, h);
         });
         __syncthreads();
       }

@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -23,11 +24,6 @@ namespace {
 constexpr int RAG_THREADS = 256;
 constexpr int RAG_QMAX = RNN_SEQ_MAX_H / RAG_THREADS;  // (row, column) items per thread, as rnn_seq.hip
 constexpr size_t RAG_LDS_MAX = 160 * 1024;
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }   // rnn_seq.hip's, bit for bit
-__device__ __forceinline__ double sigm(double x) { return 1.0 / (1.0 + exp(-x)); }
-__device__ __forceinline__ float fma_r(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double fma_r(double a, double b, double c) { return fma(a, b, c); }
 
 struct alignas(16) Piece16 { unsigned v[4]; };
 
@@ -155,19 +151,19 @@ __global__ __launch_bounds__(RAG_THREADS) void rnn_ragged_seq_kernel(RaggedSeqAr
           const S* vr = vc + (size_t)r * H;
           const S* mj = M + j;
 #pragma unroll 4
-          for (int k = 0; k < H; ++k) acc = fma_r(vr[k], mj[(size_t)k * H], acc);
+          for (int k = 0; k < H; ++k) acc = dm::fma(vr[k], mj[(size_t)k * H], acc);
         }
         S o;
         if (!REV) {
           const S z = pre[q] + acc;
           a.Z[at_t] = z;
-          if constexpr (ACT == ACT_KIND_TANH) o = tanh_act(z);
-          else o = sigm(z);
+          if constexpr (ACT == ACT_KIND_TANH) o = dm::tanh_act(z);
+          else o = dm::logistic(z);
           a.Sa[at_t] = o;
         } else {
           const S h = a.Sa[at_t];
-          if constexpr (ACT == ACT_KIND_TANH) o = fma_r(acc, tanh_dact(h), pre[q]);
-          else o = fma_r(acc * h, S(1) - h, pre[q]);
+          if constexpr (ACT == ACT_KIND_TANH) o = dm::fma(acc, dm::tanh_dact(h), pre[q]);
+          else o = dm::fma(acc * h, S(1) - h, pre[q]);
           a.Z[at_t] = o;
         }
         vn[item] = o;

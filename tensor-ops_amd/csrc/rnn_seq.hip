@@ -4,7 +4,7 @@
 //   forward  z_t  = P_t + s_{t-1} W'^T,  s_t = act(z_t)                   (P_t: the input projection, z_t in place over it)
 //   reverse  dz_t = G_t + (dz_{t+1} W') (.) act'(s_t),  dz_T = 0          (G_t: the output-path cotangent, in place)
 // act: the layer's state activation, a template parameter of the kernel (ACT_KIND_LOGISTIC: s (1 - s); ACT_KIND_TANH:
-// tanh, 1 - s^2 -- common.hpp).
+// tanh, 1 - s^2 -- devmath.hpp).
 // Both are out_t[j] = epilogue(sum_k v_{t-1}[k] M[k][j]) with M = W'^T (forward, a transposed copy) or W' (reverse), so one
 // kernel serves both.  rnn_seq_kernel: ONE launch per layer and direction covers all T steps.  Each workgroup owns R
 // whole sequences (rows) and all H columns, so a step's new vector never leaves the workgroup: it is exchanged through
@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "devmath.hpp"
 
 namespace to {
 
@@ -24,11 +25,6 @@ namespace {
 constexpr int RNN_THREADS = 256;
 constexpr int RNN_QMAX = RNN_SEQ_MAX_H / RNN_THREADS;  // (row, column) items per thread: R * H <= RNN_SEQ_MAX_H
 constexpr size_t RNN_LDS_MAX = 160 * 1024;
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ double sigm(double x) { return 1.0 / (1.0 + exp(-x)); }
-__device__ __forceinline__ float fma_r(float a, float b, float c) { return fmaf(a, b, c); }
-__device__ __forceinline__ double fma_r(double a, double b, double c) { return fma(a, b, c); }
 
 template <class S>
 struct RnnSeqArgs {
@@ -82,19 +78,19 @@ __global__ __launch_bounds__(RNN_THREADS) void rnn_seq_kernel(RnnSeqArgs<S> a) {
           const S* vr = vc + (size_t)r * H;
           const S* mj = M + j;
 #pragma unroll 4
-          for (int k = 0; k < H; ++k) acc = fma_r(vr[k], mj[(size_t)k * H], acc);
+          for (int k = 0; k < H; ++k) acc = dm::fma(vr[k], mj[(size_t)k * H], acc);
         }
         S o;
         if (!REV) {
           const S z = pre[q] + acc;
           a.Z[off] = z;
-          if constexpr (ACT == ACT_KIND_TANH) o = tanh_act(z);
-          else o = sigm(z);
+          if constexpr (ACT == ACT_KIND_TANH) o = dm::tanh_act(z);
+          else o = dm::logistic(z);
           a.St[off + blk] = o;
         } else {
           const S h = a.St[off + blk];
-          if constexpr (ACT == ACT_KIND_TANH) o = fma_r(acc, tanh_dact(h), pre[q]);
-          else o = fma_r(acc * h, S(1) - h, pre[q]);
+          if constexpr (ACT == ACT_KIND_TANH) o = dm::fma(acc, dm::tanh_dact(h), pre[q]);
+          else o = dm::fma(acc * h, S(1) - h, pre[q]);
           a.Z[off] = o;
         }
         vn[item] = o;

@@ -253,11 +253,19 @@ to_status to_memo_end(void);
  * on three random rows against the closed forms the kernel carries, z in [-2, 2], targets in [0.05, 1.05], agreement to
  * 1e-9; only programs without abs/signum/max/min/pow are considered, so agreement on random points means identity) runs
  * as DIFFERENT CODE from the ops it replaces: softmax >>> crossEntropy's backward as softmax(z) * sum(y) - y with the
- * row maximum subtracted before exp, logistic >>> squaredError's as -2 (y - s) s (1 - s).  Wherever the recorded ops are
- * finite the two agree within rounding (tests hold the fused step to 1e-5 / 1e-11 of the fp64 oracle); beyond the range
- * of a literal evaluation (a logit above ln(max float): 88.7 in fp32, 709.8 in fp64) the fused head returns the limit
- * value of the same formula where the recorded ops -- and the reference -- return inf/NaN
- * (tests/test_gpu_lazy.py::test_extreme_logits_state_the_loss_heads_contract). */
+ * row maximum subtracted before exp and its loss as sum y (lse - (z - max z)), lse = log sum exp(z - max z); logistic >>>
+ * squaredError's as -2 (y - s) s (1 - s) and sum (y - s)^2.  Wherever the recorded ops are finite the two agree within
+ * rounding, the gradient AND the loss (tests hold the fused step to 1e-5 / 1e-11 of the fp64 oracle); beyond the range of a
+ * literal evaluation (a logit above ln(max float): 88.7 in fp32, 709.8 in fp64) the fused head returns the limit value of
+ * the same formulas where the recorded ops -- and the reference -- return inf/NaN
+ * (tests/test_gpu_lazy.py::test_extreme_logits_state_the_loss_heads_contract).  The loss is written on lse, not on
+ * log(p), so that it stays finite where p = exp(z - max z) / sum underflows (logits further apart than about 87 in fp32, where
+ * denormal results are flushed, and 745 in fp64): -y log(p) is NaN or inf there.  Every softmax row head of the library
+ * -- the fused one, loss_grad_rows, the online recurrent head, the induce head, the reconstruction head -- takes the one
+ * term (csrc/devmath.hpp: ce_term) and is held to one fp64 reference, route by route (tests/test_gpu_heads.py).  What stays
+ * non-finite is arithmetic, the same in the reference's: a -inf logit under a zero target (0 * inf = NaN; +inf under any
+ * other target), and inf - inf -- a +inf logit, a row that is -inf throughout -- which like a NaN logit makes the whole row
+ * NaN; a NaN target makes its row's cotangent and loss NaN and no other row's. */
 /* switch for the deferral on the CALLING THREAD (default: TOPS_LAZY, on); returns the previous setting */
 to_status to_set_lazy(int on, int* previous_or_null);
 /* The loss-head recognition above is an identity test, not a proof; a host that prefers the recorded ops as they are (a row

@@ -30,6 +30,13 @@ __device__ __forceinline__ double fma(double a, double b, double c) { return ::f
 __device__ __forceinline__ float max(float a, float b) { return fmaxf(a, b); }
 __device__ __forceinline__ double max(double a, double b) { return ::fmax(a, b); }
 
+// ---- the cross-entropy term of every softmax row head ------------------------------------------------------------------
+// -t log softmax(z)_j written on d = z_j - max z and lse = log(sum_k exp(z_k - max z)): t * (lse - d).  The same value as
+// -t * log(exp(d) / sum) while exp(d) is a normal number, and finite beyond: a row whose logits lie further apart than the
+// exponential's range (about 87 in fp32, whose denormal results are flushed, 745 in fp64) has p = 0 there, and 0 * log(0) is
+// a NaN.  What stays non-finite is arithmetic: d = -inf under t = 0 (0 * inf), and inf - inf.
+template <class S> __device__ __forceinline__ S ce_term(S t, S d, S lse) { return t * (lse - d); }
+
 // ---- logistics: three different functions in fp32 (DESIGN.md 3.3 says which route computes which) -------------------
 // exact: libm's exponential and a true division
 template <class S> __device__ __forceinline__ S logistic(S x) { return S(1) / (S(1) + exp(-x)); }

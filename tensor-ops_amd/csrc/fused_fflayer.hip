@@ -34,12 +34,12 @@ __global__ __launch_bounds__(256) void loss_grad_rows_kernel(const S* __restrict
     }
     se = dm::wave_sum(se);
     sy = dm::wave_sum(sy);
-    const S inv = S(1) / se;
+    const S inv = S(1) / se, lse = dm::log(se);
     S l = S(0);
     for (int j = lane; j < n; j += 64) {
-      const S p = dm::exp(zr[j] - mx) * inv;
+      const S d = zr[j] - mx, p = dm::exp(d) * inv;
       dr[j] = p * sy - yr[j];
-      l -= yr[j] * dm::log(p);
+      l += dm::ce_term(yr[j], d, lse);
     }
     if (loss) {
       l = dm::wave_sum(l);

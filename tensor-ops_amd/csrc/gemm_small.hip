@@ -609,8 +609,8 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgsT<S>& g, const in
           const S e = valid ? dm::exp(v - mx) : S(0);
           const S se = sum16(e), sy = sum16(t);
           const S pr = e / se;
-          out = pr * sy - t;
-          l = valid ? -t * dm::log(pr) : S(0);
+          out = dm::fma(pr, sy, -t);   // (written out: left to contraction, the compiler pairs the subtraction with the loss's instead)
+          l = valid ? dm::ce_term(t, v - mx, dm::log(se)) : S(0);   // (se >= 1 wherever it is finite)
         } else {
           const S sg = dm::logistic(v);
           const S e = t - sg;

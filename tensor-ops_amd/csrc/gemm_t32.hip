@@ -635,8 +635,8 @@ __global__ __launch_bounds__(256) void gemm_t32_head_kernel(T32Args g, T32HeadAr
     const float e = lv ? expf(v - mx) : 0.f;
     const float se = sum16(e), sy = sum16(t_l);
     const float pr = e / se;
-    out_l = lv ? pr * sy - t_l : 0.f;
-    loss_l = lv ? -t_l * logf(pr) : 0.f;
+    out_l = lv ? dm::fma(pr, sy, -t_l) : 0.f;   // (written out, as in gemm_small.hip's head: not left to contraction)
+    loss_l = lv ? dm::ce_term(t_l, v - mx, logf(se)) : 0.f;
   } else {
     const float sg = dm::logistic(v);
     const float e = t_l - sg;

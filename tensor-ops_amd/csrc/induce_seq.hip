@@ -272,7 +272,7 @@ __global__ __launch_bounds__(IN_THREADS) void induce_seq_kernel(InduceArgs<S> a)
           const S e = lane < oL ? dm::exp_fast(z - mx) : S(0.);
           const S se = dm::wave_sum(e);
           d = e / se * sy - y;                                      // softmax(z) * sum(y) - y
-          lossv = lane < oL ? y * (dm::log(se) - (z - mx)) : S(0.);   // -y log softmax(z)
+          lossv = lane < oL ? dm::ce_term(y, z - mx, dm::log(se)) : S(0.);   // -y log softmax(z)
         } else {
           const S s = dm::logistic_fast(z), e = y - s;
           d = -S(2.0) * e * s * (S(1.0) - s);                       // logistic >>> squaredError

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void recon_head_kernel(const S* z, const S* __
         for (int e = 0; e < T::V; ++e) {
           if (!v.in(base, n, lane, c, e)) continue;
           const S d = v.x[c][e] - mx, p = dm::exp(d) * inv, tt = y.x[c][e];
-          l -= tt * (d - lse);          // log p, finite where p underflows
+          l += dm::ce_term(tt, d, lse);  // (not -tt log p: finite where p underflows)
           v.x[c][e] = p;
           y.x[c][e] = p * st - tt;
         }

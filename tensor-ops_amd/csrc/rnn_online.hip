@@ -256,11 +256,11 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
         }
         se = dm::wave_sum(se);
         sy = dm::wave_sum(sy);
-        const S inv = S(1) / se;
+        const S inv = S(1) / se, lse = dm::log(se);
         for (int j = lane; j < nL; j += 64) {
-          const S p = dm::exp(zr[j] - mx) * inv;
+          const S d = zr[j] - mx, p = dm::exp(d) * inv;
           zr[j] = p * sy - yr[j];
-          l -= yr[j] * dm::log(p);
+          l += dm::ce_term(yr[j], d, lse);
         }
       } else {
         for (int j = lane; j < nL; j += 64) {

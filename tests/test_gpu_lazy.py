@@ -704,6 +704,25 @@ def test_extreme_logits_state_the_loss_heads_contract(T, H, scale, oracle_finite
             assert rel_err(g, w) < RTOL
     # the unfused fp32 evaluation has left the finite range at both scales (exp(100) > max float)
     assert not all(np.isfinite(g).all() for g in got[False])
+    # The per-row losses, held as the gradients are: the fused head's (to_fflayer_stack_grad is the same launch with the losses
+    # asked for) against the limit form sum y (lse - (z - max z)) in fp64 on the operands as stored, finite at both scales --
+    # rows whose logits lie 200 and 2000 apart, where -y log(p) of an underflowed p was NaN -- and, where the oracle's own
+    # arithmetic is finite, against that: -sum y log(exp z / sum exp z) evaluated literally.  (The Trainer's plan asks for no
+    # loss; a recorded step whose plan carries a loss node is tests/test_gpu_heads.py::test_planner_heads_with_a_loss_node.)
+    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)  # noqa: E731
+    Zs = f32(X) @ f32(W).T + f32(b)
+    D = Zs - Zs.max(axis=1, keepdims=True)
+    want_l = (Y * (np.log(np.exp(D).sum(axis=1, keepdims=True)) - D)).sum(axis=1)
+    assert np.isfinite(want_l).all() and want_l.max() > 0.9 * scale
+    _, _, losses = T.stack_grad([T.put(W)], [T.put(b)], T.put(X, batched=True), T.put(Y, batched=True), want_losses=True)
+    got_l = losses.numpy()
+    assert np.isfinite(got_l).all() and rel_err(got_l, want_l) < RTOL
+    with np.errstate(all="ignore"):
+        E = np.exp(Zs)
+        literal = -(Y * np.log(E / E.sum(axis=1, keepdims=True))).sum(axis=1)
+    assert np.isfinite(literal).all() == oracle_finite
+    if oracle_finite:
+        assert rel_err(got_l, literal) < RTOL
 
 
 @pytest.mark.parametrize("graph", [False, True])

@@ -703,6 +703,55 @@ to_status to_rnn_stack_online_sgd(int n_layers, const int* state_act, const to_t
 to_status to_set_rnn_online_persistent(int on, int* previous_or_null);   /* 0 per sequence, 1 automatic, 2 wherever in range */
 to_status to_rnn_online_stats(int64_t* persistent_runs, int64_t* per_sequence_runs);
 
+/* The same per-sequence training for sequences of DIFFERENT lengths -- `trainNetwork` takes a list [(x, y)] of any length,
+ * and folded over a data set every sequence is one update of its own length: to_rnn_stack_online_sgd's argument list with
+ * `lens` directly after the data tensors, as the ragged siblings above have it.
+ *   lens  host int64[N], N = X's batch, indexed by SEQUENCE (not by position in idx); may be reused on return.  Null is
+ *         TO_ERR_ARG.  Every one of the N entries must be in 1 .. T, also those of sequences idx never names: otherwise
+ *         TO_ERR_SHAPE.
+ * For j = 0 .. n_idx-1, in order, with q = idx[j] (q = j when idx is null): one `trainNetwork'` step on steps
+ * 0 .. lens[q]-1 of sequence q alone, objective sum_{t < lens[q]} loss(out_t, Y_t), from the parameters and learned initial
+ * states step j - 1 left.  The final state is not carried, the learned initial state is.
+ *   Padding is never read: rows t >= lens[q] of X and Y may hold anything, NaN and Inf included, and influence no bit of
+ *   any parameter, state or loss.
+ *   losses_or_null  contiguous [n_idx; T]: losses[j][t] for t < lens[idx[j]] is the dense entry's quantity; exactly +0.0 at
+ *                   padding.
+ * Everything else is to_rnn_stack_online_sgd's, with its statuses: the stack, state_act, hidden_act, the (out_act, loss)
+ * pairs, unbatched contiguous initial states, the shape rules for X / Y / idx / n_idx, the overlap rule for losses; fp32 and
+ * fp64, any N, T and widths: never TO_ERR_UNSUPPORTED for a valid stack; pending operands are produced first; refused
+ * during graph capture (TO_ERR_STATE); every refusal is decided before the first launch and leaves parameters, states and
+ * losses untouched; blocks before returning; keeps no handle.
+ * With every lens[q] == T the parameters, states and losses are the dense entry's, bit for bit, on either route.  On either
+ * route n_idx = a followed by n_idx = b from the first call's result gives the bits of the one call with a + b.
+ * Routes.  Per sequence (A): losses zeroed once, then per j to_rnn_stack_sgd's own launches on the rank-2 views of the
+ * leading lens[q] rows of X[q] and Y[q] (contiguous: a sequence's leading rows are) and the leading lens[q] entries of
+ * losses[j] -- bit for bit the caller's loop of to_rnn_stack_sgd over to_wrap views of those addresses; takes every stack.
+ * Persistent (B): rnn_online_kernel with every loop over steps bounded by the sequence's own length -- one launch, one
+ * workgroup, the same fixed summation orders, no wait but the kernel's own barriers; X, Y and losses keep the row stride of
+ * the padded T; what a longer sequence left on the tape behind a shorter one's last step is read by nothing.  The lengths
+ * reach the kernel as a device table of n_idx entries (uploaded like idx, released after the call's synchronise).  The plan
+ * -- the tape's home and the pool buffer's size -- is made for the longest length the call USES, max_j lens[idx[j]]; the
+ * range depends on no length.  to_set_rnn_online_persistent chooses the route exactly as for the dense entry (0 / 1 / 2, the
+ * same H* = 128).  The dense entry, its launches and to_rnn_online_stats are untouched by these calls;
+ * to_rnn_online_ragged_stats counts them by route.
+ * Measured (tools/rnn_online_ragged_scan.py, profiles/rnn_online_ragged_scan.txt; fp32, 256 sequences padded to T = 64,
+ * lengths uniform in 1..T, N T / sum lens = 2.02, logistic states, microseconds a sequence): route B 47 against route A 114
+ * and the caller's loop of to_rnn_stack_sgd over to_wrap views 116 for 5 -> 7 -> 5 (2.4x ahead); 64 -> H (stateful) -> 10:
+ * 57 / 135 / 137 at H = 32, 79 / 152 / 155 at 64, 111 / 187 / 190 at 96, 152 / 219 / 222 at 128 (2.4x down to 1.44x ahead).
+ * Route B is ahead of route A on every scanned row, so the automatic rule H* = 128, read from equal lengths, is confirmed
+ * for these rows.  Against the dense entry on the padded set (N T rows of work on ANOTHER objective -- it trains on the
+ * padding; a work reference only) route B takes 1.82x (5 -> 7 -> 5) to 1.97x less, of the 2.02x the rows would give: a
+ * sequence's cost follows its own length.  Where it LOSES: with every length T the ragged call is up to 5 % behind the
+ * dense entry on the narrow stacks (89.4 against 85.2 for 5 -> 7 -> 5, 108.8 against 104.8 at H = 32: the lengths table and
+ * the per-sequence length read) and within 1 % of it from H = 64 on -- call the dense entry for such a set.  NOT measured:
+ * fp64, tanh states, other length distributions, other T. */
+to_status to_rnn_stack_online_sgd_ragged(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                                         const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss,
+                                         to_tensor X, to_tensor Y, const int64_t* lens, int64_t n_idx,
+                                         const int64_t* idx_or_null, double rate_state, double rate_params,
+                                         to_tensor losses_or_null);
+to_status to_rnn_online_ragged_stats(int64_t* persistent_runs, int64_t* per_sequence_runs);
+
 /* `induceNetwork` (FeedForward.hs:150-164) of the same ffLayer stacks, iterated: gradient descent on the INPUT with the
  * parameters fixed (app/MNIST.hs:357-365 runs 5000 such steps in a row), for every row of the hidden batch, in ONE call:
  *   x_0 = x[r];   g_k = d/dx loss(net(x_k), y[r]);   x_{k+1} = x_k - rate * g_k,   k = 0 .. iters-1

@@ -172,6 +172,10 @@ SIGNATURES = {
                                 C.c_double, C.c_double, c_tensor],
     "to_set_rnn_online_persistent": [C.c_int, C.POINTER(C.c_int)],
     "to_rnn_online_stats": [i64p, i64p],
+    "to_rnn_stack_online_sgd_ragged": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor),
+                                       C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int, c_tensor, c_tensor,
+                                       i64p, C.c_int64, i64p, C.c_double, C.c_double, c_tensor],
+    "to_rnn_online_ragged_stats": [i64p, i64p],
     "to_fflayer_stack_induce": [C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int, c_tensor,
                                 c_tensor, C.c_double, C.c_int64, c_tensor, c_tensor, c_tensor],
     "to_set_induce_persistent": [C.c_int, C.POINTER(C.c_int)],

@@ -539,7 +539,7 @@ void launch_rnn_gen(int dtype, const RnnGenPlan& p, const RnnGenOperands& o, hip
 void launch_rnn_feed(int dtype, const void* prev, int64_t B, int64_t n, int feed, const void* U, int64_t G, int64_t k, void* x,
                      long long* sym, hipStream_t s);
 constexpr size_t GEN_LDS_MAX = 160 * 1024;   // what a workgroup of rnn_gen_kernel / rnn_online_kernel may hold: the limit rnn_seq.hip and induce_seq.hip use
-// rnn_online.hip: per-sequence training (to_rnn_stack_online_sgd, route B) -- forward, BPTT and the update of n_idx
+// rnn_online.hip: per-sequence training (to_rnn_stack_online_sgd and its ragged sibling, route B) -- forward, BPTT and the update of n_idx
 // sequences, one after the other, in ONE launch by ONE workgroup that keeps the parameters and the learned initial states in
 // LDS.  The plan is the workgroup's LDS map (offsets in elements) and the layout of one step's tape record.
 struct RnnOnlinePlan {
@@ -561,7 +561,9 @@ struct RnnOnlineOperands {
   const void *X = nullptr, *Y = nullptr;        // contiguous [N][T][i] and [N][T][n_L]
   void* losses = nullptr;                       // contiguous [n_idx][T] (optional)
   const long long* idx = nullptr;               // device [n_idx] (null: sequences 0 .. n_idx-1)
-  void* tape = nullptr;                         // tape_elems elements of global memory unless plan.tape_lds
+  const long long* lens = nullptr;              // device [n_idx]: step j trains on the leading lens[j] <= T steps of its
+                                                // sequence (the ragged entry; the plan is made for the longest); null: on all T
+  void* tape = nullptr;                        // tape_elems elements of global memory unless plan.tape_lds
   int64_t n_idx = 0, T = 0;
   int hidden_kind = 0;
   bool softmax = true;

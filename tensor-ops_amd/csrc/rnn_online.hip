@@ -33,11 +33,16 @@
 //                       compiler its address space (LDS or global instructions instead of flat ones, whose waits are
 //                       all-or-nothing): the arithmetic is the same code and the kernel's range does not depend on T.  The
 //                       vectors on the dependent chain -- the current state, the current dz -- are in LDS always.
+//   Ragged            : to_rnn_stack_online_sgd_ragged's sequences have their own lengths.  The template parameter RAGGED
+//                       gives every step loop above the sequence's own bound (a device table of n_idx lengths) and leaves
+//                       T as the row stride; RAGGED = false is the dense entry's kernel as it was.  The plan is made for
+//                       the longest length a call uses.
 // ONLINE_THREADS = 512: the recurrences use a thread a column (at most ~200 columns fit the LDS) and pay for every wave at
 // each barrier; the item phases and the update are throughput-bound (n m T FMAs a layer, two reads each) and want more
 // than a wave a SIMD to hide the read latency.  512 is two waves a SIMD; 256 and 1024 have not been measured against it.
 // Plain VALU FMAs from LDS (no MFMA form).
 #include <algorithm>
+#include <type_traits>
 
 #include "common.hpp"
 #include "devmath.hpp"
@@ -121,16 +126,21 @@ struct RnnOnlineArgs {
   long n_idx, T, rec;
   int L, vec_off, tape_off, hidden_kind, softmax;
   S rate_state, rate_params;
+  const long long* lens;  // RAGGED: [n_idx], the steps of sequence idx[j]; the dense kernels never look at it
 };
 
-template <class S, bool TAPE_LDS>
+// RAGGED (to_rnn_stack_online_sgd_ragged): step js trains on the leading len = lens[js] steps of its sequence.  T stays what
+// it is for the dense kernels in one place only -- the row stride of X, Y and losses --; every loop over steps runs to len,
+// so the tape's records from len on, which an earlier, longer sequence left behind, are read by nothing; the head stores
+// +0.0 into losses[js][len .. T).  len is the same value in every thread, so every barrier is still reached by all of them.
+template <class S, bool TAPE_LDS, bool RAGGED>
 __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArgs<S> a) {
   extern __shared__ __align__(16) unsigned char online_lds[];
   S* const lds = reinterpret_cast<S*>(online_lds);
   constexpr int TH = ONLINE_THREADS;
   const int L = a.L, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hk = a.hidden_kind;
   const int n0 = a.n[0], nL = a.n[L];
-  const long T = a.T, rec = a.rec;
+  const long T = a.T, rec = a.rec;   // T: the rows of a sequence in X, Y and losses
   // ---- the parameters and the initial states, once --------------------------------------------------------------------
   for (int l = 0; l < L; ++l) {
     const int m = a.n[l], n = a.n[l + 1], ld = n | 1;
@@ -159,10 +169,12 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
     const long q = a.idx ? (long)a.idx[js] : js;
     const S* Xq = a.X + q * T * n0;
     const S* Yq = a.Y + q * T * nL;
+    long len = T;   // the sequence's steps
+    if constexpr (RAGGED) len = (long)a.lens[js];
     // ---- the sequence's rows of X onto the tape; S_0 = s: the current state and the tape's first record -------------------
     {
       const int o0 = a.t_in[0];
-      for_items<TH>(T, n0, tid, [&](long t, int e) { tape[t * rec + o0 + e] = Xq[t * n0 + e]; });
+      for_items<TH>(len, n0, tid, [&](long t, int e) { tape[t * rec + o0 + e] = Xq[t * n0 + e]; });
     }
     for (int l = 0; l < L; ++l) {
       if (a.sk[l] < 0) continue;
@@ -182,7 +194,7 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
       const S* bb = lds + a.b_off[l];
       const int oin = a.t_in[l], odz = a.t_dz[l], onx = last ? 0 : a.t_in[l + 1];
       // the input parts of all steps (a stateless layer: all of z, and what comes behind it)
-      for_items<TH>(T, n, tid, [&](long t, int j) {
+      for_items<TH>(len, n, tid, [&](long t, int j) {
         S* const rt = tape + t * rec;
         const S* in = static_cast<const S*>(__builtin_assume_aligned(rt + oin, 16));
         const S* wj = Wk + j;
@@ -208,9 +220,9 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
         const S* vj = WSk + tid;
         const S bj = mine ? bb[tid] : S(0);
         S pz = mine ? tape[odz + tid] : S(0);
-        for (long t = 0; t < T; ++t) {
+        for (long t = 0; t < len; ++t) {
           S* const rt = tape + t * rec;
-          const bool more = t + 1 < T;
+          const bool more = t + 1 < len;
           const int cs = (int)(t & 1);
           const S* sc = static_cast<const S*>(__builtin_assume_aligned(sc0 + cs * sq, 16));
           S* sn = sc0 + (cs ^ 1) * sq;
@@ -232,7 +244,7 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
       }
       __syncthreads();
       if (!last) {   // hidden_act(z) of all steps: the next layer's input rows
-        for_items<TH>(T, n, tid, [&](long t, int j) {
+        for_items<TH>(len, n, tid, [&](long t, int j) {
           S* const rt = tape + t * rec;
           rt[onx + j] = dm::act(hk, rt[odz + j]);
         });
@@ -241,7 +253,10 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
     }
     // ---- the head, a wave a step, all steps at once: z_L,t on the tape becomes dz_L,t in place; losses[js][t] -------------
     // (loss_grad_rows_kernel's formulas; a lane reads and writes its own elements only)
-    for (long t = wave; t < T; t += TH / 64) {
+    if constexpr (RAGGED)
+      if (a.losses)
+        for (long t = len + tid; t < T; t += TH) a.losses[js * T + t] = S(0);   // padding: +0.0
+    for (long t = wave; t < len; t += TH / 64) {
       S* const zr = tape + t * rec + a.t_dz[L - 1];
       const S* yr = Yq + t * nL;
       S l = S(0);
@@ -287,12 +302,12 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
         S* const d0 = lds + a.vec_off;
         const bool mine = tid < n;
         const S* vk = WSk + tid * ld;
-        if (mine) d0[tid] = tape[(T - 1) * rec + odz + tid];
+        if (mine) d0[tid] = tape[(len - 1) * rec + odz + tid];
         S g0 = S(0), s1 = S(0);
-        if (mine && T > 1) { g0 = tape[(T - 2) * rec + odz + tid]; s1 = tape[(T - 1) * rec + os + tid]; }
+        if (mine && len > 1) { g0 = tape[(len - 2) * rec + odz + tid]; s1 = tape[(len - 1) * rec + os + tid]; }
         __syncthreads();
         int cur = 0;
-        for (long t = T - 2; t >= 0; --t) {
+        for (long t = len - 2; t >= 0; --t) {
           S* const rt = tape + t * rec;
           const S* dcur = static_cast<const S*>(__builtin_assume_aligned(d0 + cur * wq, 16));
           S* dnxt = d0 + (cur ^ 1) * wq;
@@ -321,7 +336,7 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
       }
       if (l > 0) {   // dz_{l-1,t}[k] = (W^T dz_t)[k] hidden_act'(a_{l-1,t}[k]): time-independent, every (t, k) an item
         const int oin = a.t_in[l], odn = a.t_dz[l - 1];
-        for_items<TH>(T, m, tid, [&](long t, int k) {
+        for_items<TH>(len, m, tid, [&](long t, int k) {
           S* const rt = tape + t * rec;
           const S* wk = Wk + k * ld;
           const S* dz = static_cast<const S*>(__builtin_assume_aligned(rt + odz, 16));
@@ -338,13 +353,13 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
     for (int l = 0; l < L; ++l) {
       const int m = a.n[l], n = a.n[l + 1], ld = n | 1;
       const int odz = a.t_dz[l];
-      update_tiles<TH>(tape, rec, T, odz, a.t_in[l], n, m, ld, lds + a.w_off[l], a.rate_params, tid);
-      if (a.sk[l] >= 0) update_tiles<TH>(tape, rec, T, odz, a.t_s[l], n, n, ld, lds + a.ws_off[l], a.rate_params, tid);
+      update_tiles<TH>(tape, rec, len, odz, a.t_in[l], n, m, ld, lds + a.w_off[l], a.rate_params, tid);
+      if (a.sk[l] >= 0) update_tiles<TH>(tape, rec, len, odz, a.t_s[l], n, n, ld, lds + a.ws_off[l], a.rate_params, tid);
       for (int j = tid; j < n; j += TH) {
         const S* p = tape;
         S g = S(0);
 #pragma unroll 4
-        for (long t = 0; t < T; ++t, p += rec) g += p[odz + j];
+        for (long t = 0; t < len; ++t, p += rec) g += p[odz + j];
         lds[a.b_off[l] + j] -= a.rate_params * g;
       }
     }
@@ -372,11 +387,11 @@ __global__ __launch_bounds__(ONLINE_THREADS) void rnn_online_kernel(RnnOnlineArg
   }
 }
 
-template <class S, bool TAPE_LDS>
+template <class S, bool TAPE_LDS, bool RAGGED>
 void go_online(const RnnOnlinePlan& p, const RnnOnlineOperands& o, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_online_kernel<S, TAPE_LDS>),
+    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_online_kernel<S, TAPE_LDS, RAGGED>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GEN_LDS_MAX));
     attr = true;
   }
@@ -394,7 +409,8 @@ void go_online(const RnnOnlinePlan& p, const RnnOnlineOperands& o, hipStream_t s
   a.L = o.L; a.vec_off = p.vec_off; a.tape_off = p.tape_off; a.hidden_kind = o.hidden_kind;
   a.softmax = o.softmax ? 1 : 0;
   a.rate_state = (S)o.rate_state; a.rate_params = (S)o.rate_params;
-  launch_k(rnn_online_kernel<S, TAPE_LDS>, dim3(1), dim3(ONLINE_THREADS), p.lds, s, a);
+  a.lens = o.lens;
+  launch_k(rnn_online_kernel<S, TAPE_LDS, RAGGED>, dim3(1), dim3(ONLINE_THREADS), p.lds, s, a);
 }
 
 }  // namespace
@@ -448,8 +464,13 @@ bool rnn_online_plan(int dtype, int L, const int64_t* widths, const int* statefu
 void launch_rnn_online(int dtype, const RnnOnlinePlan& p, const RnnOnlineOperands& o, hipStream_t s) {
   TO_CHECK(o.L >= 1 && o.L <= RNN_GEN_MAX_LAYERS && o.n_idx >= 1 && o.T >= 1 && p.lds <= GEN_LDS_MAX &&
                (p.tape_lds || o.tape != nullptr), TO_ERR_STATE, "internal: rnn_online outside its plan");
-  if (dtype == TO_F64) p.tape_lds ? go_online<double, true>(p, o, s) : go_online<double, false>(p, o, s);
-  else p.tape_lds ? go_online<float, true>(p, o, s) : go_online<float, false>(p, o, s);
+  auto go = [&](auto ragged) {
+    constexpr bool R = decltype(ragged)::value;
+    if (dtype == TO_F64) p.tape_lds ? go_online<double, true, R>(p, o, s) : go_online<double, false, R>(p, o, s);
+    else p.tape_lds ? go_online<float, true, R>(p, o, s) : go_online<float, false, R>(p, o, s);
+  };
+  if (o.lens) go(std::true_type{});
+  else go(std::false_type{});
   TO_HIP(hipGetLastError());
   count_launch();
 }

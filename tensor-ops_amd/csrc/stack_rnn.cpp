@@ -806,16 +806,20 @@ static int64_t g_rnn_online_persistent_runs = 0, g_rnn_online_sequence_runs = 0;
 // 2.9 / 1.2 at 128, for T = 8 / 64).  Wider layers that still fit the LDS (up to about 200 columns in
 // fp32) have not been measured and take route A.
 constexpr int64_t RNN_ONLINE_AUTO_MAX_WIDTH = 128;
+// Sequences of their own lengths (to_rnn_stack_online_sgd_ragged): step j trains on the leading lens[idx[j]] steps of its
+// sequence; the rows behind them are padding, never read.  Route A: the same per-sequence calls on the views of the leading
+// rows -- contiguous, for a sequence's leading rows are -- with losses zeroed once up front.  Route B: the same kernel with
+// the step loops bounded by a device table of the n_idx lengths, its plan made for the longest length the call uses.  The
+// route is chosen as for the dense entry; that rule was measured on equal lengths and, by tools/rnn_online_ragged_scan.py,
+// on lengths uniform in 1 .. 64 (profiles/rnn_online_ragged_scan.txt).
+static int64_t g_rnn_online_ragged_persistent_runs = 0, g_rnn_online_ragged_sequence_runs = 0;
 
-to_status to_rnn_stack_online_sgd(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
-                                  const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
-                                  int64_t n_idx, const int64_t* idx_or_null, double rate_state, double rate_params,
-                                  to_tensor losses_or_null) {
-  API_BEGIN
-  const char* fn = "to_rnn_stack_online_sgd";
+// the dense entry (ragged false: lens is not looked at) and the ragged one
+static void rnn_online_sgd(const char* fn, int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                           const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
+                           bool ragged, const int64_t* lens, int64_t n_idx, const int64_t* idx, double rate_state,
+                           double rate_params, to_tensor losses, int64_t& persistent_runs, int64_t& sequence_runs) {
   const std::string F = std::string(fn) + ": ";
-  const to_tensor losses = losses_or_null;
-  const int64_t* idx = idx_or_null;
   require_init();
   no_capture(fn);
   NONNULL(state_act); NONNULL(s); NONNULL(ws); NONNULL(w); NONNULL(b); NONNULL(X); NONNULL(Y);
@@ -857,12 +861,23 @@ to_status to_rnn_stack_online_sgd(int n_layers, const int* state_act, const to_t
       bad = bad || stack_overlap(losses, s[l]) || stack_overlap(losses, ws[l]) || stack_overlap(losses, w[l]) || stack_overlap(losses, b[l]);
     TO_CHECK(!bad, TO_ERR_ARG, F + "losses overlaps X, Y or a parameter");
   }
+  int64_t Tused = T;   // the longest sequence the call trains on
+  std::vector<int64_t> steps;   // ragged: lens gathered by idx, as the kernel reads them
+  if (ragged) {
+    NONNULL(lens);
+    for (int64_t q = 0; q < N; ++q)
+      TO_CHECK(lens[q] >= 1 && lens[q] <= T, TO_ERR_SHAPE,
+               F + "lens[" + std::to_string(q) + "] = " + std::to_string(lens[q]) + " is outside 1 .. T = " + std::to_string(T));
+    steps.resize((size_t)n_idx);
+    for (int64_t j = 0; j < n_idx; ++j) steps[j] = lens[idx ? idx[j] : j];
+    Tused = *std::max_element(steps.begin(), steps.end());
+  }
   // The route (RNN_ONLINE_AUTO_MAX_WIDTH above).
   RnnOnlinePlan plan;
   bool persistent = false;
   if (g_rnn_online_persistent != 0 && n_layers <= RNN_GEN_MAX_LAYERS) {
     const RnnShape sh(n_layers, X->dims[1], state_act, w);
-    persistent = rnn_online_plan(dt, n_layers, sh.widths, sh.stateful, T, &plan) &&
+    persistent = rnn_online_plan(dt, n_layers, sh.widths, sh.stateful, Tused, &plan) &&
                  (g_rnn_online_persistent == 2 || plan.nmax <= RNN_ONLINE_AUTO_MAX_WIDTH);
   }
 
@@ -881,13 +896,15 @@ to_status to_rnn_stack_online_sgd(int n_layers, const int* state_act, const to_t
         o.WS[l] = ws[l]->ptr; o.s[l] = s[l]->ptr;
       }
     }
-    Holder order, tape;
-    if (idx) {
+    Holder order, count, tape;
+    auto upload = [&](const int64_t* host, Holder& h) {
       const int64_t nl = (n_idx * 8 + 3) / 4;   // n_idx int64 in a float-typed pool buffer
-      order.t = new_tensor(1, &nl, 0);
-      host_to_device(order.t->ptr, idx, (size_t)n_idx * sizeof(int64_t), S());
-      o.idx = static_cast<const long long*>(order.t->ptr);
-    }
+      h.t = new_tensor(1, &nl, 0);
+      host_to_device(h.t->ptr, host, (size_t)n_idx * sizeof(int64_t), S());
+      return static_cast<const long long*>(h.t->ptr);
+    };
+    if (idx) o.idx = upload(idx, order);
+    if (ragged) o.lens = upload(steps.data(), count);
     if (!plan.tape_lds) {
       tape.t = new_tensor(1, &plan.tape_elems, 0, dt);
       o.tape = tape.t->ptr;
@@ -898,20 +915,51 @@ to_status to_rnn_stack_online_sgd(int n_layers, const int* state_act, const to_t
     o.softmax = out_act == TO_ACT_SOFTMAX;
     o.rate_state = rate_state; o.rate_params = rate_params;
     launch_rnn_online(dt, plan, o, S());
-    TO_HIP(hipStreamSynchronize(S()));   // the order and the tape go back to the pool
-    g_rnn_online_persistent_runs++;
+    TO_HIP(hipStreamSynchronize(S()));   // the order, the lengths and the tape go back to the pool
+    persistent_runs++;
   } else {
+    if (ragged && losses) launch_fill(dt, losses->ptr, n_idx * T, 0.0, S());   // +0.0 at the padding
     for (int64_t j = 0; j < n_idx; ++j) {
-      const int64_t q = idx ? idx[j] : j;
-      Holder xq(new_view(X, X->rank, X->dims, X->strides, 0, X->numel(), q * X->bstride));
-      Holder yq(new_view(Y, Y->rank, Y->dims, Y->strides, 0, Y->numel(), q * Y->bstride));
-      Holder lq(losses ? new_view(losses, 1, losses->dims, losses->strides, 0, losses->numel(), j * losses->numel()) : nullptr);
+      const int64_t q = idx ? idx[j] : j, len = ragged ? lens[q] : T;   // the leading len rows: all T of the dense entry
+      const int64_t xd[2] = {len, X->dims[1]}, yd[2] = {len, Y->dims[1]};
+      Holder xq(new_view(X, 2, xd, X->strides, 0, xd[0] * xd[1], q * X->bstride));
+      Holder yq(new_view(Y, 2, yd, Y->strides, 0, yd[0] * yd[1], q * Y->bstride));
+      Holder lq(losses ? new_view(losses, 1, &len, losses->strides, 0, len, j * losses->numel()) : nullptr);
       RnnStackArgs a{RnnMode::Sgd, n_layers, state_act, s, ws, w, b, hidden_act, out_act, xq.t, loss, yq.t};
       a.losses = lq.t; a.rate_state = rate_state; a.rate_params = rate_params; a.fn = fn;
       rnn_stack_dense(a);
     }
-    g_rnn_online_sequence_runs++;
+    sequence_runs++;
   }
+}
+
+to_status to_rnn_stack_online_sgd(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
+                                  const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
+                                  int64_t n_idx, const int64_t* idx_or_null, double rate_state, double rate_params,
+                                  to_tensor losses_or_null) {
+  API_BEGIN
+  rnn_online_sgd("to_rnn_stack_online_sgd", n_layers, state_act, s, ws, w, b, hidden_act, out_act, loss, X, Y, false, nullptr,
+                 n_idx, idx_or_null, rate_state, rate_params, losses_or_null, g_rnn_online_persistent_runs,
+                 g_rnn_online_sequence_runs);
+  API_END
+}
+
+to_status to_rnn_stack_online_sgd_ragged(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                                         const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss,
+                                         to_tensor X, to_tensor Y, const int64_t* lens, int64_t n_idx,
+                                         const int64_t* idx_or_null, double rate_state, double rate_params,
+                                         to_tensor losses_or_null) {
+  API_BEGIN
+  rnn_online_sgd("to_rnn_stack_online_sgd_ragged", n_layers, state_act, s, ws, w, b, hidden_act, out_act, loss, X, Y, true, lens,
+                 n_idx, idx_or_null, rate_state, rate_params, losses_or_null, g_rnn_online_ragged_persistent_runs,
+                 g_rnn_online_ragged_sequence_runs);
+  API_END
+}
+
+to_status to_rnn_online_ragged_stats(int64_t* persistent_runs, int64_t* per_sequence_runs) {
+  API_BEGIN
+  if (persistent_runs) *persistent_runs = g_rnn_online_ragged_persistent_runs;
+  if (per_sequence_runs) *per_sequence_runs = g_rnn_online_ragged_sequence_runs;
   API_END
 }
 

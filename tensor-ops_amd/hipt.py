@@ -767,6 +767,36 @@ class HipT:
         check(lib().to_rnn_online_stats(C.byref(p), C.byref(q)))
         return p.value, q.value
 
+    def rnn_stack_online_sgd_ragged(self, layers, X, Y, lens, rate_state, rate_params, idx=None, n_idx=None,
+                                    out_act="softmax", loss="crossEntropy", hidden_act="logistic", want_losses=False):
+        """rnn_stack_online_sgd for sequences of their own lengths (to_rnn_stack_online_sgd_ragged): step j trains on steps
+        0 .. lens[idx[j]]-1 of its sequence, the rest of its rows is padding and never read.  lens has one entry per
+        sequence of X, whatever idx names.  The losses [n_idx; T], zero at padding, if asked for"""
+        n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
+        la = self._rnn_lens(lens, X)
+        arr = None
+        if idx is not None:
+            arr = np.ascontiguousarray(idx, dtype=np.int64)
+            n_idx = len(arr) if n_idx is None else n_idx
+        elif n_idx is None:
+            n_idx = X.batch
+        n_idx = int(n_idx)
+        losses = self._alloc((X.shape[0],), n_idx) if want_losses and n_idx >= 1 else None
+        check(lib().to_rnn_stack_online_sgd_ragged(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
+                                                   self._RNN_LOSS[loss], X.h, Y.h, la.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   n_idx,
+                                                   arr.ctypes.data_as(C.POINTER(C.c_int64)) if arr is not None else None,
+                                                   float(rate_state), float(rate_params),
+                                                   losses.h if losses is not None else None))
+        return losses
+
+    @staticmethod
+    def rnn_online_ragged_stats():
+        """(persistent runs, per-sequence runs) of the ragged entry (to_rnn_online_ragged_stats)"""
+        p, q = C.c_int64(), C.c_int64()
+        check(lib().to_rnn_online_ragged_stats(C.byref(p), C.byref(q)))
+        return p.value, q.value
+
     # -- induceNetwork iterated (to_fflayer_stack_induce) ----------------------------------------
     def induce_stack(self, ws, bs, x, y, rate, iters, out_act="softmax", loss="crossEntropy", want_gx=False,
                      want_losses=False, in_place=False, hidden_act="logistic"):

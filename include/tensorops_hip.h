@@ -789,6 +789,20 @@ to_status to_fflayer_stack_induce(int n_layers, const to_tensor* w, const to_ten
 to_status to_set_induce_persistent(int on, int* previous_or_null);
 to_status to_induce_stats(int64_t* persistent_runs, int64_t* per_iteration_runs);
 
+/* Debug: the plan of one of the two persistent kernels whose workgroups share layer 1 -- to_fflayer_stack_online_sgd's
+ * (csrc/online_sgd.hip: layer 1 split by ROWS) or route B of to_fflayer_stack_induce (csrc/induce_seq.hip: by COLUMNS) --
+ * for the stack dims[0 .. n_layers] = i0, o1 .. oL, as the entry itself would get it, without running the kernel.  B and
+ * iters are read for TO_PERSIST_INDUCE only.  *exists: the kernel takes the stack (else every other output but
+ * *placement_ok is 0); *G: workgroups that share a sample / a row; *slice: rows (online) or columns (induce) of layer 1
+ * per workgroup; *last_slice: those of workgroup G - 1; *lds_bytes: dynamic LDS per workgroup; *grid: workgroups launched
+ * (8 G where G > 1 and for every online plan; min(B, 256) for an induce plan with G = 1); *placement_ok: whether workgroups
+ * b, b + 8, .. of a grid share an XCD on this device (probed once a process), which every online plan and every induce plan
+ * with G > 1 needs.  n_layers 1..7 (a stack deeper than a kernel's range has no plan).  TO_ERR_STATE before to_init. */
+enum { TO_PERSIST_ONLINE_SGD = 0, TO_PERSIST_INDUCE = 1 };
+to_status to_persist_plan_query(int kernel, int dtype, int n_layers, const int64_t* dims, int64_t B, int64_t iters,
+                                int* exists, int* G, int* slice, int* last_slice, int64_t* lds_bytes, int64_t* grid,
+                                int* placement_ok);
+
 /* ---- measurement ---------------------------------------------------------------------- */
 /* Average duration (ms) of kernels enqueued between the two calls, measured with
  * HIP events on the library's stream. */

@@ -180,6 +180,8 @@ SIGNATURES = {
                                 c_tensor, C.c_double, C.c_int64, c_tensor, c_tensor, c_tensor],
     "to_set_induce_persistent": [C.c_int, C.POINTER(C.c_int)],
     "to_induce_stats": [i64p, i64p],
+    "to_persist_plan_query": [C.c_int, C.c_int, C.c_int, i64p, C.c_int64, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                              C.POINTER(C.c_int), C.POINTER(C.c_int), i64p, i64p, C.POINTER(C.c_int)],
     "to_graph_online_sgd": [c_graph, c_tensor, c_tensor, c_tensor, c_tensor, C.c_int64, i64p, C.POINTER(C.c_int)],
     "to_online_sgd_stats": [i64p, i64p],
     "to_timer_start": [],

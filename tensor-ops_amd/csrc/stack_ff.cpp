@@ -971,4 +971,49 @@ to_status to_induce_stats(int64_t* persistent_runs, int64_t* per_iteration_runs)
   API_END
 }
 
+// The plans of the two persistent kernels as the entries above would get them: online_sgd_plan / induce_seq_plan themselves,
+// and the placement probe's verdict.  Launches nothing but that probe (once a process).
+to_status to_persist_plan_query(int kernel, int dtype, int n_layers, const int64_t* dims, int64_t B, int64_t iters,
+                                int* exists, int* G, int* slice, int* last_slice, int64_t* lds_bytes, int64_t* grid,
+                                int* placement_ok) {
+  API_BEGIN
+  require_init();
+  NONNULL(dims); NONNULL(exists); NONNULL(G); NONNULL(slice); NONNULL(last_slice); NONNULL(lds_bytes); NONNULL(grid);
+  NONNULL(placement_ok);
+  TO_CHECK(kernel == TO_PERSIST_ONLINE_SGD || kernel == TO_PERSIST_INDUCE, TO_ERR_ARG, "persist_plan_query: unknown kernel");
+  TO_CHECK(dtype == TO_F32 || dtype == TO_F64, TO_ERR_ARG, "unknown dtype");
+  TO_CHECK(n_layers >= 1 && n_layers <= 7, TO_ERR_ARG, "persist_plan_query: 1..7 layers (dims holds n_layers + 1 widths)");
+  int g = 0, sl = 0, last = 0;
+  int64_t lds = 0, gr = 0;
+  bool ok;
+  if (kernel == TO_PERSIST_ONLINE_SGD) {
+    size_t l = 0;
+    ok = online_sgd_plan(dtype, n_layers, dims, &g, &sl, &l);
+    if (ok) {
+      lds = (int64_t)l;
+      gr = 8 * g;
+      last = (int)(dims[1] - (int64_t)(g - 1) * sl);
+    }
+  } else {
+    InduceSeqPlan plan;
+    ok = induce_seq_plan(dtype, n_layers, dims, B, iters, &plan);
+    if (ok) {
+      g = plan.G;
+      sl = plan.cw;
+      lds = (int64_t)plan.lds;
+      gr = plan.grid;
+      last = (int)(dims[0] - (int64_t)(g - 1) * sl);
+    }
+  }
+  const bool placed = online_sgd_placement_ok(S());
+  *exists = ok ? 1 : 0;
+  *G = ok ? g : 0;
+  *slice = ok ? sl : 0;
+  *last_slice = ok ? last : 0;
+  *lds_bytes = lds;
+  *grid = gr;
+  *placement_ok = placed ? 1 : 0;
+  API_END
+}
+
 }  // extern "C"

@@ -826,6 +826,19 @@ class HipT:
         check(lib().to_induce_stats(C.byref(p), C.byref(q)))
         return p.value, q.value
 
+    def persist_plan(self, kernel, dims, B=1, iters=1, dtype=None):
+        """Debug (to_persist_plan_query): the plan of the online SGD kernel (`kernel` "online") or of the persistent induce
+        kernel ("induce") for the stack of widths `dims`, running neither.  "exists" False: the kernel refuses the stack"""
+        dt = self.to_dtype if dtype is None else (capi.TO_F64 if dtype in ("f64", capi.TO_F64) else capi.TO_F32)
+        d = (C.c_int64 * 8)(*[int(v) for v in dims])
+        ex, g, sl, last, ok = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        lds, grid = C.c_int64(), C.c_int64()
+        check(lib().to_persist_plan_query(("online", "induce").index(kernel), dt, len(dims) - 1, d, int(B), int(iters),
+                                          C.byref(ex), C.byref(g), C.byref(sl), C.byref(last), C.byref(lds), C.byref(grid),
+                                          C.byref(ok)))
+        return {"exists": bool(ex.value), "G": g.value, "slice": sl.value, "last_slice": last.value, "lds_bytes": lds.value,
+                "grid": grid.value, "placement_ok": bool(ok.value)}
+
     # -- batching -------------------------------------------------------------------------
     def batch_sum(self, x):
         h = _out()

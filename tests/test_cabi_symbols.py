@@ -80,6 +80,18 @@ def test_ewise_route_query_refuses_before_init(built):
     assert got.decode().startswith("4 [-7, -7, -7] ") and "to_init" in got.decode(), got   # 4: TO_ERR_STATE
 
 
+def test_persist_plan_query_refuses_before_init(built):
+    """The plan query of the two persistent kernels reports the placement probe's verdict, which needs a device:
+    TO_ERR_STATE before to_init, outputs untouched."""
+    import sys
+    code = ("import ctypes as C; from tensor_ops_amd import capi; L = capi.lib(); dims = (C.c_int64 * 8)(784, 300, 100, 10); "
+            "i = [C.c_int(-7) for _ in range(4)]; lds, grid, ok = C.c_int64(-7), C.c_int64(-7), C.c_int(-7); "
+            "st = L.to_persist_plan_query(0, 0, 3, dims, 1, 1, *[C.byref(o) for o in i], C.byref(lds), C.byref(grid), C.byref(ok)); "
+            "print(st, [o.value for o in i] + [lds.value, grid.value, ok.value], L.to_last_error().decode())")
+    got = subprocess.check_output([sys.executable, "-c", code], cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert got.decode().startswith("4 [-7, -7, -7, -7, -7, -7, -7] ") and "to_init" in got.decode(), got   # 4: TO_ERR_STATE
+
+
 def test_kernels_are_gfx950(built):
     """The shared object carries gfx950 code objects only (no other arch, no generic fallback)."""
     blob = open(built, "rb").read()

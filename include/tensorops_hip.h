@@ -474,6 +474,55 @@ to_status to_autoencoder_stack_minibatch_sgd(int n_enc, int n_dec, const to_tens
                                              const int64_t* idx_or_null, int64_t minibatch, double rate,
                                              to_tensor losses_or_null);
 
+/* online_sgd: `foldl' (flip (trainEncoder loss r))` over the rows of a data set (trainEncoder takes ONE sample,
+ * AutoEncoder.hs:87-110) in one call.  For j = 0 .. n_idx-1 in order, q = idx[j] (idx null: q = j): step j is one
+ * to_autoencoder_stack_sgd step on row q of X alone -- the row its own target -- from the parameters step j-1 left, and
+ * losses[j] (optional, [n_idx]) is testEncoder of row q under the parameters step j started from.  The stack, the pair,
+ * dtypes, contiguity: the entries' above, with their statuses; X / idx / n_idx / losses: to_fflayer_stack_minibatch_sgd's
+ * (n_idx < 1 TO_ERR_ARG; an index out of range, a null idx with n_idx > N, losses of another batch TO_ERR_SHAPE); losses
+ * overlapping X or a parameter TO_ERR_ARG.  Every refusal is decided before the first launch and leaves parameters and
+ * losses untouched.  Refused during graph capture (TO_ERR_STATE); blocks before it returns; keeps no handle.
+ * Route A, per sample: exactly the launches of to_autoencoder_stack_minibatch_sgd with minibatch = 1, bit for bit that
+ * call; it takes every stack, so a valid stack and pair never see TO_ERR_UNSUPPORTED beyond what that call answers.
+ * Route B, persistent (csrc/ae_online.hip): ONE launch for all n_idx samples, G <= 32 workgroups of one XCD keeping the
+ * parameters in LDS between samples.  The partition is an hourglass: layer 1 split by rows, layer 2 by columns along the
+ * same rows (exchange 1: o2 numbers a workgroup a sample), layers 3 .. L-1 replicated, layer L (L >= 3) split by rows of
+ * its outputs with the head on each slice (exchange 2: o_{L-1} numbers and the loss partial); L = 2 runs the whole head in
+ * every workgroup behind exchange 1.  fp32 or fp64; 2..6 layers, i0 <= 2048, widths <= 65535, everything a workgroup holds
+ * within 160 KiB of LDS -- the plan takes the SMALLEST such G that gives every workgroup a row of layer 1 and (L >= 3) of
+ * layer L; G = 1 needs no placement and exchanges nothing through memory, G > 1 needs the placement probe to hold
+ * (else route A).  The three squaredError pairs only: (TO_ACT_SOFTMAX, TO_LOSS_CROSS_ENTROPY) always takes route A -- a
+ * row-split softmax would need a third exchange for the row's maximum and sum.  Every sum has a fixed order: n_idx = a
+ * followed by n_idx = b from the first call's parameters gives the bits of one call with a + b, a repeated call the same
+ * bits.  The two routes agree to rounding, not bit for bit.  A wait that outlives TOPS_ONLINE_TIMEOUT_S (2 s): TO_ERR_HIP
+ * naming the sample, the parameters untouched (the write-back is one compare-and-swap decision, never taken), the contents
+ * of losses UNSPECIFIED; no retry, no silent fall-back.
+ * to_set_autoencoder_online_persistent: 0 route A; 1 automatic (default); 2 route B wherever it can run.  The automatic
+ * rule takes route B only inside what was scanned and found ahead: fp32, TWO layers, a logistic code layer under (logistic,
+ * squaredError), a plan of at most G* = 12 workgroups, no layer wider than 784, n_idx >= 256; everything else route A.  Read
+ * from tools/autoencoder_online_scan.py on an MI355X (profiles/autoencoder_online_scan.txt; fp32, logistic layers, 256
+ * samples, us a sample by device events, median of 7, the caller's own loop of to_autoencoder_stack_minibatch_sgd(minibatch =
+ * 1) / route A / route B): 784 -> H -> 784: 21.5 / 21.5 / 9.5 at H = 16 (G = 1), 21.9 / 22.8 / 11.0 at 32 (G = 2), 22.0 / 23.0 /
+ * 13.7 at 64 (G = 3), 22.3 / 23.1 / 14.9 at 128 (G = 6), 23.4 / 24.3 / 16.2 at 256 (G = 12); 32 -> 8 -> 32 (G = 1): 18.7 / 20.6 /
+ * 4.0.  784 -> 256 -> 32 -> 256 -> 784 (G = 14): 38.7 / 39.5 / 47.8, route B LOSES -- the only deeper stack scanned, so deeper
+ * stacks stay on route A.  A timed window is a few milliseconds: the figures carry scheduler noise.  NOT MEASURED, and on
+ * route A unless forced: fp64, tanh and identity layers, n_idx below 256; not measured but inside the rule: i0 other than
+ * 784 and 32, n_idx above 256.
+ * to_set_autoencoder_online_groups: at least this many workgroups (raised to the next G that gives every workgroup a row;
+ * 0: the plan's own) -- for tests and the scan to reach G > 1 on tiny stacks.  to_autoencoder_online_stats counts calls by
+ * the route that ran them.  to_autoencoder_online_plan_query: the plan the entry would get for widths dims[0 .. n_layers]
+ * under the current groups setting -- exists, G, the rows of layer 1 and of layer L (0 when L = 2) a workgroup owns, LDS
+ * bytes, the grid -- and the placement probe's verdict; launches nothing but that probe; TO_ERR_STATE before to_init with
+ * its outputs untouched.  All process-wide. */
+to_status to_autoencoder_stack_online_sgd(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act,
+                                          int code_act, int out_act, int loss, to_tensor X, int64_t n_idx,
+                                          const int64_t* idx_or_null, double rate, to_tensor losses_or_null);
+to_status to_set_autoencoder_online_persistent(int on, int* previous_or_null);  /* 0 per sample, 1 automatic, 2 wherever in range */
+to_status to_set_autoencoder_online_groups(int min_groups, int* previous_or_null); /* 0: the plan's own G; else at least this many */
+to_status to_autoencoder_online_stats(int64_t* persistent_runs, int64_t* per_sample_runs);
+to_status to_autoencoder_online_plan_query(int dtype, int n_layers, const int64_t* dims, int* exists, int* G, int* slice_first,
+                                           int* slice_last, int64_t* lds_bytes, int64_t* grid, int* placement_ok);
+
 /* Per-sample online SGD -- `foldl' (\nt (i,o) -> trainNetwork loss rate i o nt)` (app/MNIST.hs:390-396,
  * app/Dots.hs:74-80) -- of the same stacks over rows idx[0..n_idx) (null: rows 0..n_idx-1) of the resident batched X / Y,
  * parameters updated in place, as ONE persistent launch: the workgroups keep the parameters in LDS between samples,

@@ -138,6 +138,13 @@ SIGNATURES = {
                                  C.c_int, c_tensor, C.c_double, c_tensor],
     "to_autoencoder_stack_minibatch_sgd": [C.c_int, C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int,
                                            C.c_int, C.c_int, c_tensor, C.c_int64, i64p, C.c_int64, C.c_double, c_tensor],
+    "to_autoencoder_stack_online_sgd": [C.c_int, C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int,
+                                        C.c_int, C.c_int, c_tensor, C.c_int64, i64p, C.c_double, c_tensor],
+    "to_set_autoencoder_online_persistent": [C.c_int, C.POINTER(C.c_int)],
+    "to_set_autoencoder_online_groups": [C.c_int, C.POINTER(C.c_int)],
+    "to_autoencoder_online_stats": [i64p, i64p],
+    "to_autoencoder_online_plan_query": [C.c_int, C.c_int, i64p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), i64p, i64p, C.POINTER(C.c_int)],
     "to_fflayer_stack_online_sgd": [C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int,
                                     c_tensor, c_tensor, C.c_int64, i64p, C.c_double],
     "to_fflayer_stack_infer": [C.c_int, C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, c_tensor, c_tensor,

@@ -588,6 +588,22 @@ void launch_induce_seq(int dtype, const InduceSeqPlan& plan, int L, const int64_
                        const void* const* b, void* X, const void* Y, int64_t y_sm, void* gx, void* losses, int64_t B,
                        int64_t iters, double rate, int head, int act_kind, hipStream_t s);
 int64_t induce_seq_status(int64_t* row);   // 0, or the iteration (1-based) at which a wait timed out
+// ae_online.hip: per-sample `trainEncoder` over the rows idx of X in one launch (to_autoencoder_stack_online_sgd, route B).
+// kinds[l]: ACT_KIND_* behind layer l (0-based), kinds[L - 1] the head's activation (a squaredError head).  A plan with
+// G > 1 may only be launched where online_sgd_placement_ok() holds.
+constexpr int AE_ONLINE_MAX_LAYERS = 6;
+struct AeOnlinePlan {
+  int G = 1;          // workgroups
+  int rpw = 0;        // rows of layer 1 per workgroup
+  int spw = 0;        // rows of layer L per workgroup (L >= 3; else 0)
+  size_t lds = 0;     // dynamic LDS bytes
+  int64_t grid = 0;   // workgroups launched
+};
+bool ae_online_plan(int dtype, int L, const int64_t* dims, int min_groups, AeOnlinePlan* plan);
+void launch_ae_online(int dtype, const AeOnlinePlan& plan, int L, const int64_t* dims, const int* kinds, void* const* W,
+                      void* const* b, const void* X, const long long* idx_dev, int64_t n, double rate, void* losses,
+                      hipStream_t s);
+int ae_online_status();   // 0, or the sample (1-based) at which a wait timed out
 
 }  // namespace to
 

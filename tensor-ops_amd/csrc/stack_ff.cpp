@@ -1,5 +1,5 @@
 // The one-call entry points for ffLayer stacks: to_fflayer_stack_grad / _sgd / _minibatch_sgd / _online_sgd / _infer / _induce,
-// and for encoder / decoder pairs of them: to_autoencoder_stack_run / _decode / _grad / _sgd / _minibatch_sgd.
+// and for encoder / decoder pairs of them: to_autoencoder_stack_run / _decode / _grad / _sgd / _minibatch_sgd / _online_sgd.
 #include <deque>
 
 #include "api_util.hpp"
@@ -613,6 +613,159 @@ to_status to_autoencoder_stack_minibatch_sgd(int n_enc, int n_dec, const to_tens
   API_BEGIN
   ae_minibatch_impl(n_enc, n_dec, w, b, hidden_act, code_act, out_act, loss, X, n_idx, idx_or_null, minibatch, rate,
                     losses_or_null);
+  API_END
+}
+
+// ---- `foldl' (flip (trainEncoder loss r))` over the rows of a data set as one call ------------------------------------------
+// Step j is one to_autoencoder_stack_sgd step on row idx[j] alone, from the parameters step j - 1 left.  Route A, per
+// sample: minibatch_steps with a minibatch of one row -- the launches and the bits of to_autoencoder_stack_minibatch_sgd
+// (minibatch = 1); takes every stack.  Route B, persistent (ae_online.hip): all n_idx samples in ONE launch, where its plan
+// fits, the head is a squaredError one and (G > 1) the placement probe holds.
+static int g_ae_online_persistent = 1;   // to_set_autoencoder_online_persistent: 0 per sample, 1 auto, 2 wherever in range
+static int g_ae_online_min_groups = 0;   // to_set_autoencoder_online_groups
+static int64_t g_ae_online_persistent_runs = 0, g_ae_online_sample_runs = 0;
+// The automatic rule takes route B only inside what tools/autoencoder_online_scan.py scanned and found it ahead on: fp32, TWO
+// layers, logistic code layer under the (logistic, squaredError) head, a plan of at most G* workgroups, no layer wider than
+// 784, and at least 256 samples a call (a shorter chain spreads the parameters' trip into LDS and back over fewer samples).
+// Everything else -- fp64, tanh and identity layers, deeper stacks, short chains -- was not scanned or lost and takes route A.
+// profiles/autoencoder_online_scan.txt, us a sample route A / route B: 784 -> H -> 784: 21.5 / 9.5 at H = 16 (G = 1), 22.8 / 11.0 at
+// 32 (G = 2), 23.0 / 13.7 at 64 (G = 3), 23.1 / 14.9 at 128 (G = 6), 24.3 / 16.2 at 256 (G = 12, so G* = 12); 32 -> 8 -> 32: 20.6 /
+// 4.0.  784 -> 256 -> 32 -> 256 -> 784 (G = 14): 39.5 / 47.8, route B LOSES.
+constexpr int AE_ONLINE_AUTO_MAX_G = 12;
+constexpr int64_t AE_ONLINE_AUTO_MAX_WIDTH = 784, AE_ONLINE_AUTO_MIN_SAMPLES = 256;
+
+static void ae_online_impl(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act, int code_act,
+                           int out_act, int loss, to_tensor X, int64_t n_idx, const int64_t* idx, double rate, to_tensor losses) {
+  const std::string F = "to_autoencoder_stack_online_sgd: ";
+  require_init();
+  no_capture("to_autoencoder_stack_online_sgd");
+  NONNULL(X);
+  const std::vector<int> acts = ae_acts(n_enc, n_dec, w, b, hidden_act, code_act, F);
+  const int head = ae_loss_head(out_act, loss, F), L = n_enc + n_dec;
+  TO_CHECK(n_idx >= 1, TO_ERR_ARG, F + "needs at least one sample");
+  TO_CHECK(X->rank == 1 && X->batch > 0, TO_ERR_SHAPE, F + "X must be batched vectors, got " + shape_str(X));
+  TO_CHECK(X->contiguous(), TO_ERR_ARG, F + "X must be contiguous");
+  const int dt = X->dtype;
+  const int64_t N = X->batch, i0 = X->dims[0];
+  TO_CHECK(stack_params_check(L, w, b, nullptr, nullptr, dt, i0) == i0, TO_ERR_SHAPE,
+           F + "the decoder's last layer must have X's width");
+  if (losses) {
+    TO_CHECK(losses->dtype == dt, TO_ERR_ARG, F + "X and losses have different dtypes");
+    TO_CHECK(losses->rank == 0 && losses->batch == n_idx && losses->contiguous(), TO_ERR_SHAPE,
+             F + "losses must be a contiguous batched scalar of batch n_idx");
+    bool bad = stack_overlap(losses, X);
+    for (int l = 0; l < L; ++l) bad = bad || stack_overlap(losses, w[l]) || stack_overlap(losses, b[l]);
+    TO_CHECK(!bad, TO_ERR_ARG, F + "losses overlaps X or a parameter");
+  }
+  for (int64_t k = 0; idx && k < n_idx; ++k) TO_CHECK(idx[k] >= 0 && idx[k] < N, TO_ERR_SHAPE, F + "sample index out of range");
+  TO_CHECK(idx || n_idx <= N, TO_ERR_SHAPE, F + "more samples than rows");
+
+  // The route.  Shapes, the pair and the two settings decide it; the placement probe is only asked where they leave it open.
+  AeOnlinePlan plan;
+  int64_t dims[AE_ONLINE_MAX_LAYERS + 1] = {0};
+  bool persistent = false;
+  if (g_ae_online_persistent != 0 && head != 1 && L <= AE_ONLINE_MAX_LAYERS && n_idx <= 2147483647LL) {
+    dims[0] = i0;
+    int64_t widest = i0;
+    for (int l = 0; l < L; ++l) widest = std::max(widest, dims[l + 1] = w[l]->dims[0]);
+    persistent = ae_online_plan(dt, L, dims, g_ae_online_min_groups, &plan) &&
+                 (g_ae_online_persistent == 2 ||
+                  (dt == TO_F32 && L == 2 && acts[0] == ACT_KIND_LOGISTIC && head == 2 && plan.G <= AE_ONLINE_AUTO_MAX_G &&
+                   widest <= AE_ONLINE_AUTO_MAX_WIDTH && n_idx >= AE_ONLINE_AUTO_MIN_SAMPLES)) &&
+                 (plan.G == 1 || online_sgd_placement_ok(S()));   // (the exchanges' precondition: one XCD's L2)
+  }
+  if (!persistent) {
+    // (its own validation repeats the checks above and adds the refusals of a one-row step, all before its first launch)
+    const StackStep step{L, w, b, w, b, acts.data(), head, dt, true, rate};
+    minibatch_steps(step, X, nullptr, n_idx, idx, 1, losses, F);
+    TO_HIP(hipStreamSynchronize(S()));
+    g_ae_online_sample_runs++;
+    return;
+  }
+  ensure(X);
+  for (int l = 0; l < L; ++l) { ensure(w[l]); ensure(b[l]); }
+  if (losses) claim(losses);
+  void *wp[AE_ONLINE_MAX_LAYERS], *bp[AE_ONLINE_MAX_LAYERS];
+  int kinds[AE_ONLINE_MAX_LAYERS];
+  for (int l = 0; l < L; ++l) {  // in-place writes: recorded readers of the old values first, new identities after
+    claim(w[l]);
+    claim(b[l]);
+    wp[l] = w[l]->ptr;
+    bp[l] = b[l]->ptr;
+    kinds[l] = acts[(size_t)l];
+  }
+  kinds[L - 1] = head == 2 ? ACT_KIND_LOGISTIC : head == 3 ? ACT_KIND_TANH : ACT_KIND_IDENTITY;
+  Holder order;
+  const long long* idx_dev = nullptr;
+  if (idx) {
+    const int64_t nl = (n_idx * 8 + 3) / 4;   // n_idx int64 in a float-typed pool buffer
+    order.t = new_tensor(1, &nl, 0);
+    host_to_device(order.t->ptr, idx, (size_t)n_idx * sizeof(int64_t), S());
+    idx_dev = static_cast<const long long*>(order.t->ptr);
+  }
+  launch_ae_online(dt, plan, L, dims, kinds, wp, bp, X->ptr, idx_dev, n_idx, rate, losses ? losses->ptr : nullptr, S());
+  TO_HIP(hipStreamSynchronize(S()));   // the order buffer goes back to the pool; the watchdog's verdict is read
+  const int bad = ae_online_status();
+  TO_CHECK(bad == 0, TO_ERR_HIP,
+           F + "the persistent kernel gave up waiting for a workgroup at sample " + std::to_string(bad - 1) +
+               " (the write-back is all or nothing: this run aborted, the parameters are unchanged; losses is unspecified)");
+  g_ae_online_persistent_runs++;
+}
+
+to_status to_autoencoder_stack_online_sgd(int n_enc, int n_dec, const to_tensor* w, const to_tensor* b, int hidden_act,
+                                          int code_act, int out_act, int loss, to_tensor X, int64_t n_idx,
+                                          const int64_t* idx_or_null, double rate, to_tensor losses_or_null) {
+  API_BEGIN
+  ae_online_impl(n_enc, n_dec, w, b, hidden_act, code_act, out_act, loss, X, n_idx, idx_or_null, rate, losses_or_null);
+  API_END
+}
+
+to_status to_set_autoencoder_online_persistent(int on, int* previous_or_null) {
+  API_BEGIN
+  TO_CHECK(on >= 0 && on <= 2, TO_ERR_ARG,
+           "to_set_autoencoder_online_persistent: 0 (per sample), 1 (automatic) or 2 (wherever in range)");
+  if (previous_or_null) *previous_or_null = g_ae_online_persistent;
+  g_ae_online_persistent = on;
+  API_END
+}
+
+to_status to_set_autoencoder_online_groups(int min_groups, int* previous_or_null) {
+  API_BEGIN
+  TO_CHECK(min_groups >= 0 && min_groups <= 32, TO_ERR_ARG,
+           "to_set_autoencoder_online_groups: 0 (the plan's own G) or at least this many workgroups, up to 32");
+  if (previous_or_null) *previous_or_null = g_ae_online_min_groups;
+  g_ae_online_min_groups = min_groups;
+  API_END
+}
+
+to_status to_autoencoder_online_stats(int64_t* persistent_runs, int64_t* per_sample_runs) {
+  API_BEGIN
+  if (persistent_runs) *persistent_runs = g_ae_online_persistent_runs;
+  if (per_sample_runs) *per_sample_runs = g_ae_online_sample_runs;
+  API_END
+}
+
+// The plan of ae_online.hip as the entry above would get it (to_set_autoencoder_online_groups included), and the placement
+// probe's verdict.  Launches nothing but that probe (once a process).
+to_status to_autoencoder_online_plan_query(int dtype, int n_layers, const int64_t* dims, int* exists, int* G, int* slice_first,
+                                           int* slice_last, int64_t* lds_bytes, int64_t* grid, int* placement_ok) {
+  API_BEGIN
+  require_init();
+  NONNULL(dims); NONNULL(exists); NONNULL(G); NONNULL(slice_first); NONNULL(slice_last); NONNULL(lds_bytes); NONNULL(grid);
+  NONNULL(placement_ok);
+  TO_CHECK(dtype == TO_F32 || dtype == TO_F64, TO_ERR_ARG, "unknown dtype");
+  TO_CHECK(n_layers >= 2 && n_layers <= AE_ONLINE_MAX_LAYERS, TO_ERR_ARG,
+           "autoencoder_online_plan_query: 2..6 layers (dims holds n_layers + 1 widths)");
+  AeOnlinePlan plan;
+  const bool ok = ae_online_plan(dtype, n_layers, dims, g_ae_online_min_groups, &plan);
+  const bool placed = online_sgd_placement_ok(S());
+  *exists = ok ? 1 : 0;
+  *G = ok ? plan.G : 0;
+  *slice_first = ok ? plan.rpw : 0;
+  *slice_last = ok ? plan.spw : 0;
+  *lds_bytes = ok ? (int64_t)plan.lds : 0;
+  *grid = ok ? plan.grid : 0;
+  *placement_ok = placed ? 1 : 0;
   API_END
 }
 

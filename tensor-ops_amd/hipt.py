@@ -538,6 +538,57 @@ class HipT:
             losses.h if losses is not None else None))
         return losses
 
+    def autoencoder_online_sgd(self, ws, bs, n_enc, X, rate, idx=None, n=None, out_act="logistic", loss="squaredError",
+                               hidden_act="logistic", code_act="logistic", want_losses=False):
+        """`trainEncoder` folded over the rows idx (None: rows 0..n-1, n None: every row) of the resident X, one row an
+        update, parameters updated in place (to_autoencoder_stack_online_sgd); the losses [n_idx] if asked for"""
+        arr = None
+        if idx is not None:
+            arr = np.ascontiguousarray(idx, dtype=np.int64)
+            n = len(arr) if n is None else n
+        elif n is None:
+            n = X.batch
+        losses = self._alloc((), int(n)) if want_losses and n >= 1 else None
+        check(lib().to_autoencoder_stack_online_sgd(
+            *self._ae_args(ws, bs, n_enc, hidden_act, code_act, out_act, loss), X.h, int(n),
+            arr.ctypes.data_as(C.POINTER(C.c_int64)) if arr is not None else None, float(rate),
+            losses.h if losses is not None else None))
+        return losses
+
+    @staticmethod
+    def autoencoder_online_persistent(on):
+        """to_set_autoencoder_online_persistent: 0 per sample, 1 automatic, 2 wherever in range; returns the previous setting"""
+        prev = C.c_int()
+        check(lib().to_set_autoencoder_online_persistent(int(on), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
+    def autoencoder_online_groups(min_groups):
+        """to_set_autoencoder_online_groups: 0 the plan's own G, else at least this many workgroups; returns the previous
+        setting"""
+        prev = C.c_int()
+        check(lib().to_set_autoencoder_online_groups(int(min_groups), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
+    def autoencoder_online_stats():
+        """(persistent runs, per-sample runs)"""
+        p, q = C.c_int64(), C.c_int64()
+        check(lib().to_autoencoder_online_stats(C.byref(p), C.byref(q)))
+        return p.value, q.value
+
+    def autoencoder_online_plan(self, dims, dtype=None):
+        """Debug (to_autoencoder_online_plan_query): the plan of the persistent autoencoder kernel for the stack of widths
+        `dims` under the current to_set_autoencoder_online_groups, running nothing.  "exists" False: the kernel refuses it"""
+        dt = self.to_dtype if dtype is None else (capi.TO_F64 if dtype in ("f64", capi.TO_F64) else capi.TO_F32)
+        d = (C.c_int64 * len(dims))(*[int(v) for v in dims])   # (a stack outside 2..6 layers: TO_ERR_ARG from the library)
+        ex, g, first, last, ok = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        lds, grid = C.c_int64(), C.c_int64()
+        check(lib().to_autoencoder_online_plan_query(dt, len(dims) - 1, d, C.byref(ex), C.byref(g), C.byref(first),
+                                                     C.byref(last), C.byref(lds), C.byref(grid), C.byref(ok)))
+        return {"exists": bool(ex.value), "G": g.value, "slice_first": first.value, "slice_last": last.value,
+                "lds_bytes": lds.value, "grid": grid.value, "placement_ok": bool(ok.value)}
+
     def stack_online_sgd(self, ws, bs, X, Y, n, rate, idx=None, out_act="softmax", loss="crossEntropy",
                          hidden_act="logistic"):
         """per-sample SGD over rows idx[0..n) (None: rows 0..n-1) of X / Y in one launch, parameters updated in place

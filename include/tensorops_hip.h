@@ -599,7 +599,25 @@ to_status to_fflayer_stack_infer(int n_layers, const to_tensor* w, const to_tens
  * 0 per step; 1 automatic (default): persistent where the kernel holds W' in LDS (fp32 n_l <= 201, fp64 n_l <= 142), the
  * threshold measured in DESIGN.md section 3.3 -- on logistic states; a tanh state takes the same routes by the same
  * threshold, which has NOT been measured for tanh --, per step otherwise; 2 persistent wherever in range.  Process-wide.
- * to_rnn_stats counts the calls with a stateful layer: all of its recurrences persistent, or at least one per step. */
+ * to_rnn_stats counts the calls with a stateful layer: all of its recurrences persistent, or at least one per step.
+ * The wide route (csrc/rnn_wide.hip; dense entries only, the ragged ones keep their routes).  Above the LDS range of the
+ * persistent kernel (fp32 n_l >= 202, fp64 n_l >= 143) and up to n_l = 1024, B <= 128: W' is split by columns over the G <= 32
+ * workgroups of a group, which keep their slabs in LDS for all T steps and exchange a step's new vector as tagged words; up
+ * to 8 groups of R = ceil(B / min(8, B)) rows run side by side; ONE launch per layer and direction whatever T.  No plan
+ * (today's routes): fp64 above n_l = 768 (a G = 32 slab no longer fits 160 KiB), and wherever the R rows' buffers do
+ * not fit beside the slab (fp32 n_l = 1024: B <= 24).  Needs the placement probe of the online-SGD kernel to hold.  Every sum
+ * has an order fixed by (dtype, n_l, B, the groups setting): a repeated call gives the same bits, a row's bits do not depend
+ * on the other rows.  The routes agree to rounding, not bit for bit.
+ * to_set_rnn_wide: 0 off (DEFAULT: every call takes exactly the routes above); 1 automatic -- the wide route on the shapes
+ * where tools/rnn_wide_scan.py found it ahead of both other routes (profiles/rnn_wide_scan.txt; DESIGN.md section 3.3 cites
+ * the rows), today's routes everywhere else; 2 wherever a plan exists.  Consulted before to_set_rnn_persistent.  For
+ * to_rnn_stats a wide recurrence counts as persistent.  to_set_rnn_wide_groups: at least this many workgroups a group (0:
+ * the plan's own G, the smallest of 2, 4, 8, 16, 32 that fits; G is lowered until no workgroup is without columns).
+ * to_rnn_wide_stats: wide launches issued, and calls that ended in a timeout.  to_rnn_wide_plan_query: the plan for (dtype,
+ * H, B) under the current groups setting; launches nothing.
+ * Every wait of the wide kernel is bounded (TOPS_ONLINE_TIMEOUT_S, 2 s).  A wait that runs out: TO_ERR_HIP naming the layer,
+ * the direction and the step.  sgd: the parameters and states are untouched.  run / grad: the destinations are
+ * UNSPECIFIED.  No retry, no silent fall-back. */
 enum { TO_RNN_STATELESS = -1 };
 to_status to_rnn_stack_run(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
                            const to_tensor* b, int hidden_act, int out_act, to_tensor X, to_tensor out,
@@ -613,6 +631,11 @@ to_status to_rnn_stack_sgd(int n_layers, const int* state_act, const to_tensor* 
                            double rate_state, double rate_params, to_tensor losses_or_null);
 to_status to_set_rnn_persistent(int on, int* previous_or_null);
 to_status to_rnn_stats(int64_t* persistent_runs, int64_t* stepwise_runs);
+to_status to_set_rnn_wide(int on, int* previous_or_null);                /* 0 off (default), 1 automatic, 2 wherever a plan exists */
+to_status to_set_rnn_wide_groups(int min_groups, int* previous_or_null);  /* 0: the plan's own G; else at least this many */
+to_status to_rnn_wide_stats(int64_t* launches, int64_t* timeouts);
+to_status to_rnn_wide_plan_query(int dtype, int64_t H, int64_t B, int* exists, int* G, int* C, int* R, int* groups, int* mfma,
+                                 int64_t* lds_bytes);
 
 /* The same three entries for a batch whose sequences have DIFFERENT lengths (`trainNetwork` of Recurrent.hs takes a list
  * [(x, y)] of any length): the argument list of the dense sibling with `lens` directly after the data tensors.  lens is a

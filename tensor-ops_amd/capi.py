@@ -159,6 +159,11 @@ SIGNATURES = {
                          c_tensor],
     "to_set_rnn_persistent": [C.c_int, C.POINTER(C.c_int)],
     "to_rnn_stats": [i64p, i64p],
+    "to_set_rnn_wide": [C.c_int, C.POINTER(C.c_int)],
+    "to_set_rnn_wide_groups": [C.c_int, C.POINTER(C.c_int)],
+    "to_rnn_wide_stats": [i64p, i64p],
+    "to_rnn_wide_plan_query": [C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                               C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), i64p],
     "to_rnn_stack_run_ragged": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor),
                                 C.POINTER(c_tensor), C.c_int, C.c_int, c_tensor, i64p, c_tensor, C.POINTER(c_tensor)],
     "to_rnn_stack_grad_ragged": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor),

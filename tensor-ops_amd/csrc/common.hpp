@@ -478,6 +478,24 @@ struct RnnSeqPlan {
 bool rnn_seq_plan(int dtype, int64_t H, int64_t B, RnnSeqPlan* p);
 void launch_rnn_seq(int dtype, bool reverse, const RnnSeqPlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T,
                     int64_t H, int act_kind, hipStream_t s);
+// rnn_wide.hip: the same recurrence for the widths above rnn_seq_plan's LDS range, W' split by columns over the G workgroups
+// of a group, up to 8 groups of R rows side by side (B <= 128), one launch for all T steps.  A plan may only be launched
+// where online_sgd_placement_ok() holds (a performance precondition: a group behind one XCD's L2).
+struct RnnWidePlan {
+  bool exists = false;
+  int G = 0, C = 0;       // workgroups of a group; columns of M a workgroup owns (the last one H - (G - 1) C)
+  int Cp = 0;             // the slab's row stride in LDS
+  int R = 0, groups = 0;  // rows a group; groups that have rows
+  int nsl = 0, klen = 0;  // K slices and their length
+  bool mfma = false;      // R > 4: the MFMA form of the inner product
+  size_t lds_bytes = 0;
+};
+bool rnn_wide_plan(int dtype, int64_t H, int64_t B, int min_groups, RnnWidePlan* p);
+void rnn_wide_begin();   // before a call's first launch: the status back to "no report"
+// id: what the status names beside the step if a wait of this launch runs out (the driver's layer and direction)
+void launch_rnn_wide(int dtype, bool reverse, const RnnWidePlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T,
+                     int64_t H, int act_kind, int64_t id, hipStream_t s);
+int64_t rnn_wide_status(int64_t* id);   // 0, or the step (1-based) at which a wait timed out
 // rnn_ragged.hip: sequences of different lengths (to_rnn_stack_*_ragged).  The row schedule: the sequences sorted by length,
 // descending and stable; at step t the active ones are the first cnt[t] sorted positions and their packed rows are
 // off[t] .. off[t] + cnt[t] - 1, N = off[Tmax] rows in all.  The tables live on the device, O(B + T) int32.

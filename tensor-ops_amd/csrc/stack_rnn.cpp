@@ -6,7 +6,9 @@
 // the weight gradients dZ^T X and dZ^T S_prev (+ the bias row sums) and the input cotangents dZ W (hidden_act' of the layer
 // below in the epilogue).  Per stateful layer `prev` is the state before each step (block 0 = the initial states) and `after`
 // the state after it.  What is left is each stateful layer's recurrence: persistent (rnn_seq.hip / rnn_ragged.hip, one launch
-// per layer and direction for all steps) or per step (one GEMM with the addend, plus one elementwise launch).
+// per layer and direction for all steps), wide (rnn_wide.hip: dense rows, the widths above rnn_seq.hip's LDS range, W' split
+// over the workgroups of a group, one launch per layer and direction too; off unless to_set_rnn_wide turns it on) or per step
+// (one GEMM with the addend, plus one elementwise launch).
 // One validator (rnn_stack_check), one forward (rnn_forward), one backward (rnn_backward) and one update (rnn_apply_sgd) serve
 // the dense entries, the ragged ones, generation's per-step route and online SGD's per-sequence route; dense and ragged
 // differ in their RnnRows and in how rows move to and from the caller (rnn_rows_in / rnn_rows_out).
@@ -30,6 +32,36 @@ static int64_t g_rnn_persistent_runs = 0, g_rnn_stepwise_runs = 0;
 static bool rnn_persistent_for(int dt, int64_t H, int64_t B, RnnSeqPlan* plan) {
   if (g_rnn_persistent == 0 || !rnn_seq_plan(dt, H, B, plan)) return false;
   return g_rnn_persistent == 2 || plan->m_lds;
+}
+
+// ---- the wide route (rnn_wide.hip), dense rows only -----------------------------------------------------------------------
+static int g_rnn_wide = 0;               // to_set_rnn_wide: 0 off (default), 1 automatic, 2 wherever a plan exists
+static int g_rnn_wide_min_groups = 0;    // to_set_rnn_wide_groups: 0 the plan's own G
+static int64_t g_rnn_wide_launches = 0, g_rnn_wide_timeouts = 0;
+// The automatic rule: the wide route exactly on the scanned (dtype, H range, B range, T range) where tools/rnn_wide_scan.py
+// found it ahead of BOTH other routes by more than the scan's run-to-run spread at T = 16 AND T = 128
+// (profiles/rnn_wide_scan.txt, ms per to_rnn_stack_grad call wide / per step / forced rnn_seq_kernel, T = 128):
+//   fp32, B = 1 and 16, H = 256: 1.02 / 2.02 / 2.04 and 1.18 / 1.90 / 2.14; H = 512: 1.01 / 1.99 / 7.90 and 1.21 / 2.24 / 8.17;
+//         H = 1024: 1.16 / 2.06 / 40.3 and 1.35 / 2.46 / 42.9 (T = 16: ahead in all six rows)    -> 256 <= H <= 1024, B <= 16
+//   fp32, B = 128, H = 512: 2.10 / 3.03 / 8.40 (T = 16: 0.378 / 0.444 / 1.18)                        -> H = 512, B <= 128
+//   fp32, B = 128, H = 256: 2.11 / 2.52 / 2.36 but T = 16: 0.384 / 0.389 / 0.395, WITHIN THE SPREAD: not taken;
+//         H = 1024, B = 128: no plan
+//   fp64, B = 1 and 16, H = 256: 0.76 / 1.99 / 2.34 and 1.11 / 1.95 / 2.45; H = 512: 0.96 / 2.31 / 8.64 and 1.43 / 2.62 / 8.81
+//         (T = 16: ahead in all four rows)                                                        -> 256 <= H <= 512, B <= 16
+//   fp64, B = 128, H = 256: 2.08 / 3.81 / 2.94 (T = 16: 0.377 / 0.558 / 0.476)                       -> H = 256, B <= 128
+//         H = 512, B = 128: no plan
+// The wide route lost no scanned row.  NOT MEASURED, and on today's routes under mode 1: tanh states, T below 16 or above 128,
+// H below 256 or between the scanned widths' rows at B above 16, fp64 above H = 512.
+static bool rnn_wide_auto(int dt, int64_t H, int64_t B, int64_t T, int kind) {
+  if (kind != ACT_KIND_LOGISTIC || T < 16 || T > 128) return false;
+  if (dt == TO_F32) return (H >= 256 && H <= 1024 && B <= 16) || (H == 512 && B <= 128);
+  return (H >= 256 && H <= 512 && B <= 16) || (H == 256 && B <= 128);
+}
+// Does the wide kernel take a layer of width H over B dense sequences?  Consulted before rnn_persistent_for.
+static bool rnn_wide_for(int dt, int64_t H, int64_t B, int64_t T, int kind, RnnWidePlan* plan) {
+  if (g_rnn_wide == 0 || !rnn_wide_plan(dt, H, B, g_rnn_wide_min_groups, plan)) return false;
+  if (g_rnn_wide == 1 && !rnn_wide_auto(dt, H, B, T, kind)) return false;
+  return online_sgd_placement_ok(S());   // (the exchange's performance precondition: a group behind one XCD's L2)
 }
 
 enum class RnnMode { Run, Grad, Sgd };
@@ -90,10 +122,14 @@ struct RnnForward {  // what the forward leaves behind
   std::vector<const void*> outp;       // what the layer above reads: hidden_act(z_l), all rows
   std::vector<RnnSeqPlan> plan;
   std::vector<char> persist;
-  bool any_state = false, all_persistent = true;
+  std::vector<RnnWidePlan> wplan;
+  std::vector<char> wide;              // the layer's recurrences go through rnn_wide.hip (counts as persistent)
+  bool allow_wide = false;             // set by the dense driver alone: it reads the watchdog's verdict
+  bool any_state = false, all_persistent = true, any_wide = false;
   const void* no_bias_for_head = nullptr;  // stateless last layer of a run: the head launch adds b_L
   explicit RnnForward(int n)
-      : Z(n), Sa(n), Sp(n), WT(n), Ah(n), prev(n, nullptr), after(n, nullptr), outp(n, nullptr), plan(n), persist(n, 0) {}
+      : Z(n), Sa(n), Sp(n), WT(n), Ah(n), prev(n, nullptr), after(n, nullptr), outp(n, nullptr), plan(n), persist(n, 0),
+        wplan(n), wide(n, 0) {}
 };
 
 static void rnn_forward(int dt, int n_layers, const int* state_act, const RnnStateSrc* init, const to_tensor* ws,
@@ -131,13 +167,18 @@ static void rnn_forward(int dt, int n_layers, const int* state_act, const RnnSta
         const int64_t dd[2] = {B, n}, ss[2] = {init[l].bstride, init[l].stride};
         launch_copy_strided(dt, init[l].ptr, sp, 2, dd, ss, S());
       }
-      f.persist[l] = rnn_persistent_for(dt, n, B, &f.plan[l]);
-      f.all_persistent = f.all_persistent && f.persist[l];
-      if (f.persist[l]) {
+      f.wide[l] = f.allow_wide && !r.tb && rnn_wide_for(dt, n, B, r.T, kind, &f.wplan[l]);
+      f.persist[l] = !f.wide[l] && rnn_persistent_for(dt, n, B, &f.plan[l]);
+      f.all_persistent = f.all_persistent && (f.persist[l] || f.wide[l]);
+      if (f.persist[l] || f.wide[l]) {
         const int64_t dd[2] = {n, n}, ss[2] = {1, n};  // W'^T: M[k][j] = W'[j][k]
         f.WT[l].t = new_tensor(2, dd, 0, dt);
         launch_copy_strided(dt, ws[l]->ptr, f.WT[l].t->ptr, 2, dd, ss, S());
-        if (r.tb) launch_rnn_ragged_seq(dt, false, f.plan[l], *r.tb, f.WT[l].t->ptr, z, sa, sp, n, kind, S());
+        if (f.wide[l]) {
+          f.any_wide = true;
+          g_rnn_wide_launches++;
+          launch_rnn_wide(dt, false, f.wplan[l], f.WT[l].t->ptr, z, sp, B, r.T, n, kind, 2 * l, S());
+        } else if (r.tb) launch_rnn_ragged_seq(dt, false, f.plan[l], *r.tb, f.WT[l].t->ptr, z, sa, sp, n, kind, S());
         else launch_rnn_seq(dt, false, f.plan[l], f.WT[l].t->ptr, z, sp, B, r.T, n, kind, S());
       } else {
         // z_t = P_t + s_{t-1} W'^T (in place), s_t = state_act(z_t), on the step's rows; the states before step t >= 1 are
@@ -384,7 +425,10 @@ static void rnn_backward(const RnnStackArgs& a, const RnnChecked& c, const RnnRo
       // dz_t = G_t + (dz_{t+1} W') (.) state_act'(s_t) where the sequence has a step t + 1, in place over G
       const int kind = rnn_state_kind(a.state_act[l]);
       void *sp = f.prev[l], *sa = f.after[l];
-      if (f.persist[l] && r.tb) {
+      if (f.wide[l]) {
+        g_rnn_wide_launches++;
+        launch_rnn_wide(dt, true, f.wplan[l], ws[l]->ptr, dz, sp, B, r.T, n, kind, 2 * l + 1, S());
+      } else if (f.persist[l] && r.tb) {
         launch_rnn_ragged_seq(dt, true, f.plan[l], *r.tb, ws[l]->ptr, dz, sa, sp, n, kind, S());
       } else if (f.persist[l]) {
         launch_rnn_seq(dt, true, f.plan[l], ws[l]->ptr, dz, sp, B, r.T, n, kind, S());
@@ -446,6 +490,19 @@ static void rnn_apply_sgd(const RnnStackArgs& a, int dt, const RnnGrads& g) {
   }
 }
 
+// The wide kernel's verdict, read once behind a call's last wide launch: a wait that ran out is TO_ERR_HIP.
+static void rnn_wide_verdict(const RnnStackArgs& a) {
+  TO_HIP(hipStreamSynchronize(S()));
+  int64_t id = 0;
+  const int64_t bad = rnn_wide_status(&id);
+  if (bad == 0) return;
+  g_rnn_wide_timeouts++;
+  TO_CHECK(false, TO_ERR_HIP,
+           std::string(a.name()) + ": the wide recurrent kernel gave up waiting for a workgroup at step " + std::to_string(bad - 1) +
+               " of layer " + std::to_string(id / 2) + "'s " + (id % 2 ? "reverse" : "forward") + " recurrence (" +
+               (a.mode == RnnMode::Sgd ? "the parameters and states are untouched" : "the destinations are unspecified") + ")");
+}
+
 // ---- the driver: a checked call whose operands exist and whose destinations are claimed, over the rows r ---------------
 // (persistent_runs / stepwise_runs: the entry family's counters)
 static void rnn_stack_rows(const RnnStackArgs& a, const RnnChecked& c, const RnnRows& r, int64_t& persistent_runs,
@@ -457,6 +514,10 @@ static void rnn_stack_rows(const RnnStackArgs& a, const RnnChecked& c, const Rnn
   const void* Xt = rnn_rows_in(dt, r, a.X, xh);
   const void* Yt = !run ? rnn_rows_in(dt, r, a.Y, yh) : nullptr;
   RnnForward f(n_layers);
+  if (!r.tb && g_rnn_wide != 0) {
+    f.allow_wide = true;
+    rnn_wide_begin();
+  }
   rnn_forward(dt, n_layers, a.state_act, rnn_initial_states(n_layers, a.s).data(), a.ws, a.w, a.b, c.hk, run, Xt, a.X->dims[1],
               r, f);
   if (f.any_state) (f.all_persistent ? persistent_runs : stepwise_runs)++;
@@ -476,6 +537,7 @@ static void rnn_stack_rows(const RnnStackArgs& a, const RnnChecked& c, const Rnn
     rnn_head_rows(dt, f, n_layers, c.nL, r.N, a.out_act, ot, zb);
     rnn_rows_out(dt, r, ot, a.out, c.nL);
     TO_HIP(hipStreamSynchronize(S()));
+    if (f.any_wide) rnn_wide_verdict(a);
     return;
   }
   RnnGrads g(n_layers);
@@ -483,6 +545,7 @@ static void rnn_stack_rows(const RnnStackArgs& a, const RnnChecked& c, const Rnn
   Holder dzL;
   rnn_loss_head(a, c, r, f, Yt, dzL);
   rnn_backward(a, c, r, f, Xt, dzL, g);
+  if (f.any_wide) rnn_wide_verdict(a);   // before the update: a wait that ran out updates nothing
   if (a.mode == RnnMode::Sgd) rnn_apply_sgd(a, dt, g);   // after the whole backward: a failure before here updates nothing
   TO_HIP(hipStreamSynchronize(S()));
 }
@@ -984,6 +1047,45 @@ to_status to_set_rnn_persistent(int on, int* previous_or_null) {
   TO_CHECK(on >= 0 && on <= 2, TO_ERR_ARG, "to_set_rnn_persistent: 0 (per step), 1 (automatic) or 2 (wherever in range)");
   if (previous_or_null) *previous_or_null = g_rnn_persistent;
   g_rnn_persistent = on;
+  API_END
+}
+
+to_status to_set_rnn_wide(int on, int* previous_or_null) {
+  API_BEGIN
+  TO_CHECK(on >= 0 && on <= 2, TO_ERR_ARG, "to_set_rnn_wide: 0 (off), 1 (automatic) or 2 (wherever a plan exists)");
+  if (previous_or_null) *previous_or_null = g_rnn_wide;
+  g_rnn_wide = on;
+  API_END
+}
+
+to_status to_set_rnn_wide_groups(int min_groups, int* previous_or_null) {
+  API_BEGIN
+  TO_CHECK(min_groups >= 0 && min_groups <= 32, TO_ERR_ARG,
+           "to_set_rnn_wide_groups: 0 (the plan's own G) or at least this many workgroups a group, up to 32");
+  if (previous_or_null) *previous_or_null = g_rnn_wide_min_groups;
+  g_rnn_wide_min_groups = min_groups;
+  API_END
+}
+
+to_status to_rnn_wide_stats(int64_t* launches, int64_t* timeouts) {
+  API_BEGIN
+  if (launches) *launches = g_rnn_wide_launches;
+  if (timeouts) *timeouts = g_rnn_wide_timeouts;
+  API_END
+}
+
+// The plan of rnn_wide.hip as the dense entries would get it (to_set_rnn_wide_groups included).  Launches nothing.
+to_status to_rnn_wide_plan_query(int dtype, int64_t H, int64_t B, int* exists, int* G, int* C, int* R, int* groups, int* mfma,
+                                 int64_t* lds_bytes) {
+  API_BEGIN
+  NONNULL(exists); NONNULL(G); NONNULL(C); NONNULL(R); NONNULL(groups); NONNULL(mfma); NONNULL(lds_bytes);
+  TO_CHECK(dtype == TO_F32 || dtype == TO_F64, TO_ERR_ARG, "unknown dtype");
+  RnnWidePlan p;
+  rnn_wide_plan(dtype, H, B, g_rnn_wide_min_groups, &p);
+  *exists = p.exists ? 1 : 0;
+  *G = p.G; *C = p.C; *R = p.R; *groups = p.groups;
+  *mfma = p.mfma ? 1 : 0;
+  *lds_bytes = (int64_t)p.lds_bytes;
   API_END
 }
 

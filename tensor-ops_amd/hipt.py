@@ -739,6 +739,40 @@ class HipT:
         return p.value, q.value
 
     @staticmethod
+    def rnn_wide(on):
+        """to_set_rnn_wide: 0 off, 1 automatic, 2 wherever a plan exists; returns the previous setting"""
+        prev = C.c_int()
+        check(lib().to_set_rnn_wide(int(on), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
+    def rnn_wide_groups(min_groups):
+        """to_set_rnn_wide_groups: 0 the plan's own G, else at least this many workgroups a group; returns the previous
+        setting"""
+        prev = C.c_int()
+        check(lib().to_set_rnn_wide_groups(int(min_groups), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
+    def rnn_wide_stats():
+        """(wide launches, calls that ended in a timeout)"""
+        p, q = C.c_int64(), C.c_int64()
+        check(lib().to_rnn_wide_stats(C.byref(p), C.byref(q)))
+        return p.value, q.value
+
+    @staticmethod
+    def rnn_wide_plan(H, B, dtype="f32"):
+        """to_rnn_wide_plan_query: the wide kernel's plan for (dtype, H, B) under the current to_set_rnn_wide_groups,
+        running nothing.  "exists" False: today's routes"""
+        dt = capi.TO_F64 if dtype in ("f64", capi.TO_F64) else capi.TO_F32
+        ex, g, c, r, groups, mfma = (C.c_int() for _ in range(6))
+        lds = C.c_int64()
+        check(lib().to_rnn_wide_plan_query(dt, int(H), int(B), C.byref(ex), C.byref(g), C.byref(c), C.byref(r),
+                                           C.byref(groups), C.byref(mfma), C.byref(lds)))
+        return {"exists": bool(ex.value), "G": g.value, "C": c.value, "R": r.value, "groups": groups.value,
+                "mfma": bool(mfma.value), "lds_bytes": lds.value}
+
+    @staticmethod
     def rnn_ragged_stats():
         """(persistent runs, per-step runs) of the ragged entries (to_rnn_ragged_stats)"""
         p, q = C.c_int64(), C.c_int64()

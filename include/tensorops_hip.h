@@ -302,7 +302,8 @@ enum {
   TO_GEMM_FAMILY_SMALL = 7,
   TO_GEMM_FAMILY_MFMA = 8,
   TO_GEMM_FAMILY_F64 = 9,
-  TO_GEMM_FAMILY_NAIVE = 10
+  TO_GEMM_FAMILY_NAIVE = 10,
+  TO_GEMM_FAMILY_KW16_64 = 11 /* the fp64 tile menu; asked just ahead of KW64, numbered last so that 0 .. 10 keep their meaning */
 };
 enum { TO_GEMM_EPI_BIAS = 1, TO_GEMM_EPI_ACT = 2, TO_GEMM_EPI_DACT = 4, TO_GEMM_EPI_BETA = 8, TO_GEMM_EPI_ROWSUM = 16 };
 /* The problem: C[m, n] = A[m, k] . B[k, n] of `dtype`, `batch` >= 1 of them (reduce_batch: summed into one C), each operand
@@ -316,6 +317,16 @@ enum { TO_GEMM_EPI_BIAS = 1, TO_GEMM_EPI_ACT = 2, TO_GEMM_EPI_DACT = 4, TO_GEMM_
 to_status to_gemm_route_query(int dtype, int64_t m, int64_t n, int64_t k, int64_t batch, int reduce_batch, int a_transposed,
                               int b_transposed, int epilogue, int capacity, int* families, int* n_leaves, int* epilogue_ok,
                               int* small_route, int* split_workspace);
+/* The fp64 tile menu (csrc/gemm_kwave_f64.hip, gemm_kw64_menu_kernel): mid-size Double products on 48x48 / 48x64 / 64x48 /
+ * 32x64 / 64x32 output tiles (menu index 0 .. 4) where a few hundred 64x64 tiles leave CUs idle.  mode 0: off (DEFAULT: every
+ * contraction takes exactly the route it took before the menu existed); 1: automatic -- the menu on the shapes where
+ * tools/gemm_f64_menu_scan.py measured it ahead (profiles/gemm_f64_menu_scan.txt; everything unscanned keeps its route);
+ * 2: wherever the kernel can run (batch 1, fp64, 16 rows / columns / k on, every operand layout -- but an even M where A is
+ * stored m-contiguous (transposed) and an even N where B is stored n-contiguous (not transposed): a 16-byte pair of either is
+ * in or out of the matrix as a whole --, alpha / beta Cin / bias / activation / act').  tile: -1 the scan's best tile on a
+ * scanned shape, the cost rule's elsewhere; 0 .. 4 that menu entry.  Process-wide, for contractions planned from now
+ * on; *previous_mode_or_null gets the mode it replaces.  Anything else: TO_ERR_ARG, nothing changed. */
+to_status to_set_gemm_f64_menu(int mode, int tile, int* previous_mode_or_null);
 /* stream capture of everything enqueued between begin/end into a HIP graph */
 to_status to_graph_begin(void);
 to_status to_graph_end(to_graph* out);

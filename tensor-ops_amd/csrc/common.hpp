@@ -298,6 +298,10 @@ bool gemm_kw16_applicable(const GemmProblem& p);  // gemm_kw16.hip: the same des
 void launch_gemm_kw16(const GemmProblem& p, hipStream_t s);
 bool gemm_kw64_applicable(const GemmProblem& p);  // gemm_kwave_f64.hip: the same design on v_mfma_f64_16x16x4_f64
 void launch_gemm_kw64(const GemmProblem& p, hipStream_t s);
+bool gemm_kw64_menu_applicable(const GemmProblem& p);  // gemm_kwave_f64.hip: fp64 on 48x48 / 48x64 / 64x48 / 32x64 / 64x32 tiles (to_set_gemm_f64_menu; off by default)
+bool gemm_kw64_menu_everywhere(const GemmProblem& p);  // ... and the switch is at mode 2 (wherever the kernel can)
+void launch_gemm_kw64_menu(const GemmProblem& p, hipStream_t s);
+bool gemm_kw64_menu_set(int mode, int tile, int* previous_mode);  // false: mode or tile out of range, nothing changed
 bool gemm_skinnyk64_applicable(const GemmProblem& p);  // gemm_skinnyk_f64.hip: config 5's shape class in Double
 void launch_gemm_skinnyk64(const GemmProblem& p, hipStream_t s);
 struct GemmEpilogue {

@@ -59,6 +59,7 @@ void gemm_plan(const GemmProblem& p, GemmLeaves& out, bool sub) {
   // tiles of 48x48 instead of 144 of 64x64 split three ways)
   if (gemm_kw16_applicable(p)) return out.push(GEMM_KW16, p, sub);
   if (gemm_kw_applicable(p)) return out.push(GEMM_KW, p, sub);
+  if (gemm_kw64_menu_applicable(p)) return out.push(GEMM_KW16_64, p, sub);   // (to_set_gemm_f64_menu; never with the switch off)
   if (gemm_kw64_applicable(p)) return out.push(GEMM_KW64, p, sub);
   if (p.K % 16 != 0 && p.K >= 128 && p.M * p.N >= 65536 && !p.reduce_batch && !p.rowsum && !p.loss_rows && p.act == 0 &&
       !p.dact) {
@@ -131,6 +132,7 @@ void run_gemm(const GemmProblem& p) {
       case GEMM_SKINNYK64: launch_gemm_skinnyk64(q, S()); break;
       case GEMM_KW16: launch_gemm_kw16(q, S()); break;
       case GEMM_KW: launch_gemm_kw(q, S()); break;
+      case GEMM_KW16_64: launch_gemm_kw64_menu(q, S()); break;
       case GEMM_KW64: launch_gemm_kw64(q, S()); break;
       case GEMM_SMALL: launch_gemm_small(q, S()); break;
       case GEMM_MFMA: launch_gemm_mfma(q, S()); break;
@@ -166,6 +168,11 @@ bool gemm_small_takes(const GemmProblem& p) {
 bool gemm_small_route(const GemmProblem& p) {
   if (p.M == 0 || p.N == 0 || p.K == 0 || p.batch != 1 || p.reduce_batch) return false;
   if (gemv_form(p)) return false;   // (a large matVec / vecMat / outer product: gemv.hip, through run_gemm)
+  // (the fp64 tile menu at mode 2, "wherever the kernel can": what it takes goes through the plan, epilogue carried; the
+  //  skinny-K routes ahead of it in the plan never hold together with the small-GEMM range.  Mode 1 changes no answer here: its
+  //  scan timed the plain product against the plan's route, not a fused launch against the small-GEMM kernel, so 640^3 and
+  //  768^3 -- under 200 tiles of 64x64 -- keep the small-first launch for a fused epilogue)
+  if (gemm_kw64_menu_everywhere(p)) return false;
   // (a few tiles under a very long K -- a weight gradient over a data set, 300 x 60000 x 784: one workgroup a tile here whatever K
   //  is, 400 us; 291 split over workgroups in gemm_kwave.hip, which carries alpha / beta C / bias / activation but no row sums)
   if (p.K >= 8192 && !p.rowsum && !p.loss_rows && !p.tail_out && gemm_kw_long_k(p)) return false;
@@ -178,7 +185,7 @@ bool gemm_small_route(const GemmProblem& p) {
 bool gemm_epilogue_ok(const GemmProblem& p) {
   if (p.M == 0 || p.N == 0 || p.K == 0 || p.batch == 0) return false;
   if (gemm_small_route(p) || gemm_skinnyk_applicable(p) || gemm_skinnyk64_applicable(p) || gemv_form(p)) return true;
-  if (p.dtype == TO_F64) return gemm_kw64_applicable(p);
+  if (p.dtype == TO_F64) return gemm_kw64_menu_applicable(p) || gemm_kw64_applicable(p);
   const GemmFamily f = gemm_tiled_family(p);
   return f == GEMM_SMALL || f == GEMM_MFMA;
 }
@@ -216,6 +223,14 @@ static GemmProblem route_query_problem(int dtype, int64_t m, int64_t n, int64_t 
 }
 
 }  // namespace to
+
+extern "C" to_status to_set_gemm_f64_menu(int mode, int tile, int* previous_mode_or_null) {
+  using namespace to;
+  API_BEGIN
+  TO_CHECK(gemm_kw64_menu_set(mode, tile, previous_mode_or_null), TO_ERR_ARG,
+           "to_set_gemm_f64_menu: mode 0 (off), 1 (automatic) or 2 (wherever the kernel can); tile -1 (the cost rule) or a menu index 0 .. 4");
+  API_END
+}
 
 // ---- the debug query (include/tensorops_hip.h) ---------------------------------------------------------------------------
 extern "C" to_status to_gemm_route_query(int dtype, int64_t m, int64_t n, int64_t k, int64_t batch, int reduce_batch,

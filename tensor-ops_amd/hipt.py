@@ -746,6 +746,14 @@ class HipT:
         return prev.value
 
     @staticmethod
+    def set_gemm_f64_menu(mode, tile=-1):
+        """to_set_gemm_f64_menu: the fp64 tile menu 0 off (default), 1 automatic, 2 wherever the kernel can; tile -1 (the scan's
+        best tile on a scanned shape, else the cost rule's) or a menu index 0 .. 4 = 48x48 / 48x64 / 64x48 / 32x64 / 64x32; returns the previous mode"""
+        prev = C.c_int()
+        check(lib().to_set_gemm_f64_menu(int(mode), int(tile), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
     def rnn_wide_groups(min_groups):
         """to_set_rnn_wide_groups: 0 the plan's own G, else at least this many workgroups a group; returns the previous
         setting"""

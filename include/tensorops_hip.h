@@ -786,6 +786,53 @@ to_status to_rnn_stack_online_sgd(int n_layers, const int* state_act, const to_t
 to_status to_set_rnn_online_persistent(int on, int* previous_or_null);   /* 0 per sequence, 1 automatic, 2 wherever in range */
 to_status to_rnn_online_stats(int64_t* persistent_runs, int64_t* per_sequence_runs);
 
+/* Minibatch SGD over a resident set of sequences -- the form a recurrent net is usually trained in: to_rnn_stack_sgd's update,
+ * M sequences an update, folded over the set in one call.  The argument list is to_rnn_stack_online_sgd's with `minibatch`
+ * behind idx_or_null.  For k = 0 .. ceil(n_idx / minibatch) - 1, in order: the sequences idx[k M .. min((k + 1) M, n_idx)) of
+ * X [N; T, i] / Y [N; T, n_L] (idx null: those rows in place) form one batch, and on it the call applies ONE to_rnn_stack_sgd
+ * update: objective sum_b sum_t loss, s -= rate_state * gs, every parameter -= rate_params * g, in place.  The last batch may
+ * be short.  Repeats in idx are allowed, also inside one minibatch.
+ *   losses_or_null  contiguous [n_idx; T]: row j holds the losses of sequence idx[j] under the parameters its update started
+ *                   from.  It may overlap neither X, Y nor a parameter (TO_ERR_ARG).
+ * minibatch < 1 or n_idx < 1: TO_ERR_ARG.  An index out of range (or, with idx null, n_idx > N): TO_ERR_SHAPE.  The stack, the
+ * activations, the (out_act, loss) pairs, the dtypes and shapes are checked as to_rnn_stack_sgd checks a batch of M (and of
+ * the short tail), with its statuses.  Every refusal is decided before the first launch and leaves parameters, states and
+ * losses untouched; refused during graph capture (TO_ERR_STATE); blocks before returning; keeps no handle.
+ * Routes.  Per minibatch (A): the batch gathered by to_batch_gather's kernel (idx null: to_batch_slice's views, no gather),
+ * to_rnn_stack_sgd's own launches on it, losses through the slice [k M ..] -- BIT FOR BIT the caller's loop of
+ * to_batch_gather + to_rnn_stack_sgd; takes every valid stack, fp32 and fp64.  Persistent (B, csrc/rnn_minibatch.hip,
+ * rnn_minibatch_kernel): every update of the call in ONE launch by ONE workgroup (nothing crosses workgroups, the kernel waits
+ * on its own barriers only) on v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64 blocks: inside an update row r = t Mp + q, Mp =
+ * M rounded up to 16, so a step's rows are whole MFMA row blocks; padding rows (q >= the minibatch's size) carry zero input
+ * and a zero dz, are never read from X / Y and never written to losses.  Every layer's W, W' and b and the initial states stay
+ * in LDS for the whole call, k-major, zero-padded to 4 in k and 16 in j, the leading dimension 17 (mod 32) so that neither the
+ * forward's B fragment (16 columns at one k) nor the backward's (one column at 16 k) collapses onto one bank.  Input
+ * projections, the head, the cotangents between layers and the weight gradients (reduction over the rows, applied from the
+ * accumulators straight into LDS) are MFMA tiles dealt to eight waves; a stateful layer's recurrence is serial in t, Hp / 4
+ * MFMAs a block and one LDS-only barrier a step, forward and backward.  What the backward needs of the forward (the tape) is
+ * a pool buffer in global memory: T does not bound the range.  Range: 1..8 layers, M <= 64, fp32 and fp64, padded parameters
+ * plus the two chain blocks [Mp][Hp + 4] within 160 KiB of LDS -- fp32 70 -> 130 (stateful) -> 3 at M = 16 fits (144 KiB), in
+ * fp64 it does not and takes route A.  Every sum's order is fixed by (dtype, widths, M): a repeated call gives the same bits,
+ * and a call cut at a minibatch boundary into two gives the bits of the one call.  The two routes agree to rounding, not bit
+ * for bit.  Not built: a tape in LDS, ragged lengths, M > 64, a form over several workgroups.
+ * to_set_rnn_minibatch_persistent: 0 route A; 2 route B wherever its plan exists; 1 automatic (default): route B exactly on
+ * the rows tools/rnn_minibatch_scan.py scanned where it was ahead of BOTH route A and the caller's loop by more than the row's
+ * run-to-run spread (profiles/rnn_minibatch_scan.txt; fp32, 256 sequences, logistic states and hidden layers, microseconds
+ * an update caller / A / B, spreads 1 - 8 %):
+ *   T = 8, M = 4 and 16:  5 -> 7 -> 5: 128 / 121 / 48 and 130 / 122 / 59;  64 -> 32 -> 10: 125 / 115 / 68 and 126 / 115 / 81;
+ *                         64 -> 64 -> 10: 134 / 122 / 96 and 134 / 123 / 110
+ *                                       -> fp32, logistic, T = 8, 4 <= M <= 16, no width (the input's included) above 64
+ * Where it LOST, and automatic is route A: M = 64 at T = 8 (179 against 159 for 5 -> 7 -> 5, 372 against 139 at H = 64); H = 128
+ * at T = 8 (170 against 141 at M = 4, 184 against 144 at M = 16; M = 64: no plan); every row at T = 64, 2x to 10x behind (343
+ * against 172 for 5 -> 7 -> 5 at M = 4; 3498 against 352 for 64 -> 64 -> 10 at M = 64).  NOT MEASURED, and route A under mode 1:
+ * fp64, tanh, any other T, M below 4.  Process-wide.  to_rnn_minibatch_stats counts calls by the route that ran them. */
+to_status to_rnn_stack_minibatch_sgd(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
+                                     const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
+                                     int64_t n_idx, const int64_t* idx_or_null, int64_t minibatch, double rate_state,
+                                     double rate_params, to_tensor losses_or_null);
+to_status to_set_rnn_minibatch_persistent(int on, int* previous_or_null);   /* 0 per minibatch, 1 automatic, 2 wherever in range */
+to_status to_rnn_minibatch_stats(int64_t* persistent_runs, int64_t* per_minibatch_runs);
+
 /* The same per-sequence training for sequences of DIFFERENT lengths -- `trainNetwork` takes a list [(x, y)] of any length,
  * and folded over a data set every sequence is one update of its own length: to_rnn_stack_online_sgd's argument list with
  * `lens` directly after the data tensors, as the ragged siblings above have it.

@@ -185,6 +185,11 @@ SIGNATURES = {
                                 C.c_double, C.c_double, c_tensor],
     "to_set_rnn_online_persistent": [C.c_int, C.POINTER(C.c_int)],
     "to_rnn_online_stats": [i64p, i64p],
+    "to_rnn_stack_minibatch_sgd": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor), C.POINTER(c_tensor),
+                                   C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int, c_tensor, c_tensor, C.c_int64, i64p,
+                                   C.c_int64, C.c_double, C.c_double, c_tensor],
+    "to_set_rnn_minibatch_persistent": [C.c_int, C.POINTER(C.c_int)],
+    "to_rnn_minibatch_stats": [i64p, i64p],
     "to_rnn_stack_online_sgd_ragged": [C.c_int, C.POINTER(C.c_int), C.POINTER(c_tensor), C.POINTER(c_tensor),
                                        C.POINTER(c_tensor), C.POINTER(c_tensor), C.c_int, C.c_int, C.c_int, c_tensor, c_tensor,
                                        i64p, C.c_int64, i64p, C.c_double, C.c_double, c_tensor],

@@ -595,6 +595,38 @@ struct RnnOnlineOperands {
 // GEN_LDS_MAX; T decides only where the tape lives
 bool rnn_online_plan(int dtype, int L, const int64_t* widths, const int* stateful, int64_t T, RnnOnlinePlan* p);
 void launch_rnn_online(int dtype, const RnnOnlinePlan& p, const RnnOnlineOperands& o, hipStream_t s);
+// rnn_minibatch.hip: minibatch BPTT (to_rnn_stack_minibatch_sgd, route B) -- forward, BPTT and the update of every minibatch of
+// a call, one after the other, in ONE launch by ONE workgroup on 16x16x4 MFMA blocks: the M sequences of an update are the rows
+// of a block.  The plan is the workgroup's LDS map (offsets in elements) and the layout of one row's tape record.
+constexpr int64_t RNN_MINIBATCH_MAX_M = 64;
+struct RnnMinibatchPlan {
+  int w_off[RNN_GEN_MAX_LAYERS] = {}, ws_off[RNN_GEN_MAX_LAYERS] = {}, b_off[RNN_GEN_MAX_LAYERS] = {}, s_off[RNN_GEN_MAX_LAYERS] = {};
+  int ld[RNN_GEN_MAX_LAYERS] = {};   // the leading dimension of layer l's k-major W and W'
+  int t_in[RNN_GEN_MAX_LAYERS] = {}, t_s[RNN_GEN_MAX_LAYERS] = {}, t_dz[RNN_GEN_MAX_LAYERS] = {};   // within a tape record
+  int Mp = 0;               // the minibatch rounded up to 16: rows of one step
+  int chain_off = 0, hs = 0;   // the chain blocks: [2][Mp][hs] at chain_off (the state's ping-pong, then the backward's dz)
+  int64_t rec = 0;          // elements of one row's tape record (every field padded to four elements)
+  int64_t tape_elems = 0;   // T * Mp * rec
+  size_t lds = 0;           // dynamic LDS bytes
+};
+struct RnnMinibatchOperands {
+  int L = 0;
+  int64_t widths[RNN_GEN_MAX_LAYERS + 1] = {};  // i, n_1 .. n_L
+  int state_kind[RNN_GEN_MAX_LAYERS] = {};      // ACT_KIND_* of a stateful layer's state, -1: stateless
+  void *W[RNN_GEN_MAX_LAYERS] = {}, *WS[RNN_GEN_MAX_LAYERS] = {}, *b[RNN_GEN_MAX_LAYERS] = {}, *s[RNN_GEN_MAX_LAYERS] = {};
+  const void *X = nullptr, *Y = nullptr;        // contiguous [N][T][i] and [N][T][n_L]
+  void* losses = nullptr;                       // contiguous [n_idx][T] (optional)
+  const long long* idx = nullptr;               // device [n_idx] (null: sequences 0 .. n_idx-1)
+  void* tape = nullptr;                         // plan.tape_elems elements of global memory
+  int64_t n_idx = 0, M = 0, T = 0;
+  int hidden_kind = 0;
+  bool softmax = true;
+  double rate_state = 0.0, rate_params = 0.0;
+};
+// widths: i, n_1 .. n_L.  False ("no plan": the per-minibatch route): more than 8 layers, M above RNN_MINIBATCH_MAX_M, or the
+// padded parameters, states and chain blocks exceed GEN_LDS_MAX; T decides only the size of the tape
+bool rnn_minibatch_plan(int dtype, int L, const int64_t* widths, const int* stateful, int64_t M, int64_t T, RnnMinibatchPlan* p);
+void launch_rnn_minibatch(int dtype, const RnnMinibatchPlan& p, const RnnMinibatchOperands& o, hipStream_t s);
 // induce_seq.hip: every iteration of `induceNetwork` on every row in one launch (to_fflayer_stack_induce, route B).
 // X [B][i0] contiguous: x_0 on entry, x_iters on exit; gx [B][i0] (optional) the last iteration's gradient; losses
 // [B][iters] (optional).  A plan with G > 1 may only be launched where online_sgd_placement_ok() holds.

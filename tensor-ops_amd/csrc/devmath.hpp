@@ -81,4 +81,9 @@ __device__ __forceinline__ S wave_max(S v) {   // max's NaN rule at every level
 }
 
 }  // namespace dm
+
+// A barrier whose hand-over is in LDS only: the workgroup's LDS accesses are done, its global stores need not be (they are
+// read behind a later __syncthreads()).  A recurrence's per-step barrier (rnn_online.hip, rnn_minibatch.hip).
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 }  // namespace to

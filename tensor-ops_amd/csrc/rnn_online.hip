@@ -67,10 +67,7 @@ __device__ __forceinline__ void for_items(long T, int w, int tid, F&& f) {
     if (c >= w) { c -= w; ++t; }
   }
 }
-// A barrier whose hand-over is in LDS only: the workgroup's LDS accesses are done, its global stores need not be (they are
-// read behind a later __syncthreads()).  A recurrence's per-step barrier.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
+// (the recurrences' per-step barrier is devmath.hpp's lds_barrier: the hand-over is in LDS only)
 // The update of one k-major matrix M[k][j] (W: k over the layer's inputs, src the input rows; W': k over the states, src
 // S_t): M[k][j] -= rate * sum over ascending t of dz_t[j] src_t[k].  A thread owns tiles of 4 columns x 4 k: per step two
 // 16-byte reads (the tape's rows start on 16-byte boundaries and are padded to four elements; what a ragged tile reads of

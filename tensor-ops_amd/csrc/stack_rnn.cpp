@@ -1042,6 +1042,172 @@ to_status to_rnn_online_stats(int64_t* persistent_runs, int64_t* per_sequence_ru
   API_END
 }
 
+// ---- minibatch training: to_rnn_stack_sgd's update folded over minibatches of a resident set, as one call -------------------
+// Update k trains on the sequences idx[k M .. min((k + 1) M, n_idx)) as one batch, from the parameters and learned initial
+// states update k - 1 left.  Per minibatch (route A): the batch gathered by to_batch_gather's kernel (idx null: to_batch_slice's
+// views, no gather), then rnn_stack_dense in Sgd mode -- bit for bit the caller's own loop of to_batch_gather + to_rnn_stack_sgd.
+// Persistent (route B, rnn_minibatch.hip): every update in ONE launch by one workgroup on MFMA blocks, the stack in LDS.
+static int g_rnn_minibatch_persistent = 1;   // to_set_rnn_minibatch_persistent: 0 per minibatch, 1 auto, 2 wherever in range
+static int64_t g_rnn_minibatch_persistent_runs = 0, g_rnn_minibatch_step_runs = 0;
+// The automatic rule: route B exactly on the scanned rows where tools/rnn_minibatch_scan.py found it ahead of BOTH route A and
+// the caller's loop of to_batch_gather + to_rnn_stack_sgd by more than the row's run-to-run spread (the rule of
+// to_set_rnn_wide; profiles/rnn_minibatch_scan.txt: fp32, 256 sequences, logistic states, us an update caller / A / B):
+//   T = 8, M = 4 and 16:  5 -> 7 -> 5: 128 / 121 / 48 and 130 / 122 / 59;  64 -> 32 -> 10: 125 / 115 / 68 and 126 / 115 / 81;
+//                         64 -> 64 -> 10: 134 / 122 / 96 and 134 / 123 / 110 (spreads 2 - 6 %)
+//                                                          -> fp32, T = 8, 4 <= M <= 16, no width (the input's included) above 64
+// Where it LOST, and automatic is route A: T = 8, M = 64 (Mp = 64: 179 against 159 at 5 -> 7 -> 5, 372 against 139 at H = 64);
+// H = 128 at T = 8 (170 against 141 at M = 4, 184 against 144 at M = 16; M = 64: no plan); every row at T = 64 (2x to 10x behind:
+// 343 against 172 at 5 -> 7 -> 5, M = 4; 3498 against 352 at H = 64, M = 64) -- the serial recurrences and the update's
+// row-long reductions read the tape from global memory, and one workgroup has eight waves for all of it.  NOT MEASURED, and on
+// route A under mode 1: fp64, tanh states or hidden layers, any other T, M below 4.
+static bool rnn_minibatch_auto(int dt, int L, const int64_t* widths, bool logistic_only, int64_t M, int64_t T) {
+  return dt == TO_F32 && logistic_only && T == 8 && M >= 4 && M <= 16 && *std::max_element(widths, widths + L + 1) <= 64;
+}
+
+to_status to_rnn_stack_minibatch_sgd(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
+                                     const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
+                                     int64_t n_idx, const int64_t* idx_or_null, int64_t minibatch, double rate_state,
+                                     double rate_params, to_tensor losses_or_null) {
+  API_BEGIN
+  const char* fn = "to_rnn_stack_minibatch_sgd";
+  const std::string F = std::string(fn) + ": ";
+  const int64_t* idx = idx_or_null;
+  const to_tensor losses = losses_or_null;
+  require_init();
+  no_capture(fn);
+  NONNULL(state_act); NONNULL(s); NONNULL(ws); NONNULL(w); NONNULL(b); NONNULL(X); NONNULL(Y);
+  TO_CHECK(n_idx >= 1 && minibatch >= 1, TO_ERR_ARG, F + "needs at least one sequence and a minibatch of at least one");
+  auto set_like = [&](to_tensor t, const char* what) {
+    TO_CHECK(t->rank == 2 && t->batch > 0 && t->contiguous(), TO_ERR_SHAPE,
+             F + what + " must be a batched, contiguous [N; T, n], got " + shape_str(t));
+  };
+  set_like(X, "X");
+  set_like(Y, "Y");
+  const int64_t N = X->batch, T = X->dims[0];
+  const int dt = X->dtype;
+  TO_CHECK(Y->batch == N, TO_ERR_SHAPE, F + "X and Y have different batches");
+  if (losses) {
+    TO_CHECK(losses->dtype == dt, TO_ERR_ARG, F + "losses and X have different dtypes");
+    TO_CHECK(losses->rank == 1 && losses->dims[0] == T && losses->batch == n_idx && losses->contiguous(), TO_ERR_SHAPE,
+             F + "losses must be a contiguous [" + std::to_string(n_idx) + "; " + std::to_string(T) + "], got " + shape_str(losses));
+  }
+  const int64_t M = std::min(minibatch, n_idx), n_steps = (n_idx + M - 1) / M, tail = n_idx - (n_steps - 1) * M;
+  // the stack, the pair and a minibatch's shapes: to_rnn_stack_sgd's checks on what to_batch_gather would hand it, for both
+  // batches that occur
+  RnnChecked chk{};
+  for (const int64_t rows : {M, tail}) {
+    to_tensor_s xv, yv, lv;
+    auto batch_of = [&](to_tensor_s& v, to_tensor t) {
+      v.dtype = t->dtype;
+      v.rank = t->rank;
+      for (int d = 0; d < t->rank; ++d) { v.dims[d] = t->dims[d]; v.strides[d] = t->strides[d]; }
+      v.batch = rows;
+      v.bstride = t->numel();
+    };
+    batch_of(xv, X);
+    batch_of(yv, Y);
+    RnnStackArgs c{RnnMode::Sgd, n_layers, state_act, s, ws, w, b, hidden_act, out_act, &xv, loss, &yv};
+    c.fn = fn;
+    if (losses) { batch_of(lv, losses); c.losses = &lv; }
+    chk = rnn_stack_check(c);
+  }
+  TO_CHECK(idx || n_idx <= N, TO_ERR_SHAPE, F + "more sequences asked for than X holds");
+  for (int64_t j = 0; idx && j < n_idx; ++j)
+    TO_CHECK(idx[j] >= 0 && idx[j] < N, TO_ERR_SHAPE, F + "sequence index out of range");
+  if (losses) {
+    bool bad = stack_overlap(losses, X) || stack_overlap(losses, Y);
+    for (int l = 0; l < n_layers; ++l)
+      bad = bad || stack_overlap(losses, s[l]) || stack_overlap(losses, ws[l]) || stack_overlap(losses, w[l]) || stack_overlap(losses, b[l]);
+    TO_CHECK(!bad, TO_ERR_ARG, F + "losses overlaps X, Y or a parameter");
+  }
+  // The route (rnn_minibatch_auto above).
+  RnnMinibatchPlan plan;
+  bool persistent = false;
+  if (g_rnn_minibatch_persistent != 0 && n_layers <= RNN_GEN_MAX_LAYERS) {
+    const RnnShape sh(n_layers, X->dims[1], state_act, w);
+    bool logistic_only = chk.hk == ACT_KIND_LOGISTIC;
+    for (int l = 0; l < n_layers; ++l) logistic_only = logistic_only && state_act[l] != TO_ACT_TANH;
+    persistent = rnn_minibatch_plan(dt, n_layers, sh.widths, sh.stateful, M, T, &plan) &&
+                 (g_rnn_minibatch_persistent == 2 || rnn_minibatch_auto(dt, n_layers, sh.widths, logistic_only, M, T));
+  }
+
+  RnnStackArgs all{RnnMode::Sgd, n_layers, state_act, s, ws, w, b, hidden_act, out_act, X, loss, Y};
+  rnn_ensure_claim(all, {X, Y}, {losses});
+  // a run of idx on the device, as to_batch_gather uploads its indices: through the pinned ring up to a slot of it, beyond
+  // that the staged transfer into a pool buffer
+  auto upload = [&](const int64_t* host, int64_t count, Holder& h) {
+    if ((size_t)count * sizeof(int64_t) <= 65536)
+      return static_cast<const long long*>(table_upload(host, (size_t)count * sizeof(int64_t), S()));
+    const int64_t nl = (count * 8 + 3) / 4;   // count int64 in a float-typed pool buffer
+    h.t = new_tensor(1, &nl, 0);
+    host_to_device(h.t->ptr, host, (size_t)count * sizeof(int64_t), S());
+    return static_cast<const long long*>(h.t->ptr);
+  };
+  if (persistent) {
+    RnnMinibatchOperands o;
+    o.L = n_layers;
+    o.widths[0] = X->dims[1];
+    for (int l = 0; l < n_layers; ++l) {   // in-place writes: recorded readers of the old values first, new identities after
+      claim(w[l]); claim(b[l]);
+      o.widths[l + 1] = w[l]->dims[0];
+      o.state_kind[l] = !s[l] ? -1 : rnn_state_kind(state_act[l]);
+      o.W[l] = w[l]->ptr; o.b[l] = b[l]->ptr;
+      if (s[l]) {
+        claim(s[l]); claim(ws[l]);
+        o.WS[l] = ws[l]->ptr; o.s[l] = s[l]->ptr;
+      }
+    }
+    Holder order, tape(new_tensor(1, &plan.tape_elems, 0, dt));
+    o.tape = tape.t->ptr;
+    o.X = X->ptr; o.Y = Y->ptr; o.losses = losses ? losses->ptr : nullptr;
+    if (idx) o.idx = upload(idx, n_idx, order);
+    o.n_idx = n_idx; o.M = M; o.T = T;
+    o.hidden_kind = chk.hk;
+    o.softmax = out_act == TO_ACT_SOFTMAX;
+    o.rate_state = rate_state; o.rate_params = rate_params;
+    launch_rnn_minibatch(dt, plan, o, S());
+    TO_HIP(hipStreamSynchronize(S()));   // the order and the tape go back to the pool
+    g_rnn_minibatch_persistent_runs++;
+  } else {
+    for (int64_t k = 0; k < n_steps; ++k) {
+      const int64_t rows = k + 1 == n_steps ? tail : M;
+      Holder xk, yk, order;
+      if (idx) {   // to_batch_gather's upload and launch on this minibatch's run of idx
+        const long long* didx = upload(idx + k * M, rows, order);
+        xk.t = new_tensor(X->rank, X->dims, rows, dt);
+        yk.t = new_tensor(Y->rank, Y->dims, rows, dt);
+        launch_gather_rows(X->ptr, xk.t->ptr, didx, rows, X->numel() * (int64_t)X->esize(), S());
+        launch_gather_rows(Y->ptr, yk.t->ptr, didx, rows, Y->numel() * (int64_t)Y->esize(), S());
+      } else {     // to_batch_slice's views
+        xk.t = new_view(X, X->rank, X->dims, X->strides, rows, X->bstride, k * M * X->bstride);
+        yk.t = new_view(Y, Y->rank, Y->dims, Y->strides, rows, Y->bstride, k * M * Y->bstride);
+      }
+      Holder lk(losses ? new_view(losses, 1, losses->dims, losses->strides, rows, losses->bstride, k * M * losses->bstride) : nullptr);
+      RnnStackArgs a{RnnMode::Sgd, n_layers, state_act, s, ws, w, b, hidden_act, out_act, xk.t, loss, yk.t};
+      a.losses = lk.t; a.rate_state = rate_state; a.rate_params = rate_params; a.fn = fn;
+      rnn_stack_dense(a);
+    }
+    g_rnn_minibatch_step_runs++;
+  }
+  API_END
+}
+
+to_status to_set_rnn_minibatch_persistent(int on, int* previous_or_null) {
+  API_BEGIN
+  TO_CHECK(on >= 0 && on <= 2, TO_ERR_ARG,
+           "to_set_rnn_minibatch_persistent: 0 (per minibatch), 1 (automatic) or 2 (wherever in range)");
+  if (previous_or_null) *previous_or_null = g_rnn_minibatch_persistent;
+  g_rnn_minibatch_persistent = on;
+  API_END
+}
+
+to_status to_rnn_minibatch_stats(int64_t* persistent_runs, int64_t* per_minibatch_runs) {
+  API_BEGIN
+  if (persistent_runs) *persistent_runs = g_rnn_minibatch_persistent_runs;
+  if (per_minibatch_runs) *per_minibatch_runs = g_rnn_minibatch_step_runs;
+  API_END
+}
+
 to_status to_set_rnn_persistent(int on, int* previous_or_null) {
   API_BEGIN
   TO_CHECK(on >= 0 && on <= 2, TO_ERR_ARG, "to_set_rnn_persistent: 0 (per step), 1 (automatic) or 2 (wherever in range)");

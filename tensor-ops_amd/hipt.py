@@ -860,6 +860,41 @@ class HipT:
         check(lib().to_rnn_online_stats(C.byref(p), C.byref(q)))
         return p.value, q.value
 
+    def rnn_stack_minibatch_sgd(self, layers, X, Y, rate_state, rate_params, minibatch, idx=None, n_idx=None, out_act="softmax",
+                                loss="crossEntropy", hidden_act="logistic", want_losses=False):
+        """Minibatch SGD over the sequences idx[0 .. n_idx) (None: sequences 0 .. n_idx-1, all of them when n_idx is None too)
+        of X [N; T, i] / Y [N; T, n_L]: one rnn_stack_sgd update per `minibatch` sequences, parameters and initial states
+        updated in place (to_rnn_stack_minibatch_sgd); the losses [n_idx; T] if asked for"""
+        n, sact, (s, ws, w, b) = self._rnn_arrays(layers)
+        arr = None
+        if idx is not None:
+            arr = np.ascontiguousarray(idx, dtype=np.int64)
+            n_idx = len(arr) if n_idx is None else n_idx
+        elif n_idx is None:
+            n_idx = X.batch
+        n_idx = int(n_idx)
+        losses = self._alloc((X.shape[0],), n_idx) if want_losses and n_idx >= 1 else None
+        check(lib().to_rnn_stack_minibatch_sgd(n, sact, s, ws, w, b, self._HIDDEN[hidden_act], self._RNN_OUT[out_act],
+                                               self._RNN_LOSS[loss], X.h, Y.h, n_idx,
+                                               arr.ctypes.data_as(C.POINTER(C.c_int64)) if arr is not None else None,
+                                               int(minibatch), float(rate_state), float(rate_params),
+                                               losses.h if losses is not None else None))
+        return losses
+
+    @staticmethod
+    def rnn_minibatch_persistent(on):
+        """to_set_rnn_minibatch_persistent: 0 per minibatch, 1 automatic, 2 wherever in range; returns the previous setting"""
+        prev = C.c_int()
+        check(lib().to_set_rnn_minibatch_persistent(int(on), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
+    def rnn_minibatch_stats():
+        """(persistent runs, per-minibatch runs)"""
+        p, q = C.c_int64(), C.c_int64()
+        check(lib().to_rnn_minibatch_stats(C.byref(p), C.byref(q)))
+        return p.value, q.value
+
     def rnn_stack_online_sgd_ragged(self, layers, X, Y, lens, rate_state, rate_params, idx=None, n_idx=None,
                                     out_act="softmax", loss="crossEntropy", hidden_act="logistic", want_losses=False):
         """rnn_stack_online_sgd for sequences of their own lengths (to_rnn_stack_online_sgd_ragged): step j trains on steps

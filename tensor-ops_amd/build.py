@@ -10,7 +10,7 @@ HOST_LIB = os.path.join(HERE, "libtensorops_host.so")
 HOST_DIR = os.path.join(HERE, "host")
 DOTS_BIN = os.path.join(HERE, "tensor-ops-dots-hip")
 MNIST_BIN = os.path.join(HERE, "tensor-ops-mnist-hip")
-SOURCES = ["runtime.cpp", "expr.cpp", "expr_jit.cpp", "rowprog.cpp", "api.cpp", "gemm_route.cpp", "stack_util.cpp", "stack_ff.cpp", "stack_rnn.cpp", "lazy.cpp", "lazy_plan.cpp", "lazy_cache.cpp", "lazy_exec.cpp", "comm.cpp", "gemm_f32_mfma.hip", "gemm_small.hip", "gemm_t32.hip", "gemm_skinnyk.hip", "gemm_kwave.hip", "gemm_kw16.hip", "gemm_kwave_f64.hip", "gemm_skinnyk_f64.hip", "gemm_f64.hip", "ewise.hip", "reduce_layout.hip", "gemv.hip", "fused_fflayer.hip", "p2p.hip", "online_sgd.hip", "infer_head.hip", "rnn_seq.hip", "rnn_wide.hip", "rnn_ragged.hip", "rnn_generate.hip", "rnn_online.hip", "rnn_minibatch.hip", "induce_seq.hip", "minibatch_stage.hip", "recon_head.hip", "ae_online.hip"]
+SOURCES = ["runtime.cpp", "expr.cpp", "expr_jit.cpp", "rowprog.cpp", "api.cpp", "gemm_route.cpp", "stack_util.cpp", "stack_ff.cpp", "stack_rnn.cpp", "lazy.cpp", "lazy_plan.cpp", "lazy_cache.cpp", "lazy_exec.cpp", "comm.cpp", "gemm_f32_mfma.hip", "gemm_small.hip", "gemm_t32.hip", "gemm_skinnyk.hip", "gemm_kwave.hip", "gemm_kw16.hip", "gemm_kwave_f64.hip", "gemm_skinnyk_f64.hip", "gemm_f64.hip", "ewise.hip", "reduce_layout.hip", "gemv.hip", "fused_fflayer.hip", "p2p.hip", "xcd_exchange.hip", "online_sgd.hip", "infer_head.hip", "rnn_seq.hip", "rnn_wide.hip", "rnn_ragged.hip", "rnn_generate.hip", "rnn_online.hip", "rnn_minibatch.hip", "induce_seq.hip", "minibatch_stage.hip", "recon_head.hip", "ae_online.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function"]
 # Kernarg preload: the dispatcher puts a kernel's LEADING scalar and pointer parameters (up to 14 dwords beside the kernarg
@@ -42,6 +42,11 @@ NO_PACKED_FP32 = ["ae_online.hip", "rnn_wide.hip", "rnn_minibatch.hip"]
 # beside the object (build/<stem>-hip-amdgcn-amd-amdhsa-gfx950.s; -save-temps, everything else it leaves is deleted).
 ASM_CHECKED = ["gemm_f32_mfma.hip", "gemm_f64.hip", "gemm_kwave.hip", "gemm_kw16.hip", "gemm_kwave_f64.hip", "gemm_skinnyk.hip",
                "gemm_skinnyk_f64.hip", "gemm_small.hip", "online_sgd.hip"]
+
+
+def extra_flags(src):
+    """what csrc/<src> is compiled with beside FLAGS: the build and tools/device_asm_digest.py compile alike"""
+    return ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] if src in NO_PACKED_FP32 else []
 
 
 def device_asm(src):
@@ -108,7 +113,7 @@ def _build_locked(force, verbose, objdir):
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(hdr_t, os.path.getmtime(spath)):
             continue
         cmd = [hipcc] + FLAGS + ["-x", "hip", "-c", spath, "-o", obj] + (["-save-temps=obj"] if src in ASM_CHECKED else []) + \
-            (["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] if src in NO_PACKED_FP32 else [])
+            extra_flags(src)
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
     # the C++ host mirror compiles in parallel with the kernels
     host_obj = os.path.join(objdir, "toh_api.cpp.o")

@@ -22,17 +22,13 @@
 // writes losses[j].  The three squaredError heads only: a row-split softmax would need a third exchange for the row's
 // maximum and sum.
 //
-// The exchanges are online_sgd.hip's: every 32-bit word of a partial travels with its sample's tag in one L1-bypassing
-// 64-bit store, a reader polls the words it needs until their tags say "this sample" -- data and "it is there" are one
-// transaction through the XCD's L2 -- and each exchange has two parity slots: a slot is written again two samples later,
-// which its writer can only reach after every workgroup has published the sample in between, i.e. after all of them have
-// read this one.  A reader sums the words as they arrive, in registers: no landing area in LDS.  A wait that outlives the
-// watchdog reports the sample and the launch ends in ONE compare-and-swap decision, commit or abort, that every workgroup
-// obeys: the write-back is all or nothing.  G = 1 touches none of this: no placement, no exchange through memory, no vote.
+// The two exchanges, their watchdog and the commit are xcd_exchange.hpp's; a reader sums the words as they arrive, in
+// registers: no landing area in LDS.  G = 1 touches none of this: no placement, no exchange through memory, no vote.
 // Activations are a small per-layer switch (hidden, code and head activation of a layer may all differ); no hand-written
 // instruction sequences: the wave sum is the shared butterfly.
 #include "common.hpp"
 #include "devmath.hpp"
+#include "xcd_exchange.hpp"
 
 namespace to {
 
@@ -40,8 +36,6 @@ namespace {
 
 constexpr int AO_THREADS = 512, AO_NW = AO_THREADS / 64;
 constexpr int AO_XREGS = 4;       // input elements prefetched per thread: i0 <= 2048
-constexpr int AO_DECISION = 32;   // the commit's decision word, behind the 32 vote slots
-constexpr unsigned long long AO_COMMIT = 1ull, AO_ABORT = 2ull;
 // red[0 .. 7]: a wave's part of a loss; [8]: a wait timed out (only ever set); [9]: the decision; [10]: G = 1's own loss partial
 constexpr int AO_RED = 16, AO_FLAG = 8, AO_VERDICT = 9, AO_LOSS = 10;
 constexpr int64_t AO_LDS_MAX = 160 * 1024;
@@ -69,19 +63,9 @@ struct AeOnlineArgs {
 template <class S> __device__ __forceinline__ S ao_act(int kind, S z) { return kind == ACT_KIND_IDENTITY ? z : dm::act(kind, z); }
 template <class S> __device__ __forceinline__ S ao_dact(int kind, S h) { return kind == ACT_KIND_IDENTITY ? S(1) : dm::dact(kind, h); }
 
-// one number into its exchange slot: each 32-bit word with the sample's tag in ONE 64-bit store
-template <class S>
-__device__ __forceinline__ void ao_publish(unsigned long long* slot, S v, unsigned tag) {
-  constexpr int WORDS = sizeof(S) / 4;
-  unsigned wd[WORDS];
-  __builtin_memcpy(wd, &v, sizeof(S));
-#pragma unroll
-  for (int u = 0; u < WORDS; ++u)
-    __hip_atomic_store(slot + u, ((unsigned long long)tag << 32) | wd[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Number j of every workgroup's contribution (ex: [G][n][WORDS]), summed in workgroup order -- every reader gets the same
 // bits.  Four workgroups' words are in flight together; a word is asked for again until its tag says "this sample".
+// (the poll is written out: on a shared primitive, in each shape tried, this file's assembly moves -- xcd_exchange.hpp)
 template <class S>
 __device__ __forceinline__ S ao_gather(const unsigned long long* ex, int G, int n, int j, unsigned tag, long long timeout, bool& ok) {
   constexpr int WORDS = sizeof(S) / 4;
@@ -129,21 +113,6 @@ __device__ __forceinline__ S ao_gather(const unsigned long long* ex, int G, int 
       }
   }
   return sum;
-}
-
-// a 64-lane dot product of w[0 .. K) with x[0 .. K), both in LDS: four independent chains a lane, then the butterfly
-template <class S>
-__device__ __forceinline__ S ao_wave_dot(const S* __restrict__ w, const S* __restrict__ x, int K, int lane) {
-  S acc0 = S(0.), acc1 = S(0.), acc2 = S(0.), acc3 = S(0.);
-  int k = lane;
-  for (; k + 192 < K; k += 256) {
-    acc0 = dm::fma(w[k], x[k], acc0);
-    acc1 = dm::fma(w[k + 64], x[k + 64], acc1);
-    acc2 = dm::fma(w[k + 128], x[k + 128], acc2);
-    acc3 = dm::fma(w[k + 192], x[k + 192], acc3);
-  }
-  for (; k < K; k += 64) acc0 = dm::fma(w[k], x[k], acc0);
-  return dm::wave_sum((acc0 + acc1) + (acc2 + acc3));
 }
 
 // (S = float or double)
@@ -219,16 +188,6 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
   __syncthreads();
   const S rate = a.rate;
   constexpr int WORDS = sizeof(S) / 4;
-  // a peer never showed up (uniform: read behind a barrier): this workgroup votes "failed", decides ABORT for everybody
-  // (unless COMMIT was decided -- impossible: that needs this vote to be "ok") and leaves
-  auto give_up = [&]() {
-    if (tid == 0) {
-      __hip_atomic_store(a.votes + g, 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      unsigned long long expect = 0ull;
-      __hip_atomic_compare_exchange_strong(a.votes + AO_DECISION, &expect, AO_ABORT, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-    }
-  };
   // the next sample's row is requested behind the LAST wait on memory of a sample: loads return in order, so issued any
   // earlier an exchange would sit behind a row that comes from HBM
   auto prefetch = [&](long t) {
@@ -251,7 +210,7 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
     __syncthreads();
     // ---- layer 1, this workgroup's rows: one wave a row ----------------------------------------------------------------
     for (int r = wave; r < nr; r += AO_NW) {
-      const S z = ao_wave_dot(W1s + (long)r * i0, xs, i0, lane);
+      const S z = dm::wave_dot(W1s + (long)r * i0, xs, i0, lane);
       if (lane == 0) h1s[r] = ao_act(a.kind[0], z + b1s[r]);
     }
     __syncthreads();
@@ -266,7 +225,7 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
         S acc = S(0.);
         for (int r = 0; r < nr; ++r) acc = dm::fma(w[r], h1s[r], acc);
         if (G == 1) act[2][j] = acc;   // (read back by this very thread)
-        else ao_publish(ex + ((long)g * o2 + j) * WORDS, acc, tag);
+        else xe::publish(ex + ((long)g * o2 + j) * WORDS, acc, tag);
       }
       for (int j = tid; j < o2; j += AO_THREADS) {
         const S s = G == 1 ? act[2][j] : ao_gather<S>(ex, G, o2, j, tag, a.timeout, ok);
@@ -290,7 +249,7 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
     }
     __syncthreads();
     if (red[AO_FLAG] != S(0.)) {
-      give_up();
+      xe::give_up(a.votes, g);   // (a peer never showed up; uniform: read behind a barrier)
       return;
     }
     if (!deep) {
@@ -304,7 +263,7 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
       for (int l = 2; l + 1 < L; ++l) {
         const int K = a.dims[l], O = a.dims[l + 1];
         for (int j = wave; j < O; j += AO_NW) {
-          const S z = ao_wave_dot(Wr[l] + (long)j * (K + 1), act[l], K, lane);
+          const S z = dm::wave_dot(Wr[l] + (long)j * (K + 1), act[l], K, lane);
           if (lane == 0) act[l + 1][j] = ao_act(a.kind[l], z + br[l][j]);
         }
         __syncthreads();
@@ -312,7 +271,7 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
       // ---- layer L on rows S_g: z, the head and this workgroup's part of the squared error ------------------------------------
       S lpart = S(0.);   // (lane 0 of a wave: its rows in order)
       for (int r = wave; r < ns; r += AO_NW) {
-        const S z = ao_wave_dot(WLs + (long)r * (KL + 1), act[L - 1], KL, lane);
+        const S z = dm::wave_dot(WLs + (long)r * (KL + 1), act[L - 1], KL, lane);
         if (lane == 0) {
           const S h = ao_act(a.kind[L - 1], z + bLs[r]), d = h - xs[s0 + r];
           lpart += d * d;
@@ -331,7 +290,7 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
         } else {
           for (int q = 0; q < AO_NW; ++q) c += red[q];
         }
-        if (G > 1) ao_publish(ex + ((long)g * n2 + k) * WORDS, c, tag);
+        if (G > 1) xe::publish(ex + ((long)g * n2 + k) * WORDS, c, tag);
         else if (k < KL) dz[L - 1][k] = c;
         else red[AO_LOSS] = c;
       }
@@ -347,7 +306,7 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
       }
       __syncthreads();
       if (red[AO_FLAG] != S(0.)) {
-        give_up();
+        xe::give_up(a.votes, g);   // (a peer never showed up; uniform: read behind a barrier)
         return;
       }
       // ---- back through the replicated layers (OLD weights) --------------------------------------------------------------------
@@ -412,7 +371,8 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
     }
     __syncthreads();
   }
-  // ---- commit: ONE decision for all workgroups (online_sgd.hip's: votes, then a single compare-and-swap everybody obeys) -------
+  // ---- commit: ONE decision for all workgroups --------------------------------------------------------------------------
+  // (written out here and in online_sgd.hip: as a function, in each form tried, this file's assembly moves -- xcd_exchange.hpp)
   if (G > 1) {
     if (tid == 0) __hip_atomic_store(a.votes + g, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (tid < G) {
@@ -421,7 +381,7 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
       while (true) {
         v = __hip_atomic_load(a.votes + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (v != 0) break;
-        if (__hip_atomic_load(a.votes + AO_DECISION, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;   // (decided meanwhile)
+        if (__hip_atomic_load(a.votes + xe::DECISION, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;   // (decided meanwhile)
         if (wall_clock64() - c0 > a.timeout) break;
         __builtin_amdgcn_s_sleep(1);
       }
@@ -430,12 +390,12 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
     __syncthreads();
     if (tid == 0) {
       unsigned long long expect = 0ull;
-      const unsigned long long mine = red[AO_FLAG] != S(0.) ? AO_ABORT : AO_COMMIT;
-      const bool won = __hip_atomic_compare_exchange_strong(a.votes + AO_DECISION, &expect, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+      const unsigned long long mine = red[AO_FLAG] != S(0.) ? xe::ABORT : xe::COMMIT;
+      const bool won = __hip_atomic_compare_exchange_strong(a.votes + xe::DECISION, &expect, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                                             __HIP_MEMORY_SCOPE_AGENT);
       const unsigned long long decision = won ? mine : expect;   // (expect holds what was there)
-      red[AO_VERDICT] = decision == AO_COMMIT ? S(1.) : S(0.);
-      if (decision == AO_ABORT && *a.status == 0) *a.status = (int)(a.n + 1);   // (no sample to name: reported as "sample n")
+      red[AO_VERDICT] = decision == xe::COMMIT ? S(1.) : S(0.);
+      if (decision == xe::ABORT && *a.status == 0) *a.status = (int)(a.n + 1);   // (no sample to name: reported as "sample n")
     }
     __syncthreads();
     if (red[AO_VERDICT] != S(1.)) return;
@@ -461,14 +421,7 @@ __global__ __launch_bounds__(AO_THREADS) void ae_online_kernel(AeOnlineArgs<S> a
   }
 }
 
-struct AeOnlineState {
-  void* exch = nullptr;
-  size_t exch_bytes = 0;
-  unsigned long long* votes = nullptr;
-  int* status = nullptr;
-  int* status_dev = nullptr;
-};
-AeOnlineState g_ao;
+xe::XcdExchange g_ao(true);
 
 template <class S>
 void launch_ae_online_t(const AeOnlinePlan& plan, int L, const int64_t* dims, const int* kinds, void* const* W, void* const* b,
@@ -490,18 +443,12 @@ void launch_ae_online_t(const AeOnlinePlan& plan, int L, const int64_t* dims, co
   a.G = plan.G;
   a.rpw = plan.rpw;
   a.spw = plan.spw;
-  a.ex1 = static_cast<unsigned long long*>(g_ao.exch);
-  a.ex2 = reinterpret_cast<unsigned long long*>(static_cast<char*>(g_ao.exch) + ex1_bytes);
-  a.votes = g_ao.votes;
-  a.status = g_ao.status_dev;
-  static const double timeout_s = [] { const char* e = getenv("TOPS_ONLINE_TIMEOUT_S"); return e ? atof(e) : 2.0; }();
-  a.timeout = (long long)(timeout_s * 100e6);
-  static bool attr = false;
-  if (!attr) {
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ae_online_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)AO_LDS_MAX));
-    attr = true;
-  }
+  a.ex1 = g_ao.exch();
+  a.ex2 = g_ao.exch() + ex1_bytes / 8;
+  a.votes = g_ao.votes();
+  a.status = g_ao.status_dev<int>();
+  a.timeout = xe::watchdog_ticks();
+  xe::allow_full_lds<ae_online_kernel<S>>();
   launch_k(ae_online_kernel<S>, dim3((unsigned)plan.grid), dim3(AO_THREADS), plan.lds, s, a);
 }
 
@@ -543,29 +490,15 @@ void launch_ae_online(int dtype, const AeOnlinePlan& plan, int L, const int64_t*
   TO_CHECK(L >= 2 && L <= AE_ONLINE_MAX_LAYERS && n >= 1 && n <= 2147483647LL, TO_ERR_STATE, "internal: autoencoder online kernel: out of range");
   const size_t words = dtype == TO_F64 ? 2 : 1;
   const size_t ex1 = (size_t)2 * plan.G * dims[2] * words * 8, ex2 = L >= 3 ? (size_t)2 * plan.G * (dims[L - 1] + 1) * words * 8 : 0;
-  if (!g_ao.votes) {
-    TO_HIP(hipMalloc(&g_ao.votes, 512));   // 32 vote slots + the decision word
-    TO_HIP(hipHostMalloc(&g_ao.status, sizeof(int), hipHostMallocMapped));
-    TO_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&g_ao.status_dev), g_ao.status, 0));
-  }
-  *g_ao.status = 0;
-  if (g_ao.exch_bytes < ex1 + ex2) {
-    if (g_ao.exch) (void)hipFree(g_ao.exch);
-    g_ao.exch = nullptr;
-    g_ao.exch_bytes = 0;
-    TO_HIP(hipMalloc(&g_ao.exch, ex1 + ex2));
-    g_ao.exch_bytes = ex1 + ex2;
-  }
-  if (plan.G > 1) {   // (no tag or vote of an earlier launch may pass for one of this launch)
-    TO_HIP(hipMemsetAsync(g_ao.votes, 0, 512, s));
-    TO_HIP(hipMemsetAsync(g_ao.exch, 0, ex1 + ex2, s));
-  }
+  g_ao.reserve(ex1 + ex2);
+  g_ao.status_reset();
+  if (plan.G > 1) g_ao.zero(s);
   if (dtype == TO_F64) launch_ae_online_t<double>(plan, L, dims, kinds, W, b, X, idx_dev, n, rate, losses, ex1, s);
   else launch_ae_online_t<float>(plan, L, dims, kinds, W, b, X, idx_dev, n, rate, losses, ex1, s);
   TO_HIP(hipGetLastError());
   count_launch();
 }
 
-int ae_online_status() { return g_ao.status ? *g_ao.status : 0; }
+int ae_online_status() { return g_ao.status<int>() ? *g_ao.status<int>() : 0; }
 
 }  // namespace to

@@ -2084,7 +2084,7 @@ to_status to_graph_online_sgd(to_graph g, to_tensor x_buf, to_tensor y_buf, to_t
   int G = 0, rpw = 0;
   size_t lds = 0;
   if (!online_sgd_plan(f.dtype, f.L, f.dims, &G, &rpw, &lds)) return TO_OK;
-  if (!online_sgd_placement_ok(S())) return TO_OK;   // (the captured step is replayed per sample instead)
+  if (!xcd_placement_ok(S())) return TO_OK;   // (the captured step is replayed per sample instead)
   for (int64_t k = 0; k < n_idx; ++k)
     TO_CHECK(!idx_or_null || (idx_or_null[k] >= 0 && idx_or_null[k] < X->batch), TO_ERR_SHAPE, "sample index out of range");
   TO_CHECK(idx_or_null || n_idx <= X->batch, TO_ERR_SHAPE, "more samples than rows");

@@ -445,9 +445,15 @@ void launch_rank1_general(int dtype, int n, const void* const* dz, const void* c
 bool online_sgd_plan(int dtype, int L, const int64_t* dims, int* G_out, int* rpw_out, size_t* lds_out);
 void launch_online_sgd(int dtype, int L, const int64_t* dims, void* const* W, void* const* b, const void* X, const void* Y,
                        const long long* idx_dev, int64_t n, double rate, int head, int act_kind, hipStream_t s);
-bool online_sgd_placement_ok(hipStream_t s);   // probed once: do workgroups b, b + 8, ... of a grid share an XCD?
-int online_sgd_status();
-void online_sgd_reset_status();
+// xcd_exchange.hip: what the four persistent kernels with a single-XCD exchange (xcd_exchange.hpp: online_sgd.hip,
+// induce_seq.hip, ae_online.hip, rnn_wide.hip) report, read after the stream has been synchronised
+bool xcd_placement_ok(hipStream_t s);      // probed once: do workgroups b, b + 8, ... of a grid share an XCD (one L2)?
+int online_sgd_status();                   // 0, or the sample (1-based) at which a wait timed out
+void online_sgd_reset_status();            // before a call's launches: the status back to "no report"
+int64_t induce_seq_status(int64_t* row);   // 0, or the iteration (1-based) at which a wait timed out (reset at launch)
+int ae_online_status();                    // 0, or the sample (1-based) at which a wait timed out (reset at launch)
+void rnn_wide_begin();                     // before a call's first launch: the status back to "no report"
+int64_t rnn_wide_status(int64_t* id);      // 0, or the step (1-based) at which a wait timed out
 void launch_loss_grad_rows(int dtype, const void* z, const void* y, void* dz, void* loss, int64_t B, int64_t n,
                            int kind, hipStream_t s);
 // infer_head.hip: the output head of to_fflayer_stack_infer.  out (optional) = act(A W^T + b) with act softmax or logistic,
@@ -484,7 +490,7 @@ void launch_rnn_seq(int dtype, bool reverse, const RnnSeqPlan& p, const void* M,
                     int64_t H, int act_kind, hipStream_t s);
 // rnn_wide.hip: the same recurrence for the widths above rnn_seq_plan's LDS range, W' split by columns over the G workgroups
 // of a group, up to 8 groups of R rows side by side (B <= 128), one launch for all T steps.  A plan may only be launched
-// where online_sgd_placement_ok() holds (a performance precondition: a group behind one XCD's L2).
+// where xcd_placement_ok() holds (a performance precondition: a group behind one XCD's L2).
 struct RnnWidePlan {
   bool exists = false;
   int G = 0, C = 0;       // workgroups of a group; columns of M a workgroup owns (the last one H - (G - 1) C)
@@ -495,11 +501,9 @@ struct RnnWidePlan {
   size_t lds_bytes = 0;
 };
 bool rnn_wide_plan(int dtype, int64_t H, int64_t B, int min_groups, RnnWidePlan* p);
-void rnn_wide_begin();   // before a call's first launch: the status back to "no report"
 // id: what the status names beside the step if a wait of this launch runs out (the driver's layer and direction)
 void launch_rnn_wide(int dtype, bool reverse, const RnnWidePlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T,
                      int64_t H, int act_kind, int64_t id, hipStream_t s);
-int64_t rnn_wide_status(int64_t* id);   // 0, or the step (1-based) at which a wait timed out
 // rnn_ragged.hip: sequences of different lengths (to_rnn_stack_*_ragged).  The row schedule: the sequences sorted by length,
 // descending and stable; at step t the active ones are the first cnt[t] sorted positions and their packed rows are
 // off[t] .. off[t] + cnt[t] - 1, N = off[Tmax] rows in all.  The tables live on the device, O(B + T) int32.
@@ -629,7 +633,7 @@ bool rnn_minibatch_plan(int dtype, int L, const int64_t* widths, const int* stat
 void launch_rnn_minibatch(int dtype, const RnnMinibatchPlan& p, const RnnMinibatchOperands& o, hipStream_t s);
 // induce_seq.hip: every iteration of `induceNetwork` on every row in one launch (to_fflayer_stack_induce, route B).
 // X [B][i0] contiguous: x_0 on entry, x_iters on exit; gx [B][i0] (optional) the last iteration's gradient; losses
-// [B][iters] (optional).  A plan with G > 1 may only be launched where online_sgd_placement_ok() holds.
+// [B][iters] (optional).  A plan with G > 1 may only be launched where xcd_placement_ok() holds.
 constexpr int INDUCE_MAX_LAYERS = 6;
 struct InduceSeqPlan {
   int G = 1;          // workgroups that share a row (layer 1 split by columns)
@@ -641,10 +645,9 @@ bool induce_seq_plan(int dtype, int L, const int64_t* dims, int64_t B, int64_t i
 void launch_induce_seq(int dtype, const InduceSeqPlan& plan, int L, const int64_t* dims, const void* const* W,
                        const void* const* b, void* X, const void* Y, int64_t y_sm, void* gx, void* losses, int64_t B,
                        int64_t iters, double rate, int head, int act_kind, hipStream_t s);
-int64_t induce_seq_status(int64_t* row);   // 0, or the iteration (1-based) at which a wait timed out
 // ae_online.hip: per-sample `trainEncoder` over the rows idx of X in one launch (to_autoencoder_stack_online_sgd, route B).
 // kinds[l]: ACT_KIND_* behind layer l (0-based), kinds[L - 1] the head's activation (a squaredError head).  A plan with
-// G > 1 may only be launched where online_sgd_placement_ok() holds.
+// G > 1 may only be launched where xcd_placement_ok() holds.
 constexpr int AE_ONLINE_MAX_LAYERS = 6;
 struct AeOnlinePlan {
   int G = 1;          // workgroups
@@ -657,7 +660,6 @@ bool ae_online_plan(int dtype, int L, const int64_t* dims, int min_groups, AeOnl
 void launch_ae_online(int dtype, const AeOnlinePlan& plan, int L, const int64_t* dims, const int* kinds, void* const* W,
                       void* const* b, const void* X, const long long* idx_dev, int64_t n, double rate, void* losses,
                       hipStream_t s);
-int ae_online_status();   // 0, or the sample (1-based) at which a wait timed out
 
 }  // namespace to
 

@@ -80,6 +80,22 @@ __device__ __forceinline__ S wave_max(S v) {   // max's NaN rule at every level
   return v;
 }
 
+// a 64-lane dot product of w[0 .. K) with x[0 .. K), both in LDS: four independent chains a lane (the LDS reads of one pass
+// are all in flight together), then the butterfly
+template <class S>
+__device__ __forceinline__ S wave_dot(const S* __restrict__ w, const S* __restrict__ x, int K, int lane) {
+  S acc0 = S(0.), acc1 = S(0.), acc2 = S(0.), acc3 = S(0.);
+  int k = lane;
+  for (; k + 192 < K; k += 256) {
+    acc0 = fma(w[k], x[k], acc0);
+    acc1 = fma(w[k + 64], x[k + 64], acc1);
+    acc2 = fma(w[k + 128], x[k + 128], acc2);
+    acc3 = fma(w[k + 192], x[k + 192], acc3);
+  }
+  for (; k < K; k += 64) acc0 = fma(w[k], x[k], acc0);
+  return wave_sum((acc0 + acc1) + (acc2 + acc3));
+}
+
 }  // namespace dm
 
 // A barrier whose hand-over is in LDS only: the workgroup's LDS accesses are done, its global stores need not be (they are

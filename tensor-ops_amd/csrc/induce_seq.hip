@@ -16,12 +16,9 @@
 //     as there are rows (up to 256), each walking its share of the rows.  With G > 1 one group -- the workgroups with
 //     blockIdx.x % 8 == 0 of a grid of 8 G, the others leave at once -- takes the rows one after the other.
 //
-// The exchange is online_sgd.hip's: {tag, 32 bits of the value} in one 64-bit word, L1-bypassing agent-scope stores and
-// loads, two buffers by step parity, and it carries that kernel's precondition -- it is only right between workgroups that
-// share one XCD's L2, so a plan with G > 1 may only be launched where online_sgd_placement_ok() holds (the caller asks).
-// Every wait is bounded by a wall_clock64 watchdog; a workgroup that gives up reports (iteration, row) in a host-visible
-// word and leaves.  The kernel writes only scratch: the host copies to the caller's tensors after a launch that reported
-// success.  Residency of the G workgroups comes from the grid size alone (8 G <= 256 workgroups, one per CU).
+// The exchange, its one-L2 precondition (a plan with G > 1 may only be launched where xcd_placement_ok() holds: the caller
+// asks) and its watchdog are xcd_exchange.hpp's.  A workgroup that gives up reports (iteration, row) in a host-visible word
+// and leaves.  The kernel writes only scratch: the host copies to the caller's tensors after a launch that reported success.
 //
 // Range: 1..6 layers, a head of at most 64 outputs, every width <= 65535, everything a workgroup holds within 160 KiB of
 // LDS (the plan picks the smallest G that fits): fp32 784-300-100-10 at G = 32 (about 161.6 KB), 784-32-10 at G = 1;
@@ -32,6 +29,7 @@
 // (tools/induce_scan.py, profiles/r08_induce_scan.txt).
 #include "common.hpp"
 #include "devmath.hpp"
+#include "xcd_exchange.hpp"
 
 namespace to {
 
@@ -67,7 +65,7 @@ __device__ __forceinline__ void matvec(const S* __restrict__ W, int ld, int O, i
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (K >= 64) {
     for (int j = wave; j < O; j += IN_NWV) {
-      const S* __restrict__ w = W + (long)j * ld;
+      const S* __restrict__ w = W + (long)j * ld;   // (dm::wave_dot written out: as a call, this file's assembly moves)
       S a0 = S(0.), a1 = S(0.), a2 = S(0.), a3 = S(0.);
       int k = lane;
       for (; k + 192 < K; k += 256) {
@@ -193,14 +191,9 @@ __global__ __launch_bounds__(IN_THREADS) void induce_seq_kernel(InduceArgs<S> a)
         for (int j = tid; j < o1; j += IN_THREADS) {
           S z = act[1][j];
           if (a.G > 1) {
-            unsigned wd[WORDS];
-            __builtin_memcpy(wd, &z, sizeof(S));
-#pragma unroll
-            for (int u = 0; u < WORDS; ++u)
-              __hip_atomic_store(ex + ((long)g * o1 + j) * WORDS + u, ((unsigned long long)tag << 32) | wd[u], __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
+            xe::publish(ex + ((long)g * o1 + j) * WORDS, z, tag);
             // every partial (this workgroup's too) comes back from L2, eight workgroups' words in flight at a time, and is
-            // added in workgroup order
+            // added in workgroup order (the poll is written out: on a shared primitive, in each shape tried, this file's assembly moves -- xcd_exchange.hpp)
             z = S(0.);
             for (int q0 = 0; q0 < a.G && ok; q0 += 8) {
               const int nq = a.G - q0 < 8 ? a.G - q0 : 8;
@@ -306,13 +299,7 @@ __global__ __launch_bounds__(IN_THREADS) void induce_seq_kernel(InduceArgs<S> a)
   }
 }
 
-struct InduceState {
-  void* exch = nullptr;
-  size_t exch_bytes = 0;
-  long long* status = nullptr;
-  long long* status_dev = nullptr;
-};
-InduceState g_in;
+xe::XcdExchange g_in(false);
 
 template <class S, int ACT>
 void launch_induce_t(const InduceSeqPlan& plan, int L, const int64_t* dims, const void* const* W, const void* const* b, void* X,
@@ -336,16 +323,10 @@ void launch_induce_t(const InduceSeqPlan& plan, int L, const int64_t* dims, cons
   a.head = head;
   a.G = plan.G;
   a.cw = plan.cw;
-  a.exch = static_cast<unsigned long long*>(g_in.exch);
-  a.status = g_in.status_dev;
-  static const double timeout_s = [] { const char* e = getenv("TOPS_ONLINE_TIMEOUT_S"); return e ? atof(e) : 2.0; }();
-  a.timeout = (long long)(timeout_s * 100e6);
-  static bool attr = false;
-  if (!attr) {
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(induce_seq_kernel<S, ACT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               160 * 1024));
-    attr = true;
-  }
+  a.exch = g_in.exch();
+  a.status = g_in.status_dev<long long>();
+  a.timeout = xe::watchdog_ticks();
+  xe::allow_full_lds<induce_seq_kernel<S, ACT>>();
   launch_k(induce_seq_kernel<S, ACT>, dim3((unsigned)plan.grid), dim3(IN_THREADS), plan.lds, s, a);
 }
 
@@ -384,21 +365,10 @@ void launch_induce_seq(int dtype, const InduceSeqPlan& plan, int L, const int64_
   TO_CHECK(act_kind == ACT_KIND_LOGISTIC || act_kind == ACT_KIND_TANH, TO_ERR_ARG, "induce kernel: unknown hidden activation");
   TO_CHECK(plan.G >= 1 && plan.G <= 32 && plan.grid >= 1 && plan.grid <= 256 && plan.lds <= 160 * 1024, TO_ERR_STATE,
            "induce kernel: not a plan of induce_seq_plan");
-  if (!g_in.status) {
-    TO_HIP(hipHostMalloc(&g_in.status, 2 * sizeof(long long), hipHostMallocMapped));
-    TO_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&g_in.status_dev), g_in.status, 0));
-  }
-  g_in.status[0] = g_in.status[1] = 0;
+  g_in.status_reset();
   if (plan.G > 1) {
-    const size_t need = (size_t)2 * plan.G * dims[1] * (dtype == TO_F64 ? 2 : 1) * 8;
-    if (g_in.exch_bytes < need) {
-      if (g_in.exch) (void)hipFree(g_in.exch);
-      g_in.exch = nullptr;
-      g_in.exch_bytes = 0;
-      TO_HIP(hipMalloc(&g_in.exch, need));
-      g_in.exch_bytes = need;
-    }
-    TO_HIP(hipMemsetAsync(g_in.exch, 0, need, s));  // (no tag of an earlier launch may pass for one of this launch)
+    g_in.reserve((size_t)2 * plan.G * dims[1] * (dtype == TO_F64 ? 2 : 1) * 8);
+    g_in.zero(s);
   }
   if (act_kind == ACT_KIND_TANH) {
     if (dtype == TO_F64) launch_induce_t<double, ACT_KIND_TANH>(plan, L, dims, W, b, X, Y, y_sm, gx, losses, B, iters, rate, head, s);
@@ -413,9 +383,10 @@ void launch_induce_seq(int dtype, const InduceSeqPlan& plan, int L, const int64_
 
 // after the stream has been synchronised: 0, or the iteration (1-based) at which a workgroup gave up waiting (and its row)
 int64_t induce_seq_status(int64_t* row) {
-  if (!g_in.status || g_in.status[0] == 0) return 0;
-  if (row) *row = g_in.status[1];
-  return g_in.status[0];
+  const long long* st = g_in.status<long long>();
+  if (!st || st[0] == 0) return 0;
+  if (row) *row = st[1];
+  return st[0];
 }
 
 }  // namespace to

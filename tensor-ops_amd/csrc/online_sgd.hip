@@ -18,14 +18,13 @@
 //     dz1 = (W2[:, R_g]^T dz2) act'(h1) needs only what the workgroup owns; then every parameter is updated in LDS
 //     (`p - r * g`, FeedForward.hs:145-147).  The next sample's input is fetched while this one is computed.
 //
-// All participating workgroups sit on one XCD (the grid is 8 G workgroups, workgroup b runs on XCD b % 8, those with
-// b % 8 != 0 leave at once): the exchange goes through that XCD's L2 with L1-bypassing loads and stores and a counter
-// in the same L2 -- no device-scope cache write-back or invalidate, which is what made a cross-XCD grid barrier cost
-// 180 us in round 2.  A workgroup that waits longer than the watchdog gives up and reports.
+// The exchange of the partials, its watchdog and the all-or-nothing commit at the end are xcd_exchange.hpp's (the grid is
+// 8 G workgroups, those with b % 8 != 0 leave at once); the partials land in LDS.
 #include <cstring>
 
 #include "common.hpp"
 #include "devmath.hpp"
+#include "xcd_exchange.hpp"
 
 namespace to {
 
@@ -33,9 +32,6 @@ namespace {
 
 constexpr int ON_MAX_LAYERS = 6;
 constexpr int ON_THREADS = 512;
-// the commit's decision word: counter[ON_DECISION] (behind the 32 vote slots), decided once by compare-and-swap
-constexpr int ON_DECISION = 32;
-constexpr unsigned long long ON_COMMIT = 1ull, ON_ABORT = 2ull;
 constexpr int ON_XREGS = 4;  // input elements prefetched per thread: i0 <= 2048
 
 template <class S>
@@ -52,7 +48,7 @@ struct OnlineArgs {
   int head;          // 1: softmax >>> crossEntropy, 2: logistic >>> squaredError
   int G, rpw;        // workgroups, rows of layer 1 per workgroup
   unsigned long long* exch;  // [2][G][o2][words of S]: {tag, 32 bits of the value} (zero at launch)
-  unsigned* counter;         // 256 bytes, zero at launch: the commit verdicts, one 64-bit word per workgroup
+  unsigned long long* votes; // zero at launch: the commit's votes and its decision word
   int* status;       // host-visible: nonzero = a barrier timed out at that sample + 1
   long long timeout; // wall_clock64 ticks
   long long* dbg;    // development (TOPS_ONLINE_STAMPS): phase time stamps of workgroup 0 at sample 64
@@ -76,10 +72,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 __device__ __forceinline__ double wave_sum(double v) { return dm::wave_sum(v); }
-
-// L1-bypassing accesses to the exchange buffer (all readers and writers share one L2)
-template <class S> __device__ __forceinline__ void st_l2(S* p, S v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <class S> __device__ __forceinline__ S ld_l2(const S* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // (S = float, or double: the reference's own element type, `HMat Double`, BLAS/HMat.hs:35)
 template <class S, int ACT>
@@ -205,11 +197,6 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
     __syncthreads();
     ON_STAMP();
     // ---- partial z2 = W2[:, R_g] h1[R_g] -> exchange ----------------------------------------------------------------------
-    // Every 32-bit word of a partial travels with the sample's tag in ONE 64-bit store; a reader polls the words it
-    // needs until their tags say "this sample".  Data and "it is there" are the same memory transaction: one L2 round
-    // trip per sample (store -> L2 -> load), where a counter barrier needs three (store ack, arrive, poll, then load).
-    // A slot is written again two samples later, which its writer can only reach after every workgroup has written the
-    // sample in between -- i.e. after all of them have read this one.
     constexpr int WORDS = sizeof(S) / 4;
     const unsigned tag = (unsigned)(t + 1);
     unsigned long long* ex = a.exch + (long)(t & 1) * a.G * o2 * WORDS;
@@ -217,14 +204,10 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
       const S* w = W2s + j * a.rpw;
       S acc = S(0.);
       for (int r = 0; r < nr; ++r) acc = dm::fma(w[r], h1s[r], acc);
-      unsigned wd[WORDS];
-      __builtin_memcpy(wd, &acc, sizeof(S));
-#pragma unroll
-      for (int u = 0; u < WORDS; ++u)
-        __hip_atomic_store(ex + ((long)g * o2 + j) * WORDS + u, ((unsigned long long)tag << 32) | wd[u], __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+      xe::publish(ex + ((long)g * o2 + j) * WORDS, acc, tag);
     }
     // ---- z2 = b2 + sum_g partial_g ; layer 2's activation -----------------------------------------------------------------
+    // (the poll is written out: on a shared primitive, in each shape tried, this file's assembly moves -- xcd_exchange.hpp)
     {
       const int total = a.G * o2 * WORDS;
       unsigned* pw = reinterpret_cast<unsigned*>(part);
@@ -281,13 +264,8 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
     }
     __syncthreads();
     ON_STAMP();
-    if (red[7] != S(0.)) {        // a peer never showed up (uniform): this workgroup votes "failed", decides ABORT for
-      if (tid == 0) {             // everybody (unless COMMIT was decided -- impossible: that needs this vote to be "ok") and leaves
-        unsigned long long* cmv = reinterpret_cast<unsigned long long*>(a.counter);
-        __hip_atomic_store(cmv + g, 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned long long expect = 0ull;
-        __hip_atomic_compare_exchange_strong(cmv + ON_DECISION, &expect, ON_ABORT, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+    if (red[7] != S(0.)) {        // a peer never showed up (uniform)
+      xe::give_up(a.votes, g);
       return;
     }
     for (int j = tid; j < o2; j += ON_THREADS) {
@@ -434,18 +412,10 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
     __syncthreads();
     ON_STAMP();
   }
-  // ---- commit: ONE decision for all workgroups -------------------------------------------------------------------------
-  // A workgroup that got through its stream votes "ok" and waits for the other votes.  Votes alone cannot make the write-back
-  // all-or-nothing (round 3's form): a peer that saw every "ok" in time would write its slice while one whose poll timed out
-  // a moment earlier would not -- parameters half updated.  So the outcome is a single word that is decided
-  // exactly once, by compare-and-swap: whoever has seen all G "ok" votes proposes COMMIT, whoever has seen a "failed" vote or
-  // run out of time proposes ABORT, the first proposal wins and EVERYBODY obeys the word, not their own view.  A workgroup
-  // that timed out but reads COMMIT writes its slice after all: COMMIT can only have been proposed by a peer that saw all G
-  // votes "ok", this one's included, so every slice is complete.  Same L1-bypassing accesses, same watchdog.
+  // ---- commit: ONE decision for all workgroups ----------------------------------------------------------------------------
+  // (written out here and in ae_online.hip: as a function, in each form tried, this file's register allocation moves -- xcd_exchange.hpp)
   {
-    unsigned long long* cm = reinterpret_cast<unsigned long long*>(a.counter);
-    // (the decision travels to the other threads in red[6]: the kernel's dynamic LDS may be all 160 KiB, a static
-    //  __shared__ word on top of it would make the launch fail)
+    unsigned long long* cm = a.votes;
     if (tid == 0) __hip_atomic_store(cm + g, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (tid < a.G) {
       const long long c0 = wall_clock64();
@@ -453,7 +423,7 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
       while (true) {
         v = __hip_atomic_load(cm + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (v != 0) break;
-        if (__hip_atomic_load(cm + ON_DECISION, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;   // (decided meanwhile)
+        if (__hip_atomic_load(cm + xe::DECISION, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;   // (decided meanwhile)
         if (wall_clock64() - c0 > a.timeout) break;
         __builtin_amdgcn_s_sleep(1);
       }
@@ -462,11 +432,11 @@ __global__ __launch_bounds__(ON_THREADS) void online_sgd_kernel(OnlineArgs<S> a)
     __syncthreads();
     if (tid == 0) {
       unsigned long long expect = 0ull;
-      const unsigned long long mine = red[7] != S(0.) ? ON_ABORT : ON_COMMIT;
-      const bool won = __hip_atomic_compare_exchange_strong(cm + ON_DECISION, &expect, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned long long mine = red[7] != S(0.) ? xe::ABORT : xe::COMMIT;
+      const bool won = __hip_atomic_compare_exchange_strong(cm + xe::DECISION, &expect, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const unsigned long long decision = won ? mine : expect;   // (expect holds what was there)
-      red[6] = decision == ON_COMMIT ? S(1.) : S(0.);
-      if (decision == ON_ABORT && *a.status == 0) *a.status = (int)(a.n + 1);   // (no sample to name: reported as "sample n")
+      red[6] = decision == xe::COMMIT ? S(1.) : S(0.);
+      if (decision == xe::ABORT && *a.status == 0) *a.status = (int)(a.n + 1);   // (no sample to name: reported as "sample n")
     }
     __syncthreads();
     if (red[6] != S(1.)) return;
@@ -492,14 +462,7 @@ static long long*& dbg_ptr() {
   static long long* p = nullptr;
   return p;
 }
-struct OnlineState {
-  void* exch = nullptr;
-  size_t exch_bytes = 0;
-  unsigned* counter = nullptr;
-  int* status = nullptr;
-  int* status_dev = nullptr;
-};
-OnlineState g_on;
+xe::XcdExchange g_on(true);
 
 }  // namespace
 
@@ -548,11 +511,10 @@ static void launch_online_t(int L, const int64_t* dims, void* const* W, void* co
   a.head = head;
   a.G = G;
   a.rpw = rpw;
-  a.exch = static_cast<unsigned long long*>(g_on.exch);
-  a.counter = g_on.counter;
-  a.status = g_on.status_dev;
-  static const double timeout_s = [] { const char* e = getenv("TOPS_ONLINE_TIMEOUT_S"); return e ? atof(e) : 2.0; }();
-  a.timeout = (long long)(timeout_s * 100e6);
+  a.exch = g_on.exch();
+  a.votes = g_on.votes();
+  a.status = g_on.status_dev<int>();
+  a.timeout = xe::watchdog_ticks();
   static long long* dbg = [] {
     long long* p = nullptr;
     if (ab_getenv("TOPS_ONLINE_STAMPS") && hipHostMalloc(&p, 64 * sizeof(long long), hipHostMallocMapped) == hipSuccess) {
@@ -576,43 +538,8 @@ static void launch_online_t(int L, const int64_t* dims, void* const* W, void* co
     }
     dbg_ptr() = dbg;
   }
-  static bool attr = false;
-  if (!attr) {
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(online_sgd_kernel<S, ACT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               160 * 1024));
-    attr = true;
-  }
+  xe::allow_full_lds<online_sgd_kernel<S, ACT>>();
   launch_k(online_sgd_kernel<S, ACT>, dim3(8 * G), dim3(ON_THREADS), lds, s, a);
-}
-
-// The exchange needs every participating workgroup on ONE XCD (one L2).  The kernel gets that from the dispatcher's
-// round-robin -- workgroup b of a grid lands on XCD b % 8 in SPX mode with every CU enabled -- which is observed
-// behaviour, not a documented contract: probed once per process with a grid of the same shape (every participating
-// workgroup reports the XCC it runs on) before the kernel is ever trusted with parameters.  Other partition modes or a CU
-// mask fail the probe and the caller keeps the generic per-sample path.
-__global__ void online_xcc_probe_kernel(int* out) {
-  if (blockIdx.x % 8 != 0 || threadIdx.x != 0) return;
-  unsigned xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  out[blockIdx.x / 8] = (int)(xcc & 0xf);
-}
-
-bool online_sgd_placement_ok(hipStream_t s) {
-  static int verdict = -1;
-  if (verdict >= 0) return verdict == 1;
-  int* host = nullptr;
-  if (hipHostMalloc(&host, 32 * sizeof(int), hipHostMallocMapped) != hipSuccess) return false;
-  int* dev = nullptr;
-  bool ok = hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), host, 0) == hipSuccess;
-  for (int rep = 0; ok && rep < 4; ++rep) {   // (four launches: a placement that only sometimes holds is no placement)
-    for (int i = 0; i < 32; ++i) host[i] = -1;
-    launch_k(online_xcc_probe_kernel, dim3(8 * 32), dim3(64), 0, s, dev);
-    ok = hipStreamSynchronize(s) == hipSuccess;
-    for (int i = 0; ok && i < 32; ++i) ok = host[i] >= 0 && host[i] == host[0];
-  }
-  (void)hipHostFree(host);
-  verdict = ok ? 1 : 0;
-  return ok;
 }
 
 void launch_online_sgd(int dtype, int L, const int64_t* dims, void* const* W, void* const* b, const void* X, const void* Y,
@@ -622,23 +549,11 @@ void launch_online_sgd(int dtype, int L, const int64_t* dims, void* const* W, vo
   int G = 0, rpw = 0;
   size_t lds = 0;
   TO_CHECK(online_sgd_plan(dtype, L, dims, &G, &rpw, &lds), TO_ERR_UNSUPPORTED, "online SGD kernel: stack outside its range");
-  TO_CHECK(online_sgd_placement_ok(s), TO_ERR_UNSUPPORTED,
+  TO_CHECK(xcd_placement_ok(s), TO_ERR_UNSUPPORTED,
            "online SGD kernel: workgroups b, b+8, b+16 ... of a grid do not share an XCD on this device (partition mode / CU mask)");
   const size_t need = (size_t)2 * G * dims[2] * (dtype == TO_F64 ? 2 : 1) * 8;
-  if (!g_on.counter) {
-    TO_HIP(hipMalloc(&g_on.counter, 512));   // 32 vote slots + the decision word
-    TO_HIP(hipHostMalloc(&g_on.status, sizeof(int), hipHostMallocMapped));
-    TO_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&g_on.status_dev), g_on.status, 0));
-    *g_on.status = 0;
-  }
-  if (g_on.exch_bytes < need) {
-    if (g_on.exch) (void)hipFree(g_on.exch);
-    g_on.exch = nullptr;
-    TO_HIP(hipMalloc(&g_on.exch, need));
-    g_on.exch_bytes = need;
-  }
-  TO_HIP(hipMemsetAsync(g_on.counter, 0, 512, s));
-  TO_HIP(hipMemsetAsync(g_on.exch, 0, need, s));  // (no tag of an earlier launch may pass for one of this launch)
+  g_on.reserve(need);
+  g_on.zero(s);
   if (act_kind == ACT_KIND_TANH) {
     if (dtype == TO_F64) launch_online_t<double, ACT_KIND_TANH>(L, dims, W, b, X, Y, idx_dev, n, rate, head, G, rpw, lds, s);
     else launch_online_t<float, ACT_KIND_TANH>(L, dims, W, b, X, Y, idx_dev, n, rate, head, G, rpw, lds, s);
@@ -650,9 +565,9 @@ void launch_online_sgd(int dtype, int L, const int64_t* dims, void* const* W, vo
   count_launch();
 }
 
-int online_sgd_status() { return g_on.status ? *g_on.status : 0; }
+int online_sgd_status() { return g_on.status<int>() ? *g_on.status<int>() : 0; }
 void online_sgd_reset_status() {
-  if (g_on.status) *g_on.status = 0;
+  if (g_on.status<int>()) g_on.status_reset();   // (before the first launch there is nothing to reset, and nothing is allocated)
 }
 
 }  // namespace to

@@ -10,7 +10,7 @@
 //     blocks with Cp = 16 (mod 32), so that the four k rows of an operand fall into the two halves of the banks) and keeps
 //     it there for all T steps, beside two buffers [R][H | 1] for v_{t-1} / v_t and the cross-wave reduction scratch;
 //   * up to 8 groups run side by side (B <= 8 R): group q is the workgroups with blockIdx & 7 == q of a grid of 8 G -- the
-//     placement online_sgd_placement_ok() vouches for, every group behind one XCD's L2.  Workgroups of unused groups return
+//     placement xcd_placement_ok() vouches for, every group behind one XCD's L2.  Workgroups of unused groups return
 //     at once.  Placement is a performance precondition; correctness rests on agent-scope atomics only;
 //   * the inner product has two forms, by R, each with a summation order fixed by the plan (dtype, H, B, min_groups), so a
 //     result depends neither on the workgroups' timing nor on the other rows:
@@ -23,18 +23,10 @@
 //     place, act(z) to St (forward), acc act'(St) + G to Z (reverse); the new value goes into the workgroup's own next-state
 //     buffer directly and, as tagged words, to the mates.
 //
-// The exchange.  One value's 32-bit word(s) travel with tag = step + 1 in one L1-bypassing 64-bit store each, into
-// exch[parity of the step][group][row][column] (zero at launch: no tag of an earlier launch passes for one of this one).
-// Every workgroup gathers the other slabs' words into its next-state buffer, polling a word until its tag matches, eight
-// words a thread in flight.  A slot is rewritten two steps later, and that is safe: its writer reaches the store of step
-// s + 2 only after it has read EVERY mate's publication of step s + 1 (it needs all of v_{s+1}), and each mate made that
-// publication only after it had read all of step s -- this slot included.  So nobody can still be waiting to read the word
-// that is overwritten.  The last step publishes nothing.  G = 1 never arises: those widths are rnn_seq_kernel's.
-//
-// The watchdog.  Every poll is bounded by the wall_clock64 timeout of online_sgd.hip / induce_seq.hip / ae_online.hip
-// (TOPS_ONLINE_TIMEOUT_S, 2 s).  A wait that runs out stores {step + 1, the launch's id + 1} into a host-visible status
-// pair (the first report of a call is kept) and the workgroup leaves its step loop; its mates then wait for a publication
-// that never comes and run out likewise, so the launch always ends.  Z and St are then unspecified.
+// The exchange is xcd_exchange.hpp's, into exch[parity of the step][group][row][column]: every workgroup gathers the other
+// slabs' words into its next-state buffer, eight words a thread in flight.  The last step publishes nothing.  G = 1 never
+// arises: those widths are rnn_seq_kernel's.  A wait that runs out stores {step + 1, the launch's id + 1} into a host-visible
+// status pair (the first report of a call is kept) and the workgroup leaves its step loop; Z and St are then unspecified.
 //
 // Which (dtype, H) have a plan (rnn_wide_plan below): above rnn_seq_plan's LDS range, H <= RNN_SEQ_MAX_H, B <= 128, and some
 // G <= 32 whose slab fits 160 KiB beside the rows' buffers.  fp32: every H in 202 .. 1024 for B <= 8 (R = 1); at H = 1024
@@ -46,6 +38,7 @@
 
 #include "common.hpp"
 #include "devmath.hpp"
+#include "xcd_exchange.hpp"
 
 namespace to {
 
@@ -204,7 +197,7 @@ __global__ __launch_bounds__(RW_THREADS) void rnn_wide_kernel(RnnWideArgs<S> a) 
         }
         if (more) {
           vn[r * Hs + j] = o;
-          unsigned wd[WORDS];
+          unsigned wd[WORDS];   // (xe::publish written out: as a call, in each form tried, this file's address arithmetic moves)
           __builtin_memcpy(wd, &o, sizeof(S));
 #pragma unroll
           for (int w = 0; w < WORDS; ++w)
@@ -214,6 +207,7 @@ __global__ __launch_bounds__(RW_THREADS) void rnn_wide_kernel(RnnWideArgs<S> a) 
       }
     }
     // ---- the mates' slabs of v_t into the next-state buffer ------------------------------------------------------------
+    // (the poll is written out: on a shared primitive, in each shape tried, this file's assembly moves -- xcd_exchange.hpp)
     bool ok = true;
     if (more) {
       constexpr int NV = RW_FLIGHT / WORDS;   // values in flight
@@ -286,32 +280,13 @@ __global__ __launch_bounds__(RW_THREADS) void rnn_wide_kernel(RnnWideArgs<S> a) 
   }
 }
 
-struct RnnWideState {
-  void* exch = nullptr;
-  size_t exch_bytes = 0;
-  long long* status = nullptr;
-  long long* status_dev = nullptr;
-};
-RnnWideState g_rw;
-
-void rw_status_alloc() {
-  if (g_rw.status) return;
-  TO_HIP(hipHostMalloc(&g_rw.status, 2 * sizeof(long long), hipHostMallocMapped));
-  TO_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&g_rw.status_dev), g_rw.status, 0));
-  g_rw.status[0] = g_rw.status[1] = 0;
-}
+xe::XcdExchange g_rw(false);
 
 template <class S, bool REV, bool MFMA, int ACT>
 void rw_go(const RnnWidePlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T, int64_t H, int64_t id, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    TO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rnn_wide_kernel<S, REV, MFMA, ACT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)RW_LDS_MAX));
-    attr = true;
-  }
-  static const double timeout_s = [] { const char* e = getenv("TOPS_ONLINE_TIMEOUT_S"); return e ? atof(e) : 2.0; }();
+  xe::allow_full_lds<rnn_wide_kernel<S, REV, MFMA, ACT>>();
   RnnWideArgs<S> a{(const S*)M, (S*)Z, (S*)St, (long)B, (long)T, (int)H, p.G, p.C, p.Cp, p.R, p.groups, p.nsl, p.klen,
-                   static_cast<unsigned long long*>(g_rw.exch), g_rw.status_dev, (long long)(timeout_s * 100e6), (long long)id};
+                   g_rw.exch(), g_rw.status_dev<long long>(), xe::watchdog_ticks(), (long long)id};
   launch_k(rnn_wide_kernel<S, REV, MFMA, ACT>, dim3((unsigned)(8 * p.G)), dim3(RW_THREADS), p.lds_bytes, s, a);
 }
 
@@ -370,16 +345,14 @@ bool rnn_wide_plan(int dtype, int64_t H, int64_t B, int min_groups, RnnWidePlan*
 }
 
 // the status pair back to "no report": the driver calls it before a call's first launch (nothing is in flight then)
-void rnn_wide_begin() {
-  rw_status_alloc();
-  g_rw.status[0] = g_rw.status[1] = 0;
-}
+void rnn_wide_begin() { g_rw.status_reset(); }
 
 // after the stream has been synchronised: 0, or the step (1-based) at which a workgroup gave up waiting, and that launch's id
 int64_t rnn_wide_status(int64_t* id) {
-  if (!g_rw.status || g_rw.status[0] == 0) return 0;
-  if (id) *id = g_rw.status[1] - 1;
-  return g_rw.status[0];
+  const long long* st = g_rw.status<long long>();
+  if (!st || st[0] == 0) return 0;
+  if (id) *id = st[1] - 1;
+  return st[0];
 }
 
 void launch_rnn_wide(int dtype, bool reverse, const RnnWidePlan& p, const void* M, void* Z, void* St, int64_t B, int64_t T,
@@ -390,16 +363,10 @@ void launch_rnn_wide(int dtype, bool reverse, const RnnWidePlan& p, const void* 
                (int64_t)p.groups * p.R >= B && (int64_t)p.G * p.C >= H && (int64_t)(p.G - 1) * p.C < H && p.Cp >= p.C &&
                p.lds_bytes <= (size_t)RW_LDS_MAX && T < 4000000000LL,
            TO_ERR_STATE, "rnn_wide: not a plan of rnn_wide_plan for this shape");
-  rw_status_alloc();
   const size_t need = (size_t)2 * p.groups * p.R * H * (dtype == TO_F64 ? 2 : 1) * 8;
-  if (g_rw.exch_bytes < need) {
-    if (g_rw.exch) (void)hipFree(g_rw.exch);
-    g_rw.exch = nullptr;
-    g_rw.exch_bytes = 0;
-    TO_HIP(hipMalloc(&g_rw.exch, need));
-    g_rw.exch_bytes = need;
-  }
-  launch_fill(TO_F32, g_rw.exch, (int64_t)(need / 4), 0.0, s);   // (no tag of an earlier launch may pass for one of this launch)
+  g_rw.reserve(need);
+  // (a kernel launch, not XcdExchange::zero(): the launch count and the call trace of the wide route name it)
+  launch_fill(TO_F32, g_rw.exch(), (int64_t)(need / 4), 0.0, s);
   if (dtype == TO_F64) rw_go_type<double>(reverse, act_kind, p, M, Z, St, B, T, H, id, s);
   else rw_go_type<float>(reverse, act_kind, p, M, Z, St, B, T, H, id, s);
   TO_HIP(hipGetLastError());

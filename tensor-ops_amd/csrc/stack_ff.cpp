@@ -672,7 +672,7 @@ static void ae_online_impl(int n_enc, int n_dec, const to_tensor* w, const to_te
                  (g_ae_online_persistent == 2 ||
                   (dt == TO_F32 && L == 2 && acts[0] == ACT_KIND_LOGISTIC && head == 2 && plan.G <= AE_ONLINE_AUTO_MAX_G &&
                    widest <= AE_ONLINE_AUTO_MAX_WIDTH && n_idx >= AE_ONLINE_AUTO_MIN_SAMPLES)) &&
-                 (plan.G == 1 || online_sgd_placement_ok(S()));   // (the exchanges' precondition: one XCD's L2)
+                 (plan.G == 1 || xcd_placement_ok(S()));   // (the exchanges' precondition: one XCD's L2)
   }
   if (!persistent) {
     // (its own validation repeats the checks above and adds the refusals of a one-row step, all before its first launch)
@@ -758,7 +758,7 @@ to_status to_autoencoder_online_plan_query(int dtype, int n_layers, const int64_
            "autoencoder_online_plan_query: 2..6 layers (dims holds n_layers + 1 widths)");
   AeOnlinePlan plan;
   const bool ok = ae_online_plan(dtype, n_layers, dims, g_ae_online_min_groups, &plan);
-  const bool placed = online_sgd_placement_ok(S());
+  const bool placed = xcd_placement_ok(S());
   *exists = ok ? 1 : 0;
   *G = ok ? plan.G : 0;
   *slice_first = ok ? plan.rpw : 0;
@@ -1010,7 +1010,7 @@ static void induce_impl(int n_layers, const to_tensor* w, const to_tensor* b, in
     for (int l = 0; l < n_layers; ++l) dims[l + 1] = w[l]->dims[0];
     persistent = induce_seq_plan(dt, n_layers, dims, B, iters, &plan) &&
                  (g_induce_persistent == 2 || induce_auto_persistent(plan, B)) &&
-                 (plan.G == 1 || online_sgd_placement_ok(S()));   // (the exchange's precondition: one XCD's L2)
+                 (plan.G == 1 || xcd_placement_ok(S()));   // (the exchange's precondition: one XCD's L2)
   }
 
   if (persistent) {
@@ -1158,7 +1158,7 @@ to_status to_persist_plan_query(int kernel, int dtype, int n_layers, const int64
       last = (int)(dims[0] - (int64_t)(g - 1) * sl);
     }
   }
-  const bool placed = online_sgd_placement_ok(S());
+  const bool placed = xcd_placement_ok(S());
   *exists = ok ? 1 : 0;
   *G = ok ? g : 0;
   *slice = ok ? sl : 0;

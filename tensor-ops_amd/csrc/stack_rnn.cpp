@@ -61,7 +61,7 @@ static bool rnn_wide_auto(int dt, int64_t H, int64_t B, int64_t T, int kind) {
 static bool rnn_wide_for(int dt, int64_t H, int64_t B, int64_t T, int kind, RnnWidePlan* plan) {
   if (g_rnn_wide == 0 || !rnn_wide_plan(dt, H, B, g_rnn_wide_min_groups, plan)) return false;
   if (g_rnn_wide == 1 && !rnn_wide_auto(dt, H, B, T, kind)) return false;
-  return online_sgd_placement_ok(S());   // (the exchange's performance precondition: a group behind one XCD's L2)
+  return xcd_placement_ok(S());   // (the exchange's performance precondition: a group behind one XCD's L2)
 }
 
 enum class RnnMode { Run, Grad, Sgd };

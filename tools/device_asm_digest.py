@@ -2,7 +2,7 @@
 
 A refactor that only moves device helpers between headers leaves every file's generated code as it was; two runs -- one on a
 copy of the parent tree, one on the branch -- show that, or name the file where it is not so.  Each file is compiled with
-tensor-ops_amd/build.py's FLAGS (plus any -D given here: the development defines are -DTOPS_AB_KNOBS
+tensor-ops_amd/build.py's FLAGS and the file's extra_flags (plus any -D given here: the development defines are -DTOPS_AB_KNOBS
 -DTOPS_GEMM_AB_VARIANTS) and `--cuda-device-only -S` into a temporary directory.  Lines naming `__hip_cuid_<hash>` are dropped
 before hashing: that id is hashed from the source text and path, so it differs between any two trees.  Nothing else is
 filtered and nothing is searched for; no GPU is needed.
@@ -27,7 +27,7 @@ def _build_mod():
 
 def digest(b, src, defines, tmp, keep):
     out = os.path.join(tmp, src + ".s")
-    cmd = [b._hipcc()] + b.FLAGS + defines + ["--cuda-device-only", "-S", "-o", out, "-x", "hip", os.path.join(b.CSRC, src)]
+    cmd = [b._hipcc()] + b.FLAGS + b.extra_flags(src) + defines + ["--cuda-device-only", "-S", "-o", out, "-x", "hip", os.path.join(b.CSRC, src)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed: " + " ".join(cmd) + "\n" + r.stderr[-3000:])

@@ -303,7 +303,8 @@ enum {
   TO_GEMM_FAMILY_MFMA = 8,
   TO_GEMM_FAMILY_F64 = 9,
   TO_GEMM_FAMILY_NAIVE = 10,
-  TO_GEMM_FAMILY_KW16_64 = 11 /* the fp64 tile menu; asked just ahead of KW64, numbered last so that 0 .. 10 keep their meaning */
+  TO_GEMM_FAMILY_KW16_64 = 11, /* the fp64 tile menu; asked just ahead of KW64, numbered last so that 0 .. 10 keep their meaning */
+  TO_GEMM_FAMILY_FEWRHS = 12   /* few right-hand sides; asked just behind GEMV, numbered last so that 0 .. 11 keep their meaning */
 };
 enum { TO_GEMM_EPI_BIAS = 1, TO_GEMM_EPI_ACT = 2, TO_GEMM_EPI_DACT = 4, TO_GEMM_EPI_BETA = 8, TO_GEMM_EPI_ROWSUM = 16 };
 /* The problem: C[m, n] = A[m, k] . B[k, n] of `dtype`, `batch` >= 1 of them (reduce_batch: summed into one C), each operand
@@ -327,6 +328,14 @@ to_status to_gemm_route_query(int dtype, int64_t m, int64_t n, int64_t k, int64_
  * scanned shape, the cost rule's elsewhere; 0 .. 4 that menu entry.  Process-wide, for contractions planned from now
  * on; *previous_mode_or_null gets the mode it replaces.  Anything else: TO_ERR_ARG, nothing changed. */
 to_status to_set_gemm_f64_menu(int mode, int tile, int* previous_mode_or_null);
+/* Few right-hand sides (csrc/gemm_fewrhs.hip): a product with 2 .. 32 columns (or rows) beside a long other extent, the big
+ * operand streamed once from HBM into 16x16x4 MFMA blocks, the narrow one resident in LDS; fp32 and fp64, batch 1, the
+ * streamed operand contiguous along either of its axes, alpha / beta Cin / bias / logistic / tanh carried.  mode 0: off (DEFAULT:
+ * every contraction takes exactly the route it took before the kernel existed); 1: automatic -- only the shape classes
+ * tools/gemm_fewrhs_scan.py measured ahead (profiles/gemm_fewrhs_scan.txt; everything unscanned keeps its route); 2: wherever the
+ * kernel can run.  splits: -1 the launcher's rule, 1 .. 256 forced (clamped to K).  Process-wide, for contractions planned
+ * from now on; *previous_mode_or_null gets the mode it replaces.  Anything else: TO_ERR_ARG, nothing changed. */
+to_status to_set_gemm_few_rhs(int mode, int splits, int* previous_mode_or_null);
 /* stream capture of everything enqueued between begin/end into a HIP graph */
 to_status to_graph_begin(void);
 to_status to_graph_end(to_graph* out);

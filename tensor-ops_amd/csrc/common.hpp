@@ -302,6 +302,10 @@ bool gemm_kw64_menu_applicable(const GemmProblem& p);  // gemm_kwave_f64.hip: fp
 bool gemm_kw64_menu_everywhere(const GemmProblem& p);  // ... and the switch is at mode 2 (wherever the kernel can)
 void launch_gemm_kw64_menu(const GemmProblem& p, hipStream_t s);
 bool gemm_kw64_menu_set(int mode, int tile, int* previous_mode);  // false: mode or tile out of range, nothing changed
+bool gemm_fewrhs_applicable(const GemmProblem& p);  // gemm_fewrhs.hip: 2 .. 32 columns (or rows) beside a long extent, streamed at the HBM bound (to_set_gemm_few_rhs; off by default)
+bool gemm_fewrhs_everywhere(const GemmProblem& p);  // ... and the switch is at mode 2 (wherever the kernel can)
+void launch_gemm_fewrhs(const GemmProblem& p, hipStream_t s);
+bool gemm_fewrhs_set(int mode, int splits, int* previous_mode);  // false: mode or splits out of range, nothing changed
 bool gemm_skinnyk64_applicable(const GemmProblem& p);  // gemm_skinnyk_f64.hip: config 5's shape class in Double
 void launch_gemm_skinnyk64(const GemmProblem& p, hipStream_t s);
 struct GemmEpilogue {

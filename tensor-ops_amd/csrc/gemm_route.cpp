@@ -46,6 +46,8 @@ void gemm_plan(const GemmProblem& p, GemmLeaves& out, bool sub) {
            "collapsed GEMM extent exceeds 2^31-1");
   // one extent is 1: matVec / vecMat / an outer product beyond the small-GEMM kernel's range -- HBM-bound streaming kernels
   if (gemv_form(p, true)) return out.push(GEMM_GEMV, p, sub);
+  // 2 .. 32 columns (or rows) beside a long extent: the same stream with a handful of right-hand sides on MFMA blocks
+  if (gemm_fewrhs_applicable(p)) return out.push(GEMM_FEWRHS, p, sub);   // (to_set_gemm_few_rhs; never with the switch off)
   {   // (development builds, TOPS_T32_FIRST=1: the four-wave 32x32-tile kernel ahead of the wave-split one, for A/B runs)
     static const int t32_first = [] { const char* e = ab_getenv("TOPS_T32_FIRST"); return e ? atoi(e) : 0; }();
     if (t32_first && gemm_t32_applicable(p)) return out.push(GEMM_T32, p, sub);
@@ -127,6 +129,7 @@ void run_gemm(const GemmProblem& p) {
     const GemmProblem& q = *plan.problem[i];
     switch (plan.family[i]) {
       case GEMM_GEMV: launch_gemv(q, S()); break;
+      case GEMM_FEWRHS: launch_gemm_fewrhs(q, S()); break;
       case GEMM_T32: launch_gemm_t32(q, S()); break;
       case GEMM_SKINNYK: launch_gemm_skinnyk(q, S()); break;
       case GEMM_SKINNYK64: launch_gemm_skinnyk64(q, S()); break;
@@ -173,6 +176,7 @@ bool gemm_small_route(const GemmProblem& p) {
   //  scan timed the plain product against the plan's route, not a fused launch against the small-GEMM kernel, so 640^3 and
   //  768^3 -- under 200 tiles of 64x64 -- keep the small-first launch for a fused epilogue)
   if (gemm_kw64_menu_everywhere(p)) return false;
+  if (gemm_fewrhs_everywhere(p)) return false;   // (to_set_gemm_few_rhs at mode 2, likewise: through the plan, epilogue carried)
   // (a few tiles under a very long K -- a weight gradient over a data set, 300 x 60000 x 784: one workgroup a tile here whatever K
   //  is, 400 us; 291 split over workgroups in gemm_kwave.hip, which carries alpha / beta C / bias / activation but no row sums)
   if (p.K >= 8192 && !p.rowsum && !p.loss_rows && !p.tail_out && gemm_kw_long_k(p)) return false;
@@ -185,6 +189,7 @@ bool gemm_small_route(const GemmProblem& p) {
 bool gemm_epilogue_ok(const GemmProblem& p) {
   if (p.M == 0 || p.N == 0 || p.K == 0 || p.batch == 0) return false;
   if (gemm_small_route(p) || gemm_skinnyk_applicable(p) || gemm_skinnyk64_applicable(p) || gemv_form(p)) return true;
+  if (gemm_fewrhs_applicable(p)) return true;   // (never with the switch off; asks for no dact, so the kernel carries what is left)
   if (p.dtype == TO_F64) return gemm_kw64_menu_applicable(p) || gemm_kw64_applicable(p);
   const GemmFamily f = gemm_tiled_family(p);
   return f == GEMM_SMALL || f == GEMM_MFMA;
@@ -229,6 +234,14 @@ extern "C" to_status to_set_gemm_f64_menu(int mode, int tile, int* previous_mode
   API_BEGIN
   TO_CHECK(gemm_kw64_menu_set(mode, tile, previous_mode_or_null), TO_ERR_ARG,
            "to_set_gemm_f64_menu: mode 0 (off), 1 (automatic) or 2 (wherever the kernel can); tile -1 (the cost rule) or a menu index 0 .. 4");
+  API_END
+}
+
+extern "C" to_status to_set_gemm_few_rhs(int mode, int splits, int* previous_mode_or_null) {
+  using namespace to;
+  API_BEGIN
+  TO_CHECK(gemm_fewrhs_set(mode, splits, previous_mode_or_null), TO_ERR_ARG,
+           "to_set_gemm_few_rhs: mode 0 (off), 1 (automatic) or 2 (wherever the kernel can); splits -1 (the launcher's rule) or 1 .. 256");
   API_END
 }
 

@@ -22,6 +22,7 @@ enum GemmFamily {
   GEMM_F64 = TO_GEMM_FAMILY_F64,              // gemm_f64.hip
   GEMM_NAIVE = TO_GEMM_FAMILY_NAIVE,          // reduce_layout.hip: one thread per output element
   GEMM_KW16_64 = TO_GEMM_FAMILY_KW16_64,      // gemm_kwave_f64.hip, the fp64 tile menu (asked just ahead of GEMM_KW64; numbered last: the recorded table keeps 0 .. 10)
+  GEMM_FEWRHS = TO_GEMM_FAMILY_FEWRHS,        // gemm_fewrhs.hip (asked just behind GEMM_GEMV, to_set_gemm_few_rhs only; numbered last likewise)
 };
 
 // A plan's leaves -- one launch each: a kernel family and the (sub-)problem it gets -- in launch order, held inline (no heap

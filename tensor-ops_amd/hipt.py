@@ -754,6 +754,14 @@ class HipT:
         return prev.value
 
     @staticmethod
+    def set_gemm_few_rhs(mode, splits=-1):
+        """to_set_gemm_few_rhs: the few-right-hand-sides streaming kernel 0 off (default), 1 automatic, 2 wherever the kernel can;
+        splits -1 (the launcher's rule) or 1 .. 256 parts of K; returns the previous mode"""
+        prev = C.c_int()
+        check(lib().to_set_gemm_few_rhs(int(mode), int(splits), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
     def rnn_wide_groups(min_groups):
         """to_set_rnn_wide_groups: 0 the plan's own G, else at least this many workgroups a group; returns the previous
         setting"""

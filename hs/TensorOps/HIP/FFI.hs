@@ -117,6 +117,7 @@ foreign import ccall safe   "to_graph_release" c_graph_release :: Ptr ToGraph ->
 foreign import ccall safe   "to_graph_online_sgd" c_graph_online_sgd :: Ptr ToGraph -> Ptr ToTensor -> Ptr ToTensor -> Ptr ToTensor -> Ptr ToTensor -> Int64 -> Ptr Int64 -> Ptr CInt -> IO CInt
 -- minibatch BPTT over a resident set of sequences: blocks until every update is done
 foreign import ccall safe   "to_rnn_stack_minibatch_sgd" c_rnn_stack_minibatch_sgd :: CInt -> Ptr CInt -> Ptr (Ptr ToTensor) -> Ptr (Ptr ToTensor) -> Ptr (Ptr ToTensor) -> Ptr (Ptr ToTensor) -> CInt -> CInt -> CInt -> Ptr ToTensor -> Ptr ToTensor -> Int64 -> Ptr Int64 -> Int64 -> CDouble -> CDouble -> Ptr ToTensor -> IO CInt
+foreign import ccall safe   "to_rnn_stack_minibatch_sgd_ragged" c_rnn_stack_minibatch_sgd_ragged :: CInt -> Ptr CInt -> Ptr (Ptr ToTensor) -> Ptr (Ptr ToTensor) -> Ptr (Ptr ToTensor) -> Ptr (Ptr ToTensor) -> CInt -> CInt -> CInt -> Ptr ToTensor -> Ptr ToTensor -> Ptr Int64 -> Int64 -> Ptr Int64 -> Int64 -> CDouble -> CDouble -> Ptr ToTensor -> IO CInt
 foreign import ccall unsafe "to_batch_select"  c_batch_select' :: Ptr ToTensor -> Int64 -> Ptr (Ptr ToTensor) -> IO CInt
 -- ---- in-place program-level calls ---------------------------------------------------------------------------
 foreign import ccall safe   "to_sgd_step_inplace" c_sgd_step_inplace :: Ptr ToTensor -> Ptr ToTensor -> CDouble -> IO CInt

@@ -823,7 +823,8 @@ to_status to_rnn_online_stats(int64_t* persistent_runs, int64_t* per_sequence_ru
  * plus the two chain blocks [Mp][Hp + 4] within 160 KiB of LDS -- fp32 70 -> 130 (stateful) -> 3 at M = 16 fits (144 KiB), in
  * fp64 it does not and takes route A.  Every sum's order is fixed by (dtype, widths, M): a repeated call gives the same bits,
  * and a call cut at a minibatch boundary into two gives the bits of the one call.  The two routes agree to rounding, not bit
- * for bit.  Not built: a tape in LDS, ragged lengths, M > 64, a form over several workgroups.
+ * for bit.  Not built: a tape in LDS, M > 64, a form over several workgroups (sequences of their own lengths:
+ * to_rnn_stack_minibatch_sgd_ragged below).
  * to_set_rnn_minibatch_persistent: 0 route A; 2 route B wherever its plan exists; 1 automatic (default): route B exactly on
  * the rows tools/rnn_minibatch_scan.py scanned where it was ahead of BOTH route A and the caller's loop by more than the row's
  * run-to-run spread (profiles/rnn_minibatch_scan.txt; fp32, 256 sequences, logistic states and hidden layers, microseconds
@@ -890,6 +891,64 @@ to_status to_rnn_stack_online_sgd_ragged(int n_layers, const int* state_act, con
                                          const int64_t* idx_or_null, double rate_state, double rate_params,
                                          to_tensor losses_or_null);
 to_status to_rnn_online_ragged_stats(int64_t* persistent_runs, int64_t* per_sequence_runs);
+
+/* Minibatch training for sequences of DIFFERENT lengths: to_rnn_stack_minibatch_sgd's argument list with `lens` directly
+ * after the data tensors, as every ragged sibling has it (lens: host int64[N] by SEQUENCE; null is TO_ERR_ARG; any of the N
+ * entries outside 1 .. T, those of sequences idx never names included, is TO_ERR_SHAPE).
+ * For k = 0 .. ceil(n_idx / M) - 1, in order: the sequences idx[k M .. min((k + 1) M, n_idx)) (idx null: those positions in
+ * place) form one batch, and the call applies one to_rnn_stack_sgd_ragged update to it with the gathered lengths: objective
+ * sum_b sum_{t < lens[b]} loss, s -= rate_state gs, every parameter -= rate_params g, in place, from what update k - 1 left.
+ *   Padding (t >= lens[q]) of X and Y is never read: NaN or Inf there reaches no bit of any parameter, state or loss.
+ *   losses_or_null  contiguous [n_idx; T]: losses[j][t] for t < lens[idx[j]] is the loss under the parameters j's update
+ *                   started from; exactly +0.0 at padding.
+ * Everything else is to_rnn_stack_minibatch_sgd's, with its statuses: minibatch < 1 or n_idx < 1 TO_ERR_ARG, indices out of
+ * range TO_ERR_SHAPE, the overlap rule for losses, the stack, activation and (out_act, loss) pair checks for both batch
+ * sizes that occur, never TO_ERR_UNSUPPORTED for a valid stack; refused during graph capture (TO_ERR_STATE); every refusal
+ * is decided before the first launch and leaves everything untouched; blocks before returning; keeps no handle.
+ * Routes, chosen by to_set_rnn_minibatch_persistent (0 / 1 / 2; there is no switch of its own).  Per minibatch (A):
+ * to_batch_gather's kernel on this minibatch's run of idx (idx null: to_batch_slice's views), the lengths gathered on the
+ * host, to_rnn_stack_sgd_ragged's own launches, losses through the slice [k M ..] -- BIT FOR BIT the caller's loop of
+ * to_batch_gather + to_rnn_stack_sgd_ragged; fp32 and fp64, any widths, any T.  Persistent (B,
+ * csrc/rnn_minibatch_ragged.hip, rnn_minibatch_ragged_kernel): rnn_minibatch_kernel's launch -- one workgroup, eight waves,
+ * the same MFMA blocks, the stack in LDS, the tape in a pool buffer, one LDS-only barrier a recurrence step, no spin -- on a
+ * row layout of its own.  The host sorts each minibatch's members by length (descending, stable by position in idx), so the
+ * sequences running at step t are the slots q < act(t); step t owns P(t) = act(t) rounded up to 16 PACKED rows from
+ * off(t) = sum_{t' < t} P(t') on, an update R_k = off(Tk) rows (Tk: the minibatch's longest) instead of T Mp.  The rows
+ * act(t) <= q < P(t) carry zero input and a zero dz, are never read from X / Y and never written to losses.  The row-parallel
+ * phases (input projections, hidden_act, head, cotangents, the update's row reductions) run over exactly R_k rows; the forward
+ * recurrence deals (P(t) / 16) x (Hp / 16) blocks a step and ends at Tk; the backward recurrence takes the carry from step
+ * t + 1 only on the P(t + 1) rows that have one -- the blocks above start their chain at the head's cotangent, and write it
+ * to the LDS block the step below reads, so no row there is a leftover of a later step.  gs sums the P(0) rows of step 0.
+ * The schedule (per slot the sequence, its position in idx, its length; per minibatch Tk, off and the step of every row
+ * block) is int32 tables uploaded once and released after the call's synchronise; losses is zeroed once up front.  Range:
+ * rnn_minibatch_plan's (1..8 layers, M <= 64, 160 KiB), the tape sized for the call's largest R_k; no length decides the
+ * range.  Every sum's order is fixed by (dtype, widths, M, the minibatch's lengths): a repeated call gives the same bits, a
+ * call cut at a minibatch boundary gives the bits of the one call.  With every length T and n_idx a multiple of M the layout
+ * is the dense kernel's (P(t) = Mp, the same row order) and route B gives the dense entry's route-B bits; with a short tail it
+ * agrees to rounding.  On route A all lengths T give the dense entry's route-A bits.  The dense entry, its launches, its bits
+ * and to_rnn_minibatch_stats are untouched by these calls; to_rnn_minibatch_ragged_stats counts them by route.
+ * Mode 1 (automatic, the default) follows the dense entry's rule: route B exactly on the rows
+ * tools/rnn_minibatch_ragged_scan.py scanned where it was ahead of BOTH route A and the caller's loop by more than the row's
+ * run-to-run spread (profiles/rnn_minibatch_ragged_scan.txt; fp32, 256 sequences padded to T, lengths uniform in 1 .. T,
+ * logistic states and hidden layers, microseconds an update caller / A / B, spreads 1 - 5 %):
+ *   T = 8, M = 4 and 16:  5 -> 7 -> 5: 131 / 103 / 45 and 135 / 109 / 58;  64 -> 32 -> 10: 137 / 110 / 63 and 146 / 121 / 79;
+ *                         64 -> 64 -> 10: 146 / 119 / 87 and 157 / 132 / 106
+ *                                       -> fp32, logistic, T = 8, 4 <= M <= 16, no width (the input's included) above 64
+ * Where it did NOT win, and automatic is ROUTE A: M = 64 at T = 8 (133 against 135 for 5 -> 7 -> 5, within the 8 % spread; 185
+ * against 124 at H = 32, 258 against 142 at H = 64); EVERY ROW AT T = 64, 1.8x to 6x behind (305 against 172 for 5 -> 7 -> 5 at
+ * M = 4; 2095 against 344 for 64 -> 64 -> 10 at M = 64), although it packs only 64 - 95 % of the dense layout's rows: packing
+ * removes rows, not what makes a row slow -- the serial recurrences and the update's row-long reductions read the tape from
+ * global memory, with eight waves.  For reference, the dense entry on the padded set (ANOTHER objective: it trains on the
+ * padding) takes 49 / 60 / 137 us for 5 -> 7 -> 5 at T = 8 and 154 / 215 / 541 at T = 64: on the winning rows the ragged call
+ * is 3 - 10 % below it.  The rule does not look at the lengths.  NOT MEASURED, and route A under mode 1: fp64, tanh, any other
+ * T, M below 4.  Not scanned either: other length distributions (with every length T the layout is the dense kernel's).
+ * Not built: a tape in LDS, M > 64, a form over several workgroups, the wide route. */
+to_status to_rnn_stack_minibatch_sgd_ragged(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                                            const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss,
+                                            to_tensor X, to_tensor Y, const int64_t* lens, int64_t n_idx,
+                                            const int64_t* idx_or_null, int64_t minibatch, double rate_state,
+                                            double rate_params, to_tensor losses_or_null);
+to_status to_rnn_minibatch_ragged_stats(int64_t* persistent_runs, int64_t* per_minibatch_runs);
 
 /* `induceNetwork` (FeedForward.hs:150-164) of the same ffLayer stacks, iterated: gradient descent on the INPUT with the
  * parameters fixed (app/MNIST.hs:357-365 runs 5000 such steps in a row), for every row of the hidden batch, in ONE call:

@@ -10,7 +10,7 @@ HOST_LIB = os.path.join(HERE, "libtensorops_host.so")
 HOST_DIR = os.path.join(HERE, "host")
 DOTS_BIN = os.path.join(HERE, "tensor-ops-dots-hip")
 MNIST_BIN = os.path.join(HERE, "tensor-ops-mnist-hip")
-SOURCES = ["runtime.cpp", "expr.cpp", "expr_jit.cpp", "rowprog.cpp", "api.cpp", "gemm_route.cpp", "stack_util.cpp", "stack_ff.cpp", "stack_rnn.cpp", "lazy.cpp", "lazy_plan.cpp", "lazy_cache.cpp", "lazy_exec.cpp", "comm.cpp", "gemm_f32_mfma.hip", "gemm_small.hip", "gemm_t32.hip", "gemm_skinnyk.hip", "gemm_kwave.hip", "gemm_kw16.hip", "gemm_kwave_f64.hip", "gemm_skinnyk_f64.hip", "gemm_f64.hip", "ewise.hip", "reduce_layout.hip", "gemv.hip", "gemm_fewrhs.hip", "fused_fflayer.hip", "p2p.hip", "xcd_exchange.hip", "online_sgd.hip", "infer_head.hip", "rnn_seq.hip", "rnn_wide.hip", "rnn_ragged.hip", "rnn_generate.hip", "rnn_online.hip", "rnn_minibatch.hip", "induce_seq.hip", "minibatch_stage.hip", "recon_head.hip", "ae_online.hip"]
+SOURCES = ["runtime.cpp", "expr.cpp", "expr_jit.cpp", "rowprog.cpp", "api.cpp", "gemm_route.cpp", "stack_util.cpp", "stack_ff.cpp", "stack_rnn.cpp", "lazy.cpp", "lazy_plan.cpp", "lazy_cache.cpp", "lazy_exec.cpp", "comm.cpp", "gemm_f32_mfma.hip", "gemm_small.hip", "gemm_t32.hip", "gemm_skinnyk.hip", "gemm_kwave.hip", "gemm_kw16.hip", "gemm_kwave_f64.hip", "gemm_skinnyk_f64.hip", "gemm_f64.hip", "ewise.hip", "reduce_layout.hip", "gemv.hip", "gemm_fewrhs.hip", "fused_fflayer.hip", "p2p.hip", "xcd_exchange.hip", "online_sgd.hip", "infer_head.hip", "rnn_seq.hip", "rnn_wide.hip", "rnn_ragged.hip", "rnn_generate.hip", "rnn_online.hip", "rnn_minibatch.hip", "rnn_minibatch_ragged.hip", "induce_seq.hip", "minibatch_stage.hip", "recon_head.hip", "ae_online.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function"]
 # Kernarg preload: the dispatcher puts a kernel's LEADING scalar and pointer parameters (up to 14 dwords beside the kernarg
@@ -36,7 +36,7 @@ if AB:   # development build: the A/B knobs and the extra tile-shape variants ar
 # results from some forms of them have been reported for gfx950 parts, nothing here reproduces that, and no older file is
 # touched (their code is measured and pinned as it is).  For ae_online.hip the flag changes six fused multiply-adds of the W1
 # update and nothing else; its timings (profiles/autoencoder_online_scan.txt) were taken with it.
-NO_PACKED_FP32 = ["ae_online.hip", "rnn_wide.hip", "rnn_minibatch.hip"]
+NO_PACKED_FP32 = ["ae_online.hip", "rnn_wide.hip", "rnn_minibatch.hip", "rnn_minibatch_ragged.hip"]
 # The kernel files whose hand-written waits, barriers and wait states tools/asm_inflight_check.py proves on the GENERATED
 # code (tests/test_pinned_asm.py): their device assembly -- the very text the object was assembled from -- is kept
 # beside the object (build/<stem>-hip-amdgcn-amd-amdhsa-gfx950.s; -save-temps, everything else it leaves is deleted).

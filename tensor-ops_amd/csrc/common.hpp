@@ -635,6 +635,15 @@ struct RnnMinibatchOperands {
 // padded parameters, states and chain blocks exceed GEN_LDS_MAX; T decides only the size of the tape
 bool rnn_minibatch_plan(int dtype, int L, const int64_t* widths, const int* stateful, int64_t M, int64_t T, RnnMinibatchPlan* p);
 void launch_rnn_minibatch(int dtype, const RnnMinibatchPlan& p, const RnnMinibatchOperands& o, hipStream_t s);
+// rnn_minibatch_ragged.hip: the same for sequences of their own lengths (to_rnn_stack_minibatch_sgd_ragged, route B), the rows of
+// a step packed.  The plan is rnn_minibatch_plan's; its tape holds max_rows * plan.rec elements instead.  The schedule (host):
+// idx null or [n_idx], lens by sequence, all checked by the caller; tab is what the kernel reads, max_rows the most rows any
+// minibatch packs.  False: a table index beyond int32.
+bool rnn_minibatch_ragged_schedule(int64_t M, int64_t n_idx, const int64_t* idx, const int64_t* lens, std::vector<int>* tab,
+                                   int64_t* max_rows);
+// tab: the schedule on the device; o.idx is not read
+void launch_rnn_minibatch_ragged(int dtype, const RnnMinibatchPlan& p, const RnnMinibatchOperands& o, const int* tab,
+                                 hipStream_t s);
 // induce_seq.hip: every iteration of `induceNetwork` on every row in one launch (to_fflayer_stack_induce, route B).
 // X [B][i0] contiguous: x_0 on entry, x_iters on exit; gx [B][i0] (optional) the last iteration's gradient; losses
 // [B][iters] (optional).  A plan with G > 1 may only be launched where xcd_placement_ok() holds.

@@ -36,78 +36,15 @@
 //   Determinism       : every sum's order is fixed by (dtype, widths, M) alone: a repeated call gives the same bits, and so
 //                       does a call cut at a minibatch boundary into two.
 // MB_THREADS = 512, eight waves: fp32 70 -> 130 -> 3 at M = 16 has nine output blocks a step.  Not measured against 256.
+// The workgroup's shape, the MFMA block, the kernel's arguments and the update's row reduction are rnn_minibatch_dev.hpp's,
+// shared with rnn_minibatch_ragged.hip.
 #include <algorithm>
-#include <type_traits>
 
-#include "common.hpp"
-#include "devmath.hpp"
+#include "rnn_minibatch_dev.hpp"
 
 namespace to {
 
 namespace {
-
-constexpr int MB_THREADS = 512, MB_NW = MB_THREADS / 64;
-
-typedef float mb_f32x4 __attribute__((ext_vector_type(4)));
-typedef double mb_f64x4 __attribute__((ext_vector_type(4)));
-template <class S> using mb_v4 = typename std::conditional<sizeof(S) == 8, mb_f64x4, mb_f32x4>::type;
-// A lane l = A[i = l & 15][k = l >> 4], B lane l = B[k = l >> 4][j = l & 15]
-__device__ __forceinline__ mb_f32x4 mb_mfma(float a, float b, mb_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ mb_f64x4 mb_mfma(double a, double b, mb_f64x4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-// D register r of lane l (g = l >> 4) is row 4 g + r (fp32) or g + 4 r (fp64), column l & 15
-template <class S> __device__ __forceinline__ int mb_row(int g, int r) { return sizeof(S) == 8 ? g + 4 * r : 4 * g + r; }
-
-template <class S>
-struct RnnMinibatchArgs {
-  S* W[RNN_GEN_MAX_LAYERS];    // [n_l][n_{l-1}]
-  S* WS[RNN_GEN_MAX_LAYERS];   // [n_l][n_l] (stateful)
-  S* b[RNN_GEN_MAX_LAYERS];
-  S* s[RNN_GEN_MAX_LAYERS];    // [n_l] (stateful): the learned initial state
-  int n[RNN_GEN_MAX_LAYERS + 1];
-  int sk[RNN_GEN_MAX_LAYERS];  // state activation, -1: stateless
-  // LDS offsets (elements): W k-major [up4(m)][ld], W' k-major [up4(n)][ld], b and s [up4(n)]
-  int w_off[RNN_GEN_MAX_LAYERS], ws_off[RNN_GEN_MAX_LAYERS], b_off[RNN_GEN_MAX_LAYERS], s_off[RNN_GEN_MAX_LAYERS],
-      ld[RNN_GEN_MAX_LAYERS];
-  // offsets within one row's tape record: the layer's input row, its state S_t, its z_t / dz_t
-  int t_in[RNN_GEN_MAX_LAYERS], t_s[RNN_GEN_MAX_LAYERS], t_dz[RNN_GEN_MAX_LAYERS];
-  const S* X;             // [N][T][n_0]
-  const S* Y;             // [N][T][n_L]
-  S* losses;              // [n_idx][T] or null
-  const long long* idx;   // [n_idx] or null: sequences 0 .. n_idx-1
-  S* tape;                // [T * Mp][rec]
-  long n_idx, M, T, rec;
-  int L, Mp, chain_off, hs, hidden_kind, softmax;
-  S rate_state, rate_params;
-};
-
-// One k-major matrix's update: M[k][j] -= rate * sum over ascending r of src[r][k] dz[r][j], k < m, j < n.  The 16 x 16
-// output blocks are dealt to the waves; the reduction runs over the rows, four an MFMA (lane group g takes row r + g).
-template <class S>
-__device__ __forceinline__ void mb_update(const S* tape, long rec, long R, int osrc, int odz, int m, int n, int ld, S* Mk, S rate,
-                                          int wave, int c, int g) {
-  const int m4 = (m + 3) & ~3, n4 = (n + 3) & ~3, ncb = (n + 15) >> 4, nkb = (m + 15) >> 4;
-  for (int it = wave; it < nkb * ncb; it += MB_NW) {
-    const int kb = it / ncb, cb = it - kb * ncb, ka = kb * 16 + c, jb = cb * 16 + c;
-    const bool ina = ka < m4, inb = jb < n4;
-    mb_v4<S> acc = {S(0), S(0), S(0), S(0)};
-    const S* p = tape + g * rec;
-    for (long r = 0; r < R; r += 16, p += 16 * rec) {   // R is a multiple of 16: four MFMAs' loads in flight together
-      S av[4], bv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        av[u] = ina ? p[u * 4 * rec + osrc + ka] : S(0);
-        bv[u] = inb ? p[u * 4 * rec + odz + jb] : S(0);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc = mb_mfma(av[u], bv[u], acc);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int k = kb * 16 + mb_row<S>(g, r);
-      if (k < m && jb < n) Mk[k * ld + jb] -= rate * acc[r];
-    }
-  }
-}
 
 template <class S>
 __global__ __launch_bounds__(MB_THREADS) void rnn_minibatch_kernel(RnnMinibatchArgs<S> a) {
@@ -467,20 +404,7 @@ void go_minibatch(const RnnMinibatchPlan& p, const RnnMinibatchOperands& o, hipS
                                (int)GEN_LDS_MAX));
     attr = true;
   }
-  RnnMinibatchArgs<S> a{};
-  for (int l = 0; l < o.L; ++l) {
-    a.W[l] = (S*)o.W[l]; a.WS[l] = (S*)o.WS[l]; a.b[l] = (S*)o.b[l]; a.s[l] = (S*)o.s[l];
-    a.sk[l] = o.state_kind[l];
-    a.w_off[l] = p.w_off[l]; a.ws_off[l] = p.ws_off[l]; a.b_off[l] = p.b_off[l]; a.s_off[l] = p.s_off[l]; a.ld[l] = p.ld[l];
-    a.t_in[l] = p.t_in[l]; a.t_s[l] = p.t_s[l]; a.t_dz[l] = p.t_dz[l];
-  }
-  for (int l = 0; l <= o.L; ++l) a.n[l] = (int)o.widths[l];
-  a.X = (const S*)o.X; a.Y = (const S*)o.Y; a.losses = (S*)o.losses; a.idx = o.idx; a.tape = (S*)o.tape;
-  a.n_idx = (long)o.n_idx; a.M = (long)o.M; a.T = (long)o.T; a.rec = (long)p.rec;
-  a.L = o.L; a.Mp = p.Mp; a.chain_off = p.chain_off; a.hs = p.hs; a.hidden_kind = o.hidden_kind;
-  a.softmax = o.softmax ? 1 : 0;
-  a.rate_state = (S)o.rate_state; a.rate_params = (S)o.rate_params;
-  launch_k(rnn_minibatch_kernel<S>, dim3(1), dim3(MB_THREADS), p.lds, s, a);
+  launch_k(rnn_minibatch_kernel<S>, dim3(1), dim3(MB_THREADS), p.lds, s, mb_args<S>(p, o));
 }
 
 }  // namespace

@@ -1064,15 +1064,34 @@ static bool rnn_minibatch_auto(int dt, int L, const int64_t* widths, bool logist
   return dt == TO_F32 && logistic_only && T == 8 && M >= 4 && M <= 16 && *std::max_element(widths, widths + L + 1) <= 64;
 }
 
-to_status to_rnn_stack_minibatch_sgd(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
-                                     const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
-                                     int64_t n_idx, const int64_t* idx_or_null, int64_t minibatch, double rate_state,
-                                     double rate_params, to_tensor losses_or_null) {
-  API_BEGIN
-  const char* fn = "to_rnn_stack_minibatch_sgd";
+// Sequences of their own lengths (to_rnn_stack_minibatch_sgd_ragged): update k is to_rnn_stack_sgd_ragged's on its minibatch
+// with the gathered lengths; the rows behind a sequence's length are padding, never read.  Route A: the same gather, the
+// lengths gathered on the host, rnn_stack_ragged.  Route B: rnn_minibatch_ragged.hip on packed rows, losses zeroed up front.
+// The automatic rule, as for the dense entry: route B exactly on the scanned rows where tools/rnn_minibatch_ragged_scan.py found
+// it ahead of BOTH route A and the caller's loop of to_batch_gather + to_rnn_stack_sgd_ragged by more than the row's run-to-run
+// spread (profiles/rnn_minibatch_ragged_scan.txt: fp32, 256 sequences padded to T, lengths uniform in 1 .. T, logistic states,
+// us an update caller / A / B):
+//   T = 8, M = 4 and 16:  5 -> 7 -> 5: 131 / 103 / 45 and 135 / 109 / 58;  64 -> 32 -> 10: 137 / 110 / 63 and 146 / 121 / 79;
+//                         64 -> 64 -> 10: 146 / 119 / 87 and 157 / 132 / 106 (spreads 1 - 5 %)
+//                                                          -> fp32, T = 8, 4 <= M <= 16, no width (the input's included) above 64
+// Where it did NOT win, and automatic is route A: T = 8, M = 64 (5 -> 7 -> 5: 133 against 135, within the 8 % spread; 185 against
+// 124 at H = 32, 258 against 142 at H = 64); every row at T = 64, 1.8x to 6x behind (305 against 172 at 5 -> 7 -> 5, M = 4; 2095
+// against 344 at H = 64, M = 64) although it packs 64 - 95 % of the dense layout's rows: as in the dense kernel the serial
+// recurrences and the update's row-long reductions read the tape from global memory with eight waves.  The rule does not look at
+// the lengths.  NOT MEASURED, and on route A under mode 1: fp64, tanh states or hidden layers, any other T, M below 4; other
+// length distributions were not scanned (with every length T the layout is the dense kernel's, whose scan names the same rows).
+static int64_t g_rnn_minibatch_ragged_persistent_runs = 0, g_rnn_minibatch_ragged_step_runs = 0;
+static bool rnn_minibatch_ragged_auto(int dt, int L, const int64_t* widths, bool logistic_only, int64_t M, int64_t T) {
+  return dt == TO_F32 && logistic_only && T == 8 && M >= 4 && M <= 16 && *std::max_element(widths, widths + L + 1) <= 64;
+}
+
+// the dense entry (ragged false: lens is not looked at) and the ragged one
+static void rnn_minibatch_sgd(const char* fn, int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                              const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X,
+                              to_tensor Y, bool ragged, const int64_t* lens, int64_t n_idx, const int64_t* idx, int64_t minibatch,
+                              double rate_state, double rate_params, to_tensor losses, int64_t& persistent_runs,
+                              int64_t& step_runs) {
   const std::string F = std::string(fn) + ": ";
-  const int64_t* idx = idx_or_null;
-  const to_tensor losses = losses_or_null;
   require_init();
   no_capture(fn);
   NONNULL(state_act); NONNULL(s); NONNULL(ws); NONNULL(w); NONNULL(b); NONNULL(X); NONNULL(Y);
@@ -1120,15 +1139,28 @@ to_status to_rnn_stack_minibatch_sgd(int n_layers, const int* state_act, const t
       bad = bad || stack_overlap(losses, s[l]) || stack_overlap(losses, ws[l]) || stack_overlap(losses, w[l]) || stack_overlap(losses, b[l]);
     TO_CHECK(!bad, TO_ERR_ARG, F + "losses overlaps X, Y or a parameter");
   }
-  // The route (rnn_minibatch_auto above).
+  if (ragged) {
+    NONNULL(lens);
+    for (int64_t q = 0; q < N; ++q)
+      TO_CHECK(lens[q] >= 1 && lens[q] <= T, TO_ERR_SHAPE,
+               F + "lens[" + std::to_string(q) + "] = " + std::to_string(lens[q]) + " is outside 1 .. T = " + std::to_string(T));
+  }
+  // The route (rnn_minibatch_auto / rnn_minibatch_ragged_auto above).
   RnnMinibatchPlan plan;
   bool persistent = false;
+  std::vector<int> sched;   // ragged, route B: rnn_minibatch_ragged_schedule's tables
   if (g_rnn_minibatch_persistent != 0 && n_layers <= RNN_GEN_MAX_LAYERS) {
     const RnnShape sh(n_layers, X->dims[1], state_act, w);
     bool logistic_only = chk.hk == ACT_KIND_LOGISTIC;
     for (int l = 0; l < n_layers; ++l) logistic_only = logistic_only && state_act[l] != TO_ACT_TANH;
     persistent = rnn_minibatch_plan(dt, n_layers, sh.widths, sh.stateful, M, T, &plan) &&
-                 (g_rnn_minibatch_persistent == 2 || rnn_minibatch_auto(dt, n_layers, sh.widths, logistic_only, M, T));
+                 (g_rnn_minibatch_persistent == 2 ||
+                  (ragged ? rnn_minibatch_ragged_auto : rnn_minibatch_auto)(dt, n_layers, sh.widths, logistic_only, M, T));
+    if (persistent && ragged) {   // the tape: the most rows a minibatch of this call packs
+      int64_t max_rows = 0;
+      persistent = rnn_minibatch_ragged_schedule(M, n_idx, idx, lens, &sched, &max_rows);
+      plan.tape_elems = max_rows * plan.rec;
+    }
   }
 
   RnnStackArgs all{RnnMode::Sgd, n_layers, state_act, s, ws, w, b, hidden_act, out_act, X, loss, Y};
@@ -1160,15 +1192,24 @@ to_status to_rnn_stack_minibatch_sgd(int n_layers, const int* state_act, const t
     Holder order, tape(new_tensor(1, &plan.tape_elems, 0, dt));
     o.tape = tape.t->ptr;
     o.X = X->ptr; o.Y = Y->ptr; o.losses = losses ? losses->ptr : nullptr;
-    if (idx) o.idx = upload(idx, n_idx, order);
     o.n_idx = n_idx; o.M = M; o.T = T;
     o.hidden_kind = chk.hk;
     o.softmax = out_act == TO_ACT_SOFTMAX;
     o.rate_state = rate_state; o.rate_params = rate_params;
-    launch_rnn_minibatch(dt, plan, o, S());
-    TO_HIP(hipStreamSynchronize(S()));   // the order and the tape go back to the pool
-    g_rnn_minibatch_persistent_runs++;
+    if (ragged) {
+      const int64_t nw = (int64_t)sched.size();   // int32 in a float-typed pool buffer
+      order.t = new_tensor(1, &nw, 0);
+      host_to_device(order.t->ptr, sched.data(), sched.size() * sizeof(int), S());
+      if (losses) launch_fill(dt, losses->ptr, n_idx * T, 0.0, S());   // +0.0 at the padding
+      launch_rnn_minibatch_ragged(dt, plan, o, static_cast<const int*>(order.t->ptr), S());
+    } else {
+      if (idx) o.idx = upload(idx, n_idx, order);
+      launch_rnn_minibatch(dt, plan, o, S());
+    }
+    TO_HIP(hipStreamSynchronize(S()));   // the order (the schedule) and the tape go back to the pool
+    persistent_runs++;
   } else {
+    std::vector<int64_t> lk((size_t)M);   // ragged: this minibatch's lengths
     for (int64_t k = 0; k < n_steps; ++k) {
       const int64_t rows = k + 1 == n_steps ? tail : M;
       Holder xk, yk, order;
@@ -1182,13 +1223,47 @@ to_status to_rnn_stack_minibatch_sgd(int n_layers, const int* state_act, const t
         xk.t = new_view(X, X->rank, X->dims, X->strides, rows, X->bstride, k * M * X->bstride);
         yk.t = new_view(Y, Y->rank, Y->dims, Y->strides, rows, Y->bstride, k * M * Y->bstride);
       }
-      Holder lk(losses ? new_view(losses, 1, losses->dims, losses->strides, rows, losses->bstride, k * M * losses->bstride) : nullptr);
+      Holder lv(losses ? new_view(losses, 1, losses->dims, losses->strides, rows, losses->bstride, k * M * losses->bstride) : nullptr);
       RnnStackArgs a{RnnMode::Sgd, n_layers, state_act, s, ws, w, b, hidden_act, out_act, xk.t, loss, yk.t};
-      a.losses = lk.t; a.rate_state = rate_state; a.rate_params = rate_params; a.fn = fn;
-      rnn_stack_dense(a);
+      a.losses = lv.t; a.rate_state = rate_state; a.rate_params = rate_params; a.fn = fn;
+      if (ragged) {
+        for (int64_t q = 0; q < rows; ++q) lk[q] = lens[idx ? idx[k * M + q] : k * M + q];
+        rnn_stack_ragged(a, lk.data());
+      } else {
+        rnn_stack_dense(a);
+      }
     }
-    g_rnn_minibatch_step_runs++;
+    step_runs++;
   }
+}
+
+to_status to_rnn_stack_minibatch_sgd(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws, const to_tensor* w,
+                                     const to_tensor* b, int hidden_act, int out_act, int loss, to_tensor X, to_tensor Y,
+                                     int64_t n_idx, const int64_t* idx_or_null, int64_t minibatch, double rate_state,
+                                     double rate_params, to_tensor losses_or_null) {
+  API_BEGIN
+  rnn_minibatch_sgd("to_rnn_stack_minibatch_sgd", n_layers, state_act, s, ws, w, b, hidden_act, out_act, loss, X, Y, false, nullptr,
+                    n_idx, idx_or_null, minibatch, rate_state, rate_params, losses_or_null, g_rnn_minibatch_persistent_runs,
+                    g_rnn_minibatch_step_runs);
+  API_END
+}
+
+to_status to_rnn_stack_minibatch_sgd_ragged(int n_layers, const int* state_act, const to_tensor* s, const to_tensor* ws,
+                                            const to_tensor* w, const to_tensor* b, int hidden_act, int out_act, int loss,
+                                            to_tensor X, to_tensor Y, const int64_t* lens, int64_t n_idx,
+                                            const int64_t* idx_or_null, int64_t minibatch, double rate_state,
+                                            double rate_params, to_tensor losses_or_null) {
+  API_BEGIN
+  rnn_minibatch_sgd("to_rnn_stack_minibatch_sgd_ragged", n_layers, state_act, s, ws, w, b, hidden_act, out_act, loss, X, Y, true,
+                    lens, n_idx, idx_or_null, minibatch, rate_state, rate_params, losses_or_null,
+                    g_rnn_minibatch_ragged_persistent_runs, g_rnn_minibatch_ragged_step_runs);
+  API_END
+}
+
+to_status to_rnn_minibatch_ragged_stats(int64_t* persistent_runs, int64_t* per_minibatch_runs) {
+  API_BEGIN
+  if (persistent_runs) *persistent_runs = g_rnn_minibatch_ragged_persistent_runs;
+  if (per_minibatch_runs) *per_minibatch_runs = g_rnn_minibatch_ragged_step_runs;
   API_END
 }
 

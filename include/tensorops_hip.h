@@ -304,7 +304,8 @@ enum {
   TO_GEMM_FAMILY_F64 = 9,
   TO_GEMM_FAMILY_NAIVE = 10,
   TO_GEMM_FAMILY_KW16_64 = 11, /* the fp64 tile menu; asked just ahead of KW64, numbered last so that 0 .. 10 keep their meaning */
-  TO_GEMM_FAMILY_FEWRHS = 12   /* few right-hand sides; asked just behind GEMV, numbered last so that 0 .. 11 keep their meaning */
+  TO_GEMM_FAMILY_FEWRHS = 12,  /* few right-hand sides; asked just behind GEMV, numbered last so that 0 .. 11 keep their meaning */
+  TO_GEMM_FAMILY_SPLIT = 13    /* fp32 on the bf16 MFMA, three pieces an operand; asked behind the skinny-K families, numbered last likewise */
 };
 enum { TO_GEMM_EPI_BIAS = 1, TO_GEMM_EPI_ACT = 2, TO_GEMM_EPI_DACT = 4, TO_GEMM_EPI_BETA = 8, TO_GEMM_EPI_ROWSUM = 16 };
 /* The problem: C[m, n] = A[m, k] . B[k, n] of `dtype`, `batch` >= 1 of them (reduce_batch: summed into one C), each operand
@@ -336,6 +337,22 @@ to_status to_set_gemm_f64_menu(int mode, int tile, int* previous_mode_or_null);
  * kernel can run.  splits: -1 the launcher's rule, 1 .. 256 forced (clamped to K).  Process-wide, for contractions planned
  * from now on; *previous_mode_or_null gets the mode it replaces.  Anything else: TO_ERR_ARG, nothing changed. */
 to_status to_set_gemm_few_rhs(int mode, int splits, int* previous_mode_or_null);
+/* Split-bf16 fp32 GEMM (csrc/gemm_split.hip): every fp32 operand element is written as the exact sum of three bf16 pieces
+ * (8 + 8 + 8 mantissa bits, truncated, so no piece overflows) by one pre-pass launch, and the product is 6 or 9 bf16 MFMA
+ * products a k step into one fp32 accumulator, low-order products first; no atomics, no split of K: a repeated call gives
+ * the same bits.  fp32, batch 1, any storage order of A and B, any M, N, K >= 1 that the
+ * gemv (M or N = 1, K = 1, K < 16 under a large C), few-rhs and skinny-K families, asked first, do not take; alpha / beta Cin / bias / logistic / tanh
+ * carried; no act', row sums, loss head.  Scratch: 6 bytes an element of A and B padded to 256 x 16 / 16 x 128 tiles, from the
+ * pool; above 1 GiB of it the family does not apply.  Non-finite operands: an output element whose exact value is non-finite
+ * because of an inf / NaN operand element comes out non-finite, possibly NaN where the fp32 chain gives +-inf; finite
+ * operands with a finite exact result never give a non-finite.  mode 0: off (DEFAULT: every contraction takes exactly the
+ * route it took before the kernel existed); 1: automatic -- only the rows tools/gemm_split_scan.py measured ahead
+ * (profiles/gemm_split_scan.txt: 4096^3 at 1.30 x and 8192^3 at 1.38 x today's route with six products, 8192^3 alone with nine;
+ * every smaller scanned shape is BEHIND today's route; everything unscanned keeps its route, and so do those shapes with an
+ * operand stored transposed, with an epilogue, or as a block of a larger product: only the plain row-major product was scanned); 2: wherever the kernel can run.  products: 6 (drops
+ * a1 b2, a2 b1, a2 b2: ~1e-8 relative), 9, or -1 for the default, 6.  Process-wide, for contractions planned from now on;
+ * *previous_mode_or_null gets the mode it replaces.  Anything else: TO_ERR_ARG, nothing changed. */
+to_status to_set_gemm_f32_split(int mode, int products, int* previous_mode_or_null);
 /* stream capture of everything enqueued between begin/end into a HIP graph */
 to_status to_graph_begin(void);
 to_status to_graph_end(to_graph* out);

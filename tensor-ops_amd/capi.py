@@ -14,7 +14,7 @@ i64p = C.POINTER(C.c_int64)
 TO_F32 = 0
 TO_F64 = 1
 # TO_GEMM_FAMILY_* by number, TO_GEMM_EPI_* by name (to_gemm_route_query)
-GEMM_FAMILIES = ("gemv", "t32", "skinnyk", "skinnyk64", "kw16", "kw", "kw64", "small", "mfma", "f64", "naive", "kw16_64", "fewrhs")
+GEMM_FAMILIES = ("gemv", "t32", "skinnyk", "skinnyk64", "kw16", "kw", "kw64", "small", "mfma", "f64", "naive", "kw16_64", "fewrhs", "split")
 # TO_EW_FAMILY_* / TO_EW_FORM_* by number (to_ewise_route_query)
 EW_FAMILIES = ("functor", "jit", "vm")
 EW_FORMS = ("scalar", "vec", "stream")
@@ -162,6 +162,7 @@ SIGNATURES = {
     "to_set_rnn_wide": [C.c_int, C.POINTER(C.c_int)],
     "to_set_gemm_f64_menu": [C.c_int, C.c_int, C.POINTER(C.c_int)],
     "to_set_gemm_few_rhs": [C.c_int, C.c_int, C.POINTER(C.c_int)],
+    "to_set_gemm_f32_split": [C.c_int, C.c_int, C.POINTER(C.c_int)],
     "to_set_rnn_wide_groups": [C.c_int, C.POINTER(C.c_int)],
     "to_rnn_wide_stats": [i64p, i64p],
     "to_rnn_wide_plan_query": [C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),

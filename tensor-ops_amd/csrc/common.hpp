@@ -306,6 +306,10 @@ bool gemm_fewrhs_applicable(const GemmProblem& p);  // gemm_fewrhs.hip: 2 .. 32 
 bool gemm_fewrhs_everywhere(const GemmProblem& p);  // ... and the switch is at mode 2 (wherever the kernel can)
 void launch_gemm_fewrhs(const GemmProblem& p, hipStream_t s);
 bool gemm_fewrhs_set(int mode, int splits, int* previous_mode);  // false: mode or splits out of range, nothing changed
+bool gemm_split_applicable(const GemmProblem& p);  // gemm_split.hip: fp32 as three bf16 pieces an operand on the bf16 MFMA (to_set_gemm_f32_split; off by default)
+bool gemm_split_everywhere(const GemmProblem& p);  // ... and the switch is at mode 2 (wherever the kernel can)
+void launch_gemm_split(const GemmProblem& p, hipStream_t s);
+bool gemm_split_set(int mode, int products, int* previous_mode);  // false: mode or products out of range, nothing changed
 bool gemm_skinnyk64_applicable(const GemmProblem& p);  // gemm_skinnyk_f64.hip: config 5's shape class in Double
 void launch_gemm_skinnyk64(const GemmProblem& p, hipStream_t s);
 struct GemmEpilogue {

@@ -56,6 +56,10 @@ void gemm_plan(const GemmProblem& p, GemmLeaves& out, bool sub) {
   // wave-split kernel, whose rule for "more than 1,024 tiles the big tiles do not fit" would take these too (0.150 -> 0.217 ms)
   if (gemm_skinnyk_applicable(p)) return out.push(GEMM_SKINNYK, p, sub);
   if (gemm_skinnyk64_applicable(p)) return out.push(GEMM_SKINNYK64, p, sub);
+  // fp32 as three bf16 pieces an operand, 6 or 9 products on the bf16 matrix pipe, ahead of every fp32 MFMA family
+  // (to_set_gemm_f32_split; never with the switch off.  Mode 1 knows whole scanned problems only: a block or a K head of a larger
+  //  product that happens to have a scanned shape keeps its route)
+  if (gemm_split_applicable(p) && (!sub || gemm_split_everywhere(p))) return out.push(GEMM_SPLIT, p, sub);
   // a few hundred 64x64 tiles: the K loop split over the waves of each tile's workgroup (K tails included)
   // ... on the tile shape whose count fits the CUs: 48x48 / 48x64 / 64x48 / 80x80 where that beats the 64x64 routes (768^3: 256
   // tiles of 48x48 instead of 144 of 64x64 split three ways)
@@ -133,6 +137,7 @@ void run_gemm(const GemmProblem& p) {
       case GEMM_T32: launch_gemm_t32(q, S()); break;
       case GEMM_SKINNYK: launch_gemm_skinnyk(q, S()); break;
       case GEMM_SKINNYK64: launch_gemm_skinnyk64(q, S()); break;
+      case GEMM_SPLIT: launch_gemm_split(q, S()); break;
       case GEMM_KW16: launch_gemm_kw16(q, S()); break;
       case GEMM_KW: launch_gemm_kw(q, S()); break;
       case GEMM_KW16_64: launch_gemm_kw64_menu(q, S()); break;
@@ -177,6 +182,7 @@ bool gemm_small_route(const GemmProblem& p) {
   //  768^3 -- under 200 tiles of 64x64 -- keep the small-first launch for a fused epilogue)
   if (gemm_kw64_menu_everywhere(p)) return false;
   if (gemm_fewrhs_everywhere(p)) return false;   // (to_set_gemm_few_rhs at mode 2, likewise: through the plan, epilogue carried)
+  if (gemm_split_everywhere(p)) return false;    // (to_set_gemm_f32_split at mode 2, likewise)
   // (a few tiles under a very long K -- a weight gradient over a data set, 300 x 60000 x 784: one workgroup a tile here whatever K
   //  is, 400 us; 291 split over workgroups in gemm_kwave.hip, which carries alpha / beta C / bias / activation but no row sums)
   if (p.K >= 8192 && !p.rowsum && !p.loss_rows && !p.tail_out && gemm_kw_long_k(p)) return false;
@@ -190,6 +196,7 @@ bool gemm_epilogue_ok(const GemmProblem& p) {
   if (p.M == 0 || p.N == 0 || p.K == 0 || p.batch == 0) return false;
   if (gemm_small_route(p) || gemm_skinnyk_applicable(p) || gemm_skinnyk64_applicable(p) || gemv_form(p)) return true;
   if (gemm_fewrhs_applicable(p)) return true;   // (never with the switch off; asks for no dact, so the kernel carries what is left)
+  if (gemm_split_everywhere(p)) return true;    // (mode 2, likewise; it refuses what the plan's gemv question takes first.  Mode 1 changes no answer: it takes plain products only)
   if (p.dtype == TO_F64) return gemm_kw64_menu_applicable(p) || gemm_kw64_applicable(p);
   const GemmFamily f = gemm_tiled_family(p);
   return f == GEMM_SMALL || f == GEMM_MFMA;
@@ -242,6 +249,14 @@ extern "C" to_status to_set_gemm_few_rhs(int mode, int splits, int* previous_mod
   API_BEGIN
   TO_CHECK(gemm_fewrhs_set(mode, splits, previous_mode_or_null), TO_ERR_ARG,
            "to_set_gemm_few_rhs: mode 0 (off), 1 (automatic) or 2 (wherever the kernel can); splits -1 (the launcher's rule) or 1 .. 256");
+  API_END
+}
+
+extern "C" to_status to_set_gemm_f32_split(int mode, int products, int* previous_mode_or_null) {
+  using namespace to;
+  API_BEGIN
+  TO_CHECK(gemm_split_set(mode, products, previous_mode_or_null), TO_ERR_ARG,
+           "to_set_gemm_f32_split: mode 0 (off), 1 (automatic) or 2 (wherever the kernel can); products 6, 9 or -1 (the default, 6)");
   API_END
 }
 

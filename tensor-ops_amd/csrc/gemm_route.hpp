@@ -23,6 +23,7 @@ enum GemmFamily {
   GEMM_NAIVE = TO_GEMM_FAMILY_NAIVE,          // reduce_layout.hip: one thread per output element
   GEMM_KW16_64 = TO_GEMM_FAMILY_KW16_64,      // gemm_kwave_f64.hip, the fp64 tile menu (asked just ahead of GEMM_KW64; numbered last: the recorded table keeps 0 .. 10)
   GEMM_FEWRHS = TO_GEMM_FAMILY_FEWRHS,        // gemm_fewrhs.hip (asked just behind GEMM_GEMV, to_set_gemm_few_rhs only; numbered last likewise)
+  GEMM_SPLIT = TO_GEMM_FAMILY_SPLIT,          // gemm_split.hip (asked behind the skinny-K families, to_set_gemm_f32_split only; numbered last likewise)
 };
 
 // A plan's leaves -- one launch each: a kernel family and the (sub-)problem it gets -- in launch order, held inline (no heap

@@ -762,6 +762,14 @@ class HipT:
         return prev.value
 
     @staticmethod
+    def set_gemm_f32_split(mode, products=-1):
+        """to_set_gemm_f32_split: fp32 products as three bf16 pieces an operand on the bf16 MFMA: 0 off (default), 1 automatic, 2
+        wherever the kernel can; products 6, 9 or -1 (the default, 6); returns the previous mode"""
+        prev = C.c_int()
+        check(lib().to_set_gemm_f32_split(int(mode), int(products), C.byref(prev)))
+        return prev.value
+
+    @staticmethod
     def rnn_wide_groups(min_groups):
         """to_set_rnn_wide_groups: 0 the plan's own G, else at least this many workgroups a group; returns the previous
         setting"""
